@@ -69,15 +69,61 @@ def parse():
                          "parameter tree's gradients through allreduce_gradients(like=ps), then "
                          "Optimisers.update! (fused multi-tensor kernels)")
     ap.add_argument("--miopen-find", type=int, default=int(os.environ.get("BENCH_MIOPEN_FIND", "1")))
-    ap.add_argument("--choices", default=os.environ.get("BENCH_CHOICES", "measure"), choices=["measure", "shipped"],
-                    help="measure (default): per-shape kernel choices (ours vs MIOpen, tile configs) timed at the "
-                         "first step; shipped: read tuning/kernel_choices/<model>_bs<batch>.jsonl (no first-step "
-                         "timing, no run-to-run flips; measured 0.8%% slower than a fresh measurement on one box, "
-                         "profiles/r4i_bench_choices_ab.jsonl)")
+    ap.add_argument("--choices", default=os.environ.get("BENCH_CHOICES", "shipped"), choices=["measure", "shipped"],
+                    help="shipped (default): read tuning/kernel_choices/<model>_bs<batch>.jsonl where the model and "
+                         "batch have one (no first-step timing, which takes ~45 s of MIOpen finds for ResNet-50; no "
+                         "run-to-run flips; measured 0.8%% slower than a fresh measurement on one box, "
+                         "profiles/r4i_bench_choices_ab.jsonl); shapes without a record are timed at the first "
+                         "step; measure: time every per-shape kernel choice (ours vs MIOpen, tile configs) at the "
+                         "first step")
     ap.add_argument("--dump-choices", default="", help="write the per-shape kernel choices in use to this file")
     ap.add_argument("--tunableop", default=os.environ.get("BENCH_TUNABLEOP", "auto"), choices=["auto", "off"],
                     help="auto: use the shipped hipBLASLt/rocBLAS GEMM selections (tuning/tunableop/<model>.csv)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what one step of the timed path computes from the seeded "
+                         "initial model and optimiser state to DIR/<name>.npy (float32): what the step hands "
+                         "back, the loss, and a fixed seeded sample of the parameters and buffers it updated. "
+                         "The state is put back and the step run once more, untimed: the kernels sum BatchNorm statistics and split-K "
+                         "partials with float atomics, and the training steps before it amplify that "
+                         "rounding-level noise until two runs share no digit (--api ddp)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the event-timed steps after the "
+                         "timed region that measure the exposed gradient-allreduce wait (exposed_comm_ms)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 4096  # elements kept per tensor in the parameter / buffer samples of --dump-outputs
+
+
+def _sample(named, seed: int):
+    """A fixed sample of every floating-point tensor of ``named`` as one flat fp32 array: the whole
+    tensor when it has at most DUMP_SAMPLE elements, else DUMP_SAMPLE positions drawn by a CPU
+    generator seeded with ``seed`` and the tensor's place in the list (the same positions in every
+    run and every build)."""
+    parts = []
+    for i, (_, t) in enumerate(named):
+        if not t.is_floating_point():
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(seed + i)
+            flat = flat[torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
+def dump_outputs(path: str, model, loss) -> None:
+    """``--dump-outputs``: what a caller of one step receives, as ``<path>/<name>.npy`` (float32,
+    about 1 MB): ``loss`` (the step's return value) and the model it updated, ``params_sample`` /
+    ``buffers_sample`` (see :func:`_sample`)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(),
+              "params_sample": _sample(list(model.named_parameters()), 1000),
+              "buffers_sample": _sample(list(model.named_buffers()), 2000)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.contiguous().numpy().astype(np.float32, copy=False))
 
 
 def _gelu_form() -> str:
@@ -274,6 +320,9 @@ def main():
         if args.graph:
             print("bench.py: --graph needs --api ddp", file=sys.stderr)
             return 2
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs needs --api ddp", file=sys.stderr)
+            return 2
         ddp = Functional(FluxMPI, O, model, rule)
     else:
         ovo = args.overlap_opt
@@ -281,6 +330,12 @@ def main():
             ovo = int((world > 1 or args.force_comm) and not args.graph and not args.no_overlap)
         ddp = DDP(model, rule, average=True, overlap=not args.no_overlap, force_comm=args.force_comm,
                   overlap_opt=bool(ovo))
+
+    # --dump-outputs: the seeded initial state (parameters, buffers, masters, moments, step count)
+    initial = None
+    if args.dump_outputs:
+        initial = ddp.state_dict()  # the module's entries are the live tensors: keep copies
+        initial["module"] = {k: v.detach().clone() for k, v in initial["module"].items()}
 
     B = args.batch
     gx = torch.Generator(device=dev).manual_seed(rank)
@@ -344,9 +399,16 @@ def main():
         per_rank = [dt]
     dt_max = max(per_rank)
     lval = float(loss.item())
+    if args.dump_outputs:
+        # after the timed region: the step of the timed path once more, from the seeded initial state
+        ddp.load_state_dict(initial)
+        first_loss = step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, first_loss)
     exposed = None
-    if ddp.communicate and not args.graph and args.api == "ddp":
-        # after the timed region: a few steps with event timing around the gradient-allreduce
+    if args.full and ddp.communicate and not args.graph and args.api == "ddp":
+        # --full, after the timed region: a few steps with event timing around the gradient-allreduce
         # wait (exposed = not hidden behind backward), max over ranks
         ddp.timing = True
         for _ in range(3):

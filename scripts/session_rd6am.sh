@@ -5,6 +5,6 @@ rm -f "$OUT/steps.log" "$OUT/bench_results.jsonl"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 cd /tmp
 step prof_vitc 300 0 rocprofv3 --kernel-trace --stats -d "$OUT/prof_vitc_rd6am" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --model vit_b16 --steps 5 --warmup 5 --force-comm
+  python3 "$ROOT/bench.py" --model vit_b16 --steps 5 --warmup 5 --force-comm --full
 cd "$ROOT"
 echo done

@@ -12,6 +12,6 @@ B="python bench.py --steps 20 --warmup 10"
 step deq_cifar 300 0 $B --model deq_cifar --force-comm
 cd /tmp
 step prof_deqc 300 0 rocprofv3 --kernel-trace --stats -d "$OUT/prof_deqc_rd6b" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --model deq_cifar --steps 5 --warmup 5 --force-comm
+  python3 "$ROOT/bench.py" --model deq_cifar --steps 5 --warmup 5 --force-comm --full
 cd "$ROOT"
 echo done

@@ -7,7 +7,7 @@ rm -f "$OUT/steps.log" "$OUT/bench_results.jsonl"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 step rehearsal4 600 0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
   --master-port 29517 bench.py --gpus 4 --same-device --steps 5 --warmup 3
-B="python bench.py --steps 20 --warmup 10 --force-comm"
+B="python bench.py --steps 20 --warmup 10 --force-comm --full"
 for m in vit_b16 resnet50; do
   step emu_ov1_$m 300 0 $B --model $m --emulate-comm 64:300 --overlap-opt 1
   step emu_ov0_$m 300 0 $B --model $m --emulate-comm 64:300 --overlap-opt 0

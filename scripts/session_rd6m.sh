@@ -21,6 +21,6 @@ cd /tmp
 step prof_r50 300 0 rocprofv3 --kernel-trace --stats -d "$OUT/prof_r50_rd6m" -o run --output-format csv -- \
   python3 "$ROOT/bench.py" --steps 5 --warmup 5
 step prof_deqc 300 0 rocprofv3 --kernel-trace --stats -d "$OUT/prof_deqc_rd6m" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --model deq_cifar --force-comm --steps 5 --warmup 5
+  python3 "$ROOT/bench.py" --model deq_cifar --force-comm --full --steps 5 --warmup 5
 cd "$ROOT"
 echo done

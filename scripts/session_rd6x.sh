@@ -14,6 +14,6 @@ step deq_cifar 300 0 $B --model deq_cifar
 step deq_cifar_comm 300 0 $B --model deq_cifar --force-comm
 cd /tmp
 step prof_deqc 300 0 rocprofv3 --kernel-trace --stats -d "$OUT/prof_deqc_rd6x" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --model deq_cifar --force-comm --steps 5 --warmup 5
+  python3 "$ROOT/bench.py" --model deq_cifar --force-comm --full --steps 5 --warmup 5
 cd "$ROOT"
 echo done
