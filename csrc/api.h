@@ -31,7 +31,9 @@ struct AdamHyper {
   float weight_decay;  // Optimisers.jl WeightDecay after Adam (AdamW = chain)
   float grad_scale;    // multiplies the incoming gradient (e.g. 1/world for mean)
   const float* dev;    // optional device hyper block {lr, beta1^t, beta2^t} (graph mode)
-  const float* dev_gscale;  // optional device gradient scale (e.g. 1/loss_scale)
+  const float* dev_gscale;  // optional device gradient scale (e.g. 1/loss_scale, the global-norm clip)
+  const void* tscale = nullptr;  // optional device scale per leaf of the call (ClipNorm), fp32 (fp64 params: fp64)
+  float clip_delta = 0.f;        // ClipGrad: clamp the scaled gradient to [-delta, delta]; 0: off
 };
 
 // master: optional fp32 master weights (mixed precision); when given, param is
@@ -48,12 +50,29 @@ struct SgdHyper {
   float lr, momentum, weight_decay, grad_scale;
   int nesterov;  // 0: heavy ball (Optimisers.Momentum), 1: Optimisers.Nesterov
   const float* dev_lr;
+  const float* dev_gscale = nullptr;  // as in AdamHyper
+  const void* tscale = nullptr;
+  float clip_delta = 0.f;
 };
 // buf: momentum buffers (ignored when momentum == 0 -> Optimisers.Descent).
 void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
             const std::vector<uintptr_t>& buf, const std::vector<uintptr_t>& master,
             const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype,
             const SgdHyper& h, hipStream_t stream);
+
+// ---- gradient clipping: deterministic multi-tensor sum of squares ------------------
+// Two launches per group of leaves, no float atomics (bit-identical from run to run):
+// sumsq[i] = sum(grad[i]^2) and, when scale != nullptr,
+// scale[i] = min(1, omega / (grad_scale * sqrt(sumsq[i]))) with torch.clamp's edge values
+// (norm 0 -> 1, NaN -> NaN, inf -> 0). sumsq / scale / partials hold fp32 (fp64 gradients:
+// fp64); partials needs sumsq_partials(numel) entries. A leaf without elements gets 0 / 1.
+int64_t sumsq_partials(const std::vector<int64_t>& numel);
+void mt_leaf_sumsq(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
+                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream);
+// slot[0] = (accumulate ? slot[0] : 0) + sum_i sumsq[i] (fixed order); slot[1] = grad_scale *
+// sqrt(slot[0]) (the global gradient norm); slot[2] = omega > 0 ? min(1, omega / slot[1]) : 1.
+void clip_total(const void* sumsq, int64_t n, int acc_dtype, float* slot, int accumulate, float omega,
+                float grad_scale, hipStream_t stream);
 
 // ---- BatchNorm (NHWC, channels innermost) + ReLU / residual-add fusions ----------
 // Training forward: per-channel batch statistics over rows = N*H*W, then

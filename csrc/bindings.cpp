@@ -38,15 +38,18 @@ PYBIND11_MODULE(_C, m) {
            const std::vector<uintptr_t>& vv, const std::vector<uintptr_t>& master, const std::vector<int64_t>& numel,
            int p_dtype, int g_dtype, int s_dtype, float lr, float beta1, float beta2, float eps, float bc1,
            float bc2, float weight_decay, float grad_scale, uintptr_t dev_hyper, uintptr_t dev_gscale,
-           uintptr_t stream) {
+           uintptr_t stream, uintptr_t tscale, float clip_delta) {
           AdamHyper h{lr, beta1, beta2, eps, bc1, bc2, weight_decay, grad_scale,
                       reinterpret_cast<const float*>(dev_hyper), reinterpret_cast<const float*>(dev_gscale)};
+          h.tscale = reinterpret_cast<const void*>(tscale);
+          h.clip_delta = clip_delta;
           mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, S(stream));
         },
         py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("master"), py::arg("numel"),
         py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("bc1"), py::arg("bc2"), py::arg("weight_decay"),
-        py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"));
+        py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"),
+        py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f);
   m.def("adam_advance", [](uintptr_t dev, float b1, float b2, uintptr_t stream) {
     adam_advance(reinterpret_cast<float*>(dev), b1, b2, S(stream));
   });
@@ -54,14 +57,35 @@ PYBIND11_MODULE(_C, m) {
         [](const std::vector<uintptr_t>& p, const std::vector<uintptr_t>& g, const std::vector<uintptr_t>& buf,
            const std::vector<uintptr_t>& master, const std::vector<int64_t>& numel, int p_dtype, int g_dtype,
            int s_dtype, float lr, float momentum, float weight_decay, float grad_scale, int nesterov,
-           uintptr_t dev_lr, uintptr_t stream) {
+           uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta) {
           SgdHyper h{lr, momentum, weight_decay, grad_scale, nesterov, reinterpret_cast<const float*>(dev_lr)};
+          h.dev_gscale = reinterpret_cast<const float*>(dev_gscale);
+          h.tscale = reinterpret_cast<const void*>(tscale);
+          h.clip_delta = clip_delta;
           mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, S(stream));
         },
         py::arg("param"), py::arg("grad"), py::arg("buf"), py::arg("master"), py::arg("numel"),
         py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("momentum"),
         py::arg("weight_decay"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"),
-        py::arg("stream"));
+        py::arg("stream"), py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0),
+        py::arg("clip_delta") = 0.f);
+  m.def("sumsq_partials", &sumsq_partials, py::arg("numel"));
+  m.def("mt_leaf_sumsq",
+        [](const std::vector<uintptr_t>& g, const std::vector<int64_t>& numel, int g_dtype, uintptr_t partials,
+           uintptr_t sumsq, uintptr_t scale, float omega, float grad_scale, uintptr_t stream) {
+          mt_leaf_sumsq(g, numel, g_dtype, reinterpret_cast<void*>(partials), reinterpret_cast<void*>(sumsq),
+                        reinterpret_cast<void*>(scale), omega, grad_scale, S(stream));
+        },
+        py::arg("grad"), py::arg("numel"), py::arg("g_dtype"), py::arg("partials"), py::arg("sumsq"),
+        py::arg("scale"), py::arg("omega"), py::arg("grad_scale"), py::arg("stream"));
+  m.def("clip_total",
+        [](uintptr_t sumsq, int64_t n, int acc_dtype, uintptr_t slot, int accumulate, float omega, float grad_scale,
+           uintptr_t stream) {
+          clip_total(reinterpret_cast<const void*>(sumsq), n, acc_dtype, reinterpret_cast<float*>(slot), accumulate,
+                     omega, grad_scale, S(stream));
+        },
+        py::arg("sumsq"), py::arg("n"), py::arg("acc_dtype"), py::arg("slot"), py::arg("accumulate"),
+        py::arg("omega"), py::arg("grad_scale"), py::arg("stream"));
 
   // ---- fused NHWC BatchNorm ------------------------------------------------
   m.def("bn_fwd_train",

@@ -13,6 +13,17 @@
 //   Descent:  x -= lr*g
 //   Momentum: v = rho*v + lr*g ; x -= v
 //   Nesterov: dx = -rho^2*v + (1+rho)*lr*g ; v = rho*v - lr*g ; x -= dx
+// Every rule first forms its gradient, in compute precision, as
+//   g = clamp(g_in * grad_scale [* dev_gscale] [* tscale[leaf]], -delta, delta)   (delta == 0: no clamp)
+// (grad_scale: host, e.g. 1/world; dev_gscale: one device scalar, the global-norm clip;
+// tscale: one device scalar per leaf of the call, the ClipNorm chain; delta: ClipGrad).
+//
+// Gradient clipping needs norms first: mt_leaf_sumsq is a deterministic two-launch multi-tensor
+// sum of squares (one partial per 4096-element workgroup, then one workgroup per leaf reduces
+// that leaf's partials in a fixed order — no float atomics, so two runs agree bit for bit) whose
+// finish also writes the per-leaf scale min(1, omega / (grad_scale * sqrt(sumsq))); clip_total
+// folds the per-leaf sums into one device slot {sum, norm, scale} for global-norm clipping.
+// Nothing is read back to the host: the whole sequence is HIP-graph capturable.
 //
 // Optional fp32 master weights give the mixed-precision layout (bf16 param +
 // fp32 master/m/v); without them the state dtype equals the parameter dtype,
@@ -41,18 +52,27 @@ struct OptArgs {
   uintptr_t w[kMaxT];  // fp32 master (or 0)
   int64_t numel[kMaxT];
   int32_t start[kMaxT + 1];
+  int32_t tidx[kMaxT];  // position of the leaf in the CALL's lists (per-leaf scales, sums)
+  int64_t pbase;        // workgroups of the call's earlier launches (index of this one's first partial)
   int n;
 };
 
 template <typename P> struct Comp { using type = float; };
 template <> struct Comp<double> { using type = double; };
 
+// clamp(g, -delta, delta) with torch.clamp's NaN behaviour (a NaN stays a NaN); delta == 0: off
+template <typename C>
+__device__ __forceinline__ C clip_grad(C g, C delta) {
+  if (delta > C(0)) g = g < -delta ? -delta : (g > delta ? delta : g);
+  return g;
+}
+
 template <typename P, typename G, typename S, bool MASTER>
 struct AdamElem {
   using C = typename Comp<P>::type;
-  C lr, b1, b2, eps, bc1, bc2, wd, gs;
+  C lr, b1, b2, eps, bc1, bc2, wd, gs, ts, delta;
   __device__ __forceinline__ void operator()(P& p, G g_in, S& m_io, S& v_io, float& w) const {
-    const C g = static_cast<C>(g_in) * gs;
+    const C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     const C m = b1 * static_cast<C>(m_io) + (C(1) - b1) * g;
     const C v = b2 * static_cast<C>(v_io) + (C(1) - b2) * (g * g);
     C x = MASTER ? static_cast<C>(w) : static_cast<C>(p);
@@ -85,6 +105,8 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
   op.lr = lr; op.bc1 = bc1; op.bc2 = bc2;
   op.b1 = h.beta1; op.b2 = h.beta2; op.eps = h.eps; op.wd = h.weight_decay;
   op.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  op.ts = h.tscale ? static_cast<const C*>(h.tscale)[a.tidx[t]] : C(1);
+  op.delta = h.clip_delta;
 
   P* __restrict__ p = reinterpret_cast<P*>(a.p[t]);
   const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
@@ -130,11 +152,11 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
 template <typename P, typename G, typename S, bool MASTER>
 struct SgdElem {
   using C = typename Comp<P>::type;
-  C lr, rho, wd, gs;
+  C lr, rho, wd, gs, ts, delta;
   int mode;  // 0 descent, 1 momentum, 2 nesterov
   __device__ __forceinline__ void operator()(P& p, G g_in, S& buf, float& w) const {
     C x = MASTER ? static_cast<C>(w) : static_cast<C>(p);
-    C g = static_cast<C>(g_in) * gs;
+    C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     if (wd != C(0)) g += wd * x;
     C dx;
     if (mode == 0) {
@@ -156,6 +178,7 @@ struct SgdElem {
 
 template <typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h) {
+  using C = typename Comp<P>::type;
   const int b = blockIdx.x;
   const int t = find_tensor(a.start, a.n, b);
   const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
@@ -163,7 +186,10 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
   const int64_t end = base + kChunk < n ? base + kChunk : n;
   SgdElem<P, G, S, MASTER> op;
   op.lr = h.dev_lr ? *h.dev_lr : h.lr;
-  op.rho = h.momentum; op.wd = h.weight_decay; op.gs = h.grad_scale;
+  op.rho = h.momentum; op.wd = h.weight_decay;
+  op.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  op.ts = h.tscale ? static_cast<const C*>(h.tscale)[a.tidx[t]] : C(1);
+  op.delta = h.clip_delta;
   op.mode = h.momentum == 0.f ? 0 : (h.nesterov ? 2 : 1);
   P* __restrict__ p = reinterpret_cast<P*>(a.p[t]);
   const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
@@ -204,6 +230,107 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
   }
 }
 
+// ---- deterministic multi-tensor sum of squares + clip scales -------------------------------
+// sum over the workgroup, valid in thread 0. Wave level: DPP (fp32) / xor shuffles (fp64), every
+// lane takes part (EXEC full); then the four wave totals through LDS, added in wave order.
+template <typename A>
+__device__ __forceinline__ A block_sum(A v) {
+  __shared__ A wave_tot[kThreads / 64];
+  if constexpr (sizeof(A) == 4) {
+    v = wave_sum_dpp(v);
+  } else {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  A s = wave_tot[0];
+#pragma unroll
+  for (int w = 1; w < kThreads / 64; ++w) s += wave_tot[w];
+  return s;
+}
+
+// launch 1: the job layout of the update kernels; workgroup b writes partials[pbase + b]
+template <typename G>
+__global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, typename Acc<G>::type* __restrict__ partials) {
+  using A = typename Acc<G>::type;
+  const int b = blockIdx.x;
+  const int t = find_tensor(a.start, a.n, b);
+  const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
+  const int64_t n = a.numel[t];
+  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
+  const int tid = threadIdx.x;
+  A acc = A(0);
+  int64_t scalar_from = base;
+  if (aligned16(g)) {
+    const int64_t nvec = (end - base) / kVec;
+#pragma unroll
+    for (int k = 0; k < kIters; ++k) {
+      const int64_t vi = tid + k * kThreads;
+      if (vi < nvec) {
+        G gv[kVec];
+        load8(g + base + vi * kVec, gv);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) {
+          const A x = static_cast<A>(gv[j]);
+          acc += x * x;
+        }
+      }
+    }
+    scalar_from = base + nvec * kVec;
+  }
+  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+    const A x = static_cast<A>(g[i]);
+    acc += x * x;
+  }
+  const A s = block_sum(acc);
+  if (tid == 0) partials[a.pbase + b] = s;
+}
+
+// torch.clamp(omega / nrm, max=1): nrm 0 -> 1, nrm NaN -> NaN, nrm inf -> 0
+template <typename A>
+__device__ __forceinline__ A clip_scale(A omega, A nrm) {
+  const A r = omega / nrm;
+  return r > A(1) ? A(1) : r;
+}
+
+// launch 2: workgroup t adds leaf t's partials in a fixed order (thread i takes partials i,
+// i + 256, ... in sequence, then block_sum) -> sumsq[leaf], scale[leaf]
+template <typename A>
+__global__ __launch_bounds__(kThreads) void mt_sumsq_finish_kernel(OptArgs a, const A* __restrict__ partials,
+                                                                    A* __restrict__ sumsq, A* __restrict__ scale,
+                                                                    float omega, float gs) {
+  const int t = blockIdx.x;
+  const A* __restrict__ p = partials + a.pbase;
+  A acc = A(0);
+  for (int j = a.start[t] + threadIdx.x; j < a.start[t + 1]; j += kThreads) acc += p[j];
+  const A s = block_sum(acc);
+  if (threadIdx.x == 0) {
+    const int leaf = a.tidx[t];
+    sumsq[leaf] = s;
+    if (scale != nullptr) scale[leaf] = clip_scale(static_cast<A>(omega), static_cast<A>(gs) * sqrt(s));
+  }
+}
+
+// one workgroup: slot[0] = (accumulate ? slot[0] : 0) + sum_t sumsq[t] (fixed order),
+// slot[1] = gs * sqrt(slot[0]) (the gradient norm), slot[2] = omega > 0 ? clip scale : 1
+template <typename A>
+__global__ __launch_bounds__(kThreads) void clip_total_kernel(const A* __restrict__ sumsq, int64_t n,
+                                                               float* __restrict__ slot, int accumulate,
+                                                               float omega, float gs) {
+  A acc = A(0);
+  for (int64_t j = threadIdx.x; j < n; j += kThreads) acc += sumsq[j];
+  const A s = block_sum(acc);
+  if (threadIdx.x == 0) {
+    const float total = (accumulate ? slot[0] : 0.f) + static_cast<float>(s);
+    const float nrm = gs * sqrtf(total);
+    slot[0] = total;
+    slot[1] = nrm;
+    slot[2] = omega > 0.f ? clip_scale(omega, nrm) : 1.f;
+  }
+}
+
 __global__ void adam_advance_kernel(float* dev, float b1, float b2) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     dev[1] *= b1;
@@ -222,11 +349,14 @@ void for_each_group(const std::vector<uintptr_t>& p, const std::vector<uintptr_t
   OptArgs a{};
   int n = 0;
   int32_t blocks = 0;
+  int64_t pbase = 0;
   auto flush = [&]() {
     if (n == 0) return;
     a.n = n;
     a.start[n] = blocks;
+    a.pbase = pbase;
     launch(a, blocks);
+    pbase += blocks;
     a = OptArgs{};
     n = 0;
     blocks = 0;
@@ -241,6 +371,7 @@ void for_each_group(const std::vector<uintptr_t>& p, const std::vector<uintptr_t
     a.s2[n] = s2.empty() ? 0 : s2[i];
     a.w[n] = w.empty() ? 0 : w[i];
     a.numel[n] = numel[i];
+    a.tidx[n] = static_cast<int32_t>(i);
     a.start[n] = blocks;
     blocks += static_cast<int32_t>(nb);
     ++n;
@@ -318,6 +449,71 @@ void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& g
     if (!done) throw std::runtime_error("mt_sgd: unsupported dtype combination");
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
+}
+
+int64_t sumsq_partials(const std::vector<int64_t>& numel) {
+  int64_t nb = 0;
+  for (int64_t n : numel)
+    if (n > 0) nb += (n + kChunk - 1) / kChunk;
+  return nb;
+}
+
+namespace {
+template <typename G>
+void leaf_sumsq_impl(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, void* partials,
+                     void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream) {
+  using A = typename Acc<G>::type;
+  bool empty = false;
+  for (int64_t n : numel) empty = empty || n <= 0;
+  if (empty) {
+    // leaves without elements never reach a kernel: sum 0, scale 1 (memset nodes: capturable)
+    FLUXMPI_HIP_CHECK(hipMemsetAsync(sumsq, 0, numel.size() * sizeof(A), stream));
+    if (scale != nullptr) {
+      const A one = A(1);
+      for (size_t i = 0; i < numel.size(); ++i)
+        if (numel[i] <= 0) {
+          if constexpr (sizeof(A) == 4) {
+            FLUXMPI_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(static_cast<A*>(scale) + i),
+                                                __builtin_bit_cast(int, one), 1, stream));
+          } else {  // 1.0 as two 32-bit words, low word first
+            const uint64_t bits = __builtin_bit_cast(uint64_t, one);
+            int* w = reinterpret_cast<int*>(static_cast<A*>(scale) + i);
+            FLUXMPI_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w), static_cast<int>(bits & 0xffffffffu), 1, stream));
+            FLUXMPI_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w + 1), static_cast<int>(bits >> 32), 1, stream));
+          }
+        }
+    }
+  }
+  for_each_group(grad, grad, {}, {}, {}, numel, [&](const OptArgs& a, int blocks) {
+    mt_sumsq_partial_kernel<G><<<blocks, kThreads, 0, stream>>>(a, static_cast<A*>(partials));
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    mt_sumsq_finish_kernel<A><<<a.n, kThreads, 0, stream>>>(a, static_cast<const A*>(partials), static_cast<A*>(sumsq),
+                                                            static_cast<A*>(scale), omega, grad_scale);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+  });
+}
+}  // namespace
+
+void mt_leaf_sumsq(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
+                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream) {
+  switch (g_dtype) {
+    case kF32: leaf_sumsq_impl<float>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
+    case kBF16: leaf_sumsq_impl<bf16>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
+    case kF16: leaf_sumsq_impl<f16>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
+    case kF64: leaf_sumsq_impl<double>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
+    default: throw std::runtime_error("mt_leaf_sumsq: unsupported gradient dtype " + std::to_string(g_dtype));
+  }
+}
+
+void clip_total(const void* sumsq, int64_t n, int acc_dtype, float* slot, int accumulate, float omega,
+                float grad_scale, hipStream_t stream) {
+  if (acc_dtype == kF32)
+    clip_total_kernel<float><<<1, kThreads, 0, stream>>>(static_cast<const float*>(sumsq), n, slot, accumulate, omega, grad_scale);
+  else if (acc_dtype == kF64)
+    clip_total_kernel<double><<<1, kThreads, 0, stream>>>(static_cast<const double*>(sumsq), n, slot, accumulate, omega, grad_scale);
+  else
+    throw std::runtime_error("clip_total: sums are fp32 or fp64");
+  FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace fluxmpi

@@ -30,14 +30,42 @@ def supported(p_dtype, g_dtype, s_dtype, master: bool) -> bool:
     return (p_dtype, g_dtype, s_dtype, master) in _SUPPORTED
 
 
+def _acc_dtype(dt: torch.dtype) -> torch.dtype:
+    """Accumulation / scale precision of a gradient dtype: fp32, or fp64 for fp64."""
+    return torch.float64 if dt == torch.float64 else torch.float32
+
+
+def _tscale_ptr(tscale, idx, ct, n) -> int:
+    """Device address of the per-leaf scales of the leaves ``idx`` of the call, in list order.
+
+    The kernels index the scales by the leaf's position in the list they are handed: the whole
+    call's (one dtype group: the common case), a contiguous run of it, or a gathered copy."""
+    if tscale is None:
+        return 0
+    if tscale.dtype != ct or not tscale.is_contiguous():
+        raise TypeError(f"fused optimiser: tscale must be a contiguous {ct} tensor, got {tscale.dtype}")
+    if tscale.numel() < n:
+        raise ValueError(f"fused optimiser: tscale has {tscale.numel()} entries for {n} leaves")
+    if idx == list(range(idx[0], idx[0] + len(idx))):
+        return tscale.data_ptr() + idx[0] * tscale.element_size()
+    # allocated and consumed on the current stream: the allocator reuses it in stream order
+    return tscale[torch.tensor(idx, device=tscale.device)].data_ptr()
+
+
 def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
           bc1: float, bc2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
-          dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None) -> None:
+          dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
+          tscale: torch.Tensor | None = None, clip_delta: float = 0.0) -> None:
     """In-place fused Adam over lists of tensors.
 
     ``bc1``/``bc2`` are ``1 - beta^t`` (Optimisers.jl keeps ``beta^t`` in the
     state and starts it at ``beta``). ``dev_hyper`` (fp32 ``[lr, beta1^t,
     beta2^t]`` on device) overrides ``lr``/``bc1``/``bc2`` for HIP-graph replay.
+
+    Clipping, applied to the gradient before anything else:
+    ``g = clamp(g * grad_scale * dev_gscale * tscale[i], -clip_delta, clip_delta)`` with
+    ``tscale`` one device scalar per leaf of ``params`` (fp32; fp64 for fp64 parameters; see
+    :func:`sumsq_`) and ``clip_delta == 0`` meaning no clamp.
     """
     if not params:
         return
@@ -59,7 +87,8 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
                       float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
                       float(weight_decay), float(grad_scale),
                       dev_hyper.data_ptr() if dev_hyper is not None else 0,
-                      dev_gscale.data_ptr() if dev_gscale is not None else 0, stream)
+                      dev_gscale.data_ptr() if dev_gscale is not None else 0, stream,
+                      tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -67,15 +96,25 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     adam_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bc1=bc1,
-                    bc2=bc2, weight_decay=weight_decay, grad_scale=grad_scale, masters=masters)
+                    bc2=bc2, weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, tscale=tscale,
+                    clip_delta=clip_delta)
+
+
+def _clip_reference(g, i, tscale, clip_delta):
+    if tscale is not None:
+        g = g * tscale[i].to(g.dtype)
+    if clip_delta:
+        g = torch.clamp(g, -clip_delta, clip_delta)
+    return g
 
 
 def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps, bc1, bc2,
-                    weight_decay=0.0, grad_scale=1.0, masters=None):
+                    weight_decay=0.0, grad_scale=1.0, masters=None, tscale=None, clip_delta=0.0):
     """PyTorch reference of the fused kernel (compute in fp32, or fp64 for fp64 params)."""
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         g = grads[i].to(ct) * grad_scale if grad_scale != 1.0 else grads[i].to(ct)
+        g = _clip_reference(g, i, tscale, clip_delta)
         m = exp_avgs[i].to(ct) * beta1 + (1 - beta1) * g
         v = exp_avg_sqs[i].to(ct) * beta2 + (1 - beta2) * (g * g)
         x = masters[i].to(ct) if masters is not None else p.to(ct)
@@ -103,8 +142,10 @@ def adam_advance_(dev_hyper: torch.Tensor, beta1: float, beta2: float) -> None:
 
 def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: bool = False,
          weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
-         dev_lr: torch.Tensor | None = None) -> None:
-    """Fused Descent / Momentum / Nesterov (Optimisers.jl semantics)."""
+         dev_lr: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
+         tscale: torch.Tensor | None = None, clip_delta: float = 0.0) -> None:
+    """Fused Descent / Momentum / Nesterov (Optimisers.jl semantics); ``dev_gscale``, ``tscale``
+    and ``clip_delta`` as in :func:`adam_` (the clipped gradient is formed before weight decay)."""
     if not params:
         return
     if params[0].is_cuda:
@@ -123,20 +164,24 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
                      [masters[i].data_ptr() for i in idx] if hm else [],
                      [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
                      float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(nesterov)),
-                     dev_lr.data_ptr() if dev_lr is not None else 0, stream)
+                     dev_lr.data_ptr() if dev_lr is not None else 0, stream,
+                     dev_gscale=dev_gscale.data_ptr() if dev_gscale is not None else 0,
+                     tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
         return
     if dev_lr is not None:
         lr = float(dev_lr.reshape(-1)[0])
+    if dev_gscale is not None:
+        grad_scale = grad_scale * float(dev_gscale)
     sgd_reference_(params, grads, bufs, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay,
-                   grad_scale=grad_scale, masters=masters)
+                   grad_scale=grad_scale, masters=masters, tscale=tscale, clip_delta=clip_delta)
 
 
 def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, weight_decay=0.0, grad_scale=1.0,
-                   masters=None):
+                   masters=None, tscale=None, clip_delta=0.0):
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         x = masters[i].to(ct) if masters is not None else p.to(ct)
-        g = grads[i].to(ct) * grad_scale
+        g = _clip_reference(grads[i].to(ct) * grad_scale, i, tscale, clip_delta)
         if weight_decay:
             g = g + weight_decay * x
         if momentum == 0.0:
@@ -155,8 +200,85 @@ def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, wei
         p.copy_(x)
 
 
+def sumsq_partials(grads) -> int:
+    """Entries of the ``partials`` workspace :func:`sumsq_` needs for ``grads`` (one per 4096-element chunk)."""
+    return sum((g.numel() + 4095) // 4096 for g in grads)
+
+
+def sumsq_(grads, out: torch.Tensor, *, scales: torch.Tensor | None = None, omega: float = 0.0,
+           grad_scale: float = 1.0, partials: torch.Tensor | None = None) -> None:
+    """``out[i] = sum(grads[i] ** 2)`` for a list of dense gradients of one dtype, deterministically
+    (two launches per 24 leaves, no float atomics: bit-identical from run to run), and, with
+    ``scales``, the ClipNorm factors ``scales[i] = min(1, omega / (grad_scale * sqrt(out[i])))``
+    — ``torch.clamp(omega / nrm, max=1)``: norm 0 gives 1, NaN gives NaN, inf gives 0.
+
+    ``out`` / ``scales`` / ``partials`` are fp32 (fp64 for fp64 gradients) tensors on the
+    gradients' device with ``len(grads)`` (``partials``: :func:`sumsq_partials`) entries;
+    ``partials`` is scratch, allocated here when not given. No host read: graph-capturable.
+    """
+    if not grads:
+        return
+    gd, n = grads[0].dtype, len(grads)
+    at = _acc_dtype(gd)
+    if any(g.dtype != gd or g.device != grads[0].device for g in grads):
+        raise TypeError("sumsq_: the gradients of one call share one dtype and device")
+    for name, t in (("out", out), ("scales", scales)):
+        if t is not None and (t.dtype != at or t.numel() < n or not t.is_contiguous() or t.device != grads[0].device):
+            raise TypeError(f"sumsq_: {name} must be a contiguous {at} tensor with {n} entries on {grads[0].device}")
+    if grads[0].is_cuda:
+        if gd not in DTYPE_CODE or not gd.is_floating_point:
+            raise TypeError(f"sumsq_: unsupported gradient dtype {gd}")
+        C = _ext.get(required=True)
+        need = sumsq_partials(grads)
+        if partials is None:
+            partials = torch.empty(max(need, 1), dtype=at, device=grads[0].device)
+        elif partials.dtype != at or partials.numel() < need or not partials.is_contiguous():
+            raise TypeError(f"sumsq_: partials must be a contiguous {at} tensor with at least {need} entries")
+        C.mt_leaf_sumsq([g.data_ptr() for g in grads], [g.numel() for g in grads], DTYPE_CODE[gd],
+                        partials.data_ptr(), out.data_ptr(), scales.data_ptr() if scales is not None else 0,
+                        float(omega), float(grad_scale), torch.cuda.current_stream(grads[0].device).cuda_stream)
+        return
+    ss = torch.stack([(g.to(at) * g.to(at)).sum() for g in grads])
+    out[:n].copy_(ss)
+    if scales is not None:
+        scales[:n].copy_(clip_scales_reference(ss, omega, grad_scale).to(at))
+
+
+def sumsq_reference(grads) -> torch.Tensor:
+    """fp64 CPU sums of squares of ``grads`` (the oracle of :func:`sumsq_`)."""
+    return torch.stack([g.detach().cpu().double().pow(2).sum() for g in grads]) if grads else torch.zeros(0, dtype=torch.float64)
+
+
+def clip_scales_reference(sumsq: torch.Tensor, omega: float, grad_scale: float = 1.0) -> torch.Tensor:
+    """``min(1, omega / (grad_scale * sqrt(sumsq)))`` as the rule writes it (``optimisers.ClipNorm``)."""
+    return torch.clamp(omega / (grad_scale * torch.sqrt(sumsq)), max=1.0)
+
+
+def clip_total_(sumsq: torch.Tensor, slot: torch.Tensor, *, accumulate: bool = False, omega: float = 0.0,
+                grad_scale: float = 1.0) -> None:
+    """Fold per-leaf sums of squares into the fp32 device slot ``[sum, norm, scale]``:
+    ``slot[0] = (slot[0] if accumulate else 0) + sum(sumsq)`` (fixed order), ``slot[1] = grad_scale *
+    sqrt(slot[0])`` (the global gradient norm) and ``slot[2] = min(1, omega / slot[1])`` (1 when
+    ``omega <= 0``). ``slot[2:3]`` is the ``dev_gscale`` of a global-norm clipped update."""
+    if slot.dtype != torch.float32 or slot.numel() < 3 or not slot.is_contiguous():
+        raise TypeError("clip_total_: slot is a contiguous fp32 tensor of 3 entries")
+    if sumsq.dtype not in (torch.float32, torch.float64) or not sumsq.is_contiguous():
+        raise TypeError("clip_total_: sumsq is a contiguous fp32 or fp64 tensor")
+    if sumsq.is_cuda:
+        C = _ext.get(required=True)
+        C.clip_total(sumsq.data_ptr(), sumsq.numel(), DTYPE_CODE[sumsq.dtype], slot.data_ptr(), int(bool(accumulate)),
+                     float(omega), float(grad_scale), torch.cuda.current_stream(sumsq.device).cuda_stream)
+        return
+    total = (slot[0] if accumulate else 0.0) + sumsq.sum().float()
+    nrm = grad_scale * torch.sqrt(total)
+    slot[0] = total
+    slot[1] = nrm
+    slot[2] = torch.clamp(omega / nrm, max=1.0) if omega > 0 else 1.0
+
+
 def bias_corrections(beta1_t: float, beta2_t: float) -> tuple[float, float]:
     return 1.0 - beta1_t, 1.0 - beta2_t
 
 
-__all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_", "supported", "bias_corrections"]
+__all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_", "supported", "bias_corrections",
+           "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_"]

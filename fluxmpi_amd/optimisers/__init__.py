@@ -175,8 +175,23 @@ class Nesterov(AbstractRule):
         return _sgd_batch(self, items, self.rho, True)
 
 
-def _sgd_batch(rule, items, rho, nesterov):
-    """Fused GPU path for Descent / Momentum / Nesterov; per-leaf math elsewhere."""
+def _clip_kwargs(clip, x0, gs) -> dict:
+    """The fused update's clip arguments for one dtype group (``clip``: a leading ClipNorm(p=2) or
+    ClipGrad of a chain, or None). ClipNorm: the deterministic multi-tensor sum of squares and its
+    finish write one scale per leaf on the device (two launches per 24 leaves, no host read)."""
+    if clip is None:
+        return {}
+    if isinstance(clip, ClipGrad):
+        return {"clip_delta": _T(x0, clip.delta)}
+    at = torch.float64 if gs[0].dtype == torch.float64 else torch.float32
+    buf = torch.empty(2, len(gs), dtype=at, device=gs[0].device)
+    _fused.sumsq_(gs, buf[0], scales=buf[1], omega=clip.omega)
+    return {"tscale": buf[1]}
+
+
+def _sgd_batch(rule, items, rho, nesterov, clip=None):
+    """Fused GPU path for Descent / Momentum / Nesterov; per-leaf math elsewhere. ``clip``: the
+    chain's leading clip rule, fused into the update on the GPU leaves."""
     gpu = [i for i, (l, x, dx) in enumerate(items)
            if x.is_cuda and dx is not None
            and _same_dense(x, dx, *([l.state] if rho != 0.0 and isinstance(l.state, torch.Tensor) else []))
@@ -185,11 +200,14 @@ def _sgd_batch(rule, items, rho, nesterov):
     gset = set(gpu)
     for i, (leaf, x, dx) in enumerate(items):
         if i not in gset:
+            if clip is not None:
+                dx = clip.apply(None, x, dx)[1]
             leaf.state, out[i] = rule.apply(leaf.state, x, dx)
     if gpu:
         by_dtype: dict = {}
         for i in gpu:
-            by_dtype.setdefault(items[i][1].dtype, []).append(i)
+            key = items[i][1].dtype if clip is None else (items[i][1].dtype, items[i][2].dtype, items[i][1].device)
+            by_dtype.setdefault(key, []).append(i)
         for idx in by_dtype.values():
             x0 = items[idx[0]][1]
             xs = [items[i][1] for i in idx]
@@ -197,7 +215,7 @@ def _sgd_batch(rule, items, rho, nesterov):
             bufs = [items[i][0].state for i in idx] if rho != 0.0 else None
             # hyperparameters rounded to the leaves' precision, as in Julia (``_T``)
             _fused.sgd_(xs, gs, bufs, lr=_T(x0, rule.eta), momentum=_T(x0, rho) if rho else 0.0,
-                        nesterov=nesterov)
+                        nesterov=nesterov, **_clip_kwargs(clip, x0, gs))
     return out
 
 
@@ -259,8 +277,9 @@ def _same_dense(*ts) -> bool:
     return all(t.shape == t0.shape and t.stride() == t0.stride() for t in ts[1:])
 
 
-def _adam_batch(rule: Adam, items, weight_decay: float):
-    """Fused multi-tensor Adam on GPU leaves (x updated in place, dx' = None)."""
+def _adam_batch(rule: Adam, items, weight_decay: float, clip=None):
+    """Fused multi-tensor Adam on GPU leaves (x updated in place, dx' = None). ``clip``: the
+    chain's leading clip rule, fused into the update on the GPU leaves (per-leaf elsewhere)."""
     out: list = [None] * len(items)
     fused: dict = {}
     host: dict = {}
@@ -270,12 +289,16 @@ def _adam_batch(rule: Adam, items, weight_decay: float):
               and _fused.supported(x.dtype, dx.dtype, leaf.state[0].dtype, False))
         if ok:
             key = (x.device, x.dtype, tuple(leaf.state[2]))  # same precision and beta^t -> one launch
+            if clip is not None:
+                key = (*key, dx.dtype)  # the sum of squares takes one gradient dtype per call
             fused.setdefault(key, []).append(i)
-        elif (not x.is_cuda and dx is not None and x.dtype in (torch.float32, torch.float64)
+        elif (clip is None and not x.is_cuda and dx is not None and x.dtype in (torch.float32, torch.float64)
               and dx.dtype == x.dtype and isinstance(leaf.state, tuple) and len(leaf.state) == 3
               and leaf.state[0].dtype == x.dtype and x.shape == dx.shape):
             host.setdefault((x.dtype, tuple(leaf.state[2])), []).append(i)
         else:
+            if clip is not None:
+                dx = clip.apply(None, x, dx)[1]
             st, d = Adam.apply(rule, leaf.state, x, dx)
             if weight_decay:
                 d = d + _T(x, weight_decay) * x
@@ -306,7 +329,7 @@ def _adam_batch(rule: Adam, items, weight_decay: float):
             m, v, b = leaf.state
             leaf.state = (m, v, (_T(x0, b[0] * b1), _T(x0, b[1] * b2)))
             out[i] = num[k]
-    for (_, _, bt), idx in fused.items():
+    for (_, _, bt, *_), idx in fused.items():
         x0 = items[idx[0]][1]
         xs = [items[i][1] for i in idx]
         gs = [items[i][2] for i in idx]
@@ -315,7 +338,7 @@ def _adam_batch(rule: Adam, items, weight_decay: float):
         # hyperparameters rounded to the leaves' precision, as in Julia (``_T``)
         _fused.adam_(xs, gs, ms, vs, lr=_T(x0, rule.eta), beta1=_T(x0, rule.beta[0]), beta2=_T(x0, rule.beta[1]),
                      eps=_eps(x0, rule.epsilon), bc1=1.0 - bt[0], bc2=1.0 - bt[1],
-                     weight_decay=_T(x0, weight_decay) if weight_decay else 0.0)
+                     weight_decay=_T(x0, weight_decay) if weight_decay else 0.0, **_clip_kwargs(clip, x0, gs))
         for i in idx:
             leaf, x = items[i][0], items[i][1]
             m, v, b = leaf.state
@@ -371,18 +394,58 @@ class OptimiserChain(AbstractRule):
             new.append(s)
         return tuple(new), dx
 
+    def _is_adamw(self) -> bool:
+        return len(self.opts) == 2 and isinstance(self.opts[0], Adam) and isinstance(self.opts[1], WeightDecay)
+
+    def fused_plan(self):
+        """``(clip, inner, where)`` when the chain has a fused batch form, else ``None``.
+
+        ``clip``: a leading ``ClipNorm(p=2)`` / ``ClipGrad`` (or None); ``inner``: the update rule
+        — Adam, an Adam + WeightDecay chain, Descent, Momentum or Nesterov; ``where``: the
+        position of ``inner``'s state in the chain's state tuple (None: the tuple itself, the
+        flat ``(clip, Adam, WeightDecay)`` spelling, whose Adam state is ``states[1]``)."""
+        if self._is_adamw():
+            return None, self, None
+        o = self.opts
+        if len(o) < 2 or not (isinstance(o[0], ClipGrad) or (isinstance(o[0], ClipNorm) and o[0].p == 2)):
+            return None
+        if len(o) == 2 and (type(o[1]) in (Adam, Descent, Momentum, Nesterov)
+                            or (isinstance(o[1], OptimiserChain) and o[1]._is_adamw())):
+            return o[0], o[1], 1
+        if len(o) == 3 and isinstance(o[1], Adam) and isinstance(o[2], WeightDecay):
+            return o[0], OptimiserChain(o[1], o[2]), None
+        return None
+
     def apply_batch(self, items):
-        # Fuse the common AdamW shape (Adam then WeightDecay) into one kernel.
-        if (len(self.opts) == 2 and isinstance(self.opts[0], Adam) and isinstance(self.opts[1], WeightDecay)):
-            adam, wd = self.opts
-            sub = []
-            for leaf, x, dx in items:
-                sub.append((Leaf(adam, leaf.state[0]), x, dx))
-            out = _adam_batch(adam, sub, wd.gamma)
-            for (leaf, _, _), (sl, _, _) in zip(items, sub):
-                leaf.state = (sl.state, leaf.state[1])
-            return out
-        return AbstractRule.apply_batch(self, items)
+        # Fuse the common shapes into one kernel per dtype group: AdamW (Adam then WeightDecay),
+        # and a leading ClipNorm(p=2) / ClipGrad in front of Adam, AdamW, Descent, Momentum or
+        # Nesterov (the clip rides in the update kernel; ClipNorm's per-leaf scales come from a
+        # multi-tensor sum of squares). The state keeps the chain's tuple-of-member-states layout.
+        plan = self.fused_plan()
+        if plan is None:
+            return AbstractRule.apply_batch(self, items)
+        clip, inner, where = plan
+
+        def get(st):
+            if clip is None:
+                return st
+            return st[1] if where == 1 else (st[1], st[2])
+
+        def put(st, new):
+            if clip is None:
+                return new
+            return (st[0], new) if where == 1 else (st[0], new[0], new[1])
+
+        adamw = isinstance(inner, OptimiserChain)
+        rule = inner.opts[0] if adamw else inner
+        sub = [(Leaf(rule, get(leaf.state)[0] if adamw else get(leaf.state)), x, dx) for leaf, x, dx in items]
+        if isinstance(rule, Adam):
+            out = _adam_batch(rule, sub, inner.opts[1].gamma if adamw else 0.0, clip)
+        else:
+            out = _sgd_batch(rule, sub, getattr(rule, "rho", 0.0), isinstance(rule, Nesterov), clip)
+        for (leaf, _, _), (sl, _, _) in zip(items, sub):
+            leaf.state = put(leaf.state, (sl.state, get(leaf.state)[1]) if adamw else sl.state)
+        return out
 
 
 OptimizerChain = OptimiserChain

@@ -97,6 +97,8 @@ class _Bucket:
     comm_buf: torch.Tensor | None = None
     carry: torch.Tensor | None = None
     applied: bool = False  # overlap_opt: this step's update already enqueued (during backward)
+    clip: torch.Tensor | None = None  # gradient clipping: [2, leaves] per-leaf sums of squares / scales
+    partials: torch.Tensor | None = None  # ... and the sum-of-squares kernel's per-workgroup partials
 
 
 def _strided_view(flat: torch.Tensor, like: torch.Tensor, offset: int) -> torch.Tensor:
@@ -128,8 +130,18 @@ class DDP:
     Parameters
     ----------
     module: the model (already on its device, in its compute dtype/memory format).
-    rule:   an ``optimisers`` rule (Adam, AdamW chain, Descent, Momentum, Nesterov);
-            the engine runs it with fused flat-buffer kernels.
+    rule:   an ``optimisers`` rule (Adam, AdamW chain, Descent, Momentum, Nesterov), optionally
+            behind a clip: ``OptimiserChain(ClipNorm(omega), rule)`` (per-leaf L2 norm) or
+            ``OptimiserChain(ClipGrad(delta), rule)``; the engine runs it with fused flat-buffer
+            kernels (the clip inside the update kernel, the norms from a deterministic
+            multi-tensor sum of squares on the updates' stream: over all buckets at once in
+            ``step()``, in front of each bucket's update with ``overlap_opt``).
+    clip_global_norm: clip the whole gradient to this L2 norm (``clip_grad_norm_`` semantics):
+            ``step()`` takes every bucket's sum of squares once the last bucket is reduced, then
+            runs all updates, which read one device scalar. Not with ``overlap_opt=True`` (an
+            update cannot start before the last bucket is reduced) and not with a ``ClipNorm``
+            chain; with ``ClipGrad`` the global scale is applied first.
+            :meth:`grad_norm` returns the step's global gradient norm in either clip mode.
     master_weights: keep fp32 master copies (+ fp32 moments) for low-precision params.
     average: divide the summed gradient by the world size (default False = reference SUM).
     overlap: launch bucket allreduces from backward hooks (default: ``FLUXMPI_OVERLAP``).
@@ -150,8 +162,13 @@ class DDP:
                  broadcast: bool = True, root_rank: int = 0, comm: Communicator | None = None,
                  comm_dtype: torch.dtype | None = None, watchdog: bool | None = None,
                  grad_mode: str | None = None, force_comm: bool | None = None,
-                 tail_bucket_mb: float | None = None, overlap_opt: bool | None = None):
+                 tail_bucket_mb: float | None = None, overlap_opt: bool | None = None,
+                 clip_global_norm: float | None = None):
         cfg = get_config()
+        if clip_global_norm is not None and overlap_opt:
+            raise ValueError("DDP: clip_global_norm needs every bucket's norm before the first update, so the "
+                             "updates cannot overlap with backward: drop overlap_opt=True")
+        self.clip_global_norm = None if clip_global_norm is None else float(clip_global_norm)
         # "steal": autograd hands over each freshly produced gradient (no in-place accumulate
         # kernel per parameter, no zero fill) and one multi-tensor launch per bucket packs them
         # into the flat buffer; "view": p.grad is a view into the flat buffer (autograd adds in).
@@ -230,6 +247,8 @@ class DDP:
         # allreduce) when it has one, on a side stream when nothing is communicated, else in
         # step() (host-synchronous collectives: nothing to overlap with)
         want_opt = cfg.overlap_opt if overlap_opt is None else bool(overlap_opt)
+        if self.clip_global_norm is not None:
+            want_opt = False
         self.overlap_opt = want_opt and self.overlap and self.grad_mode == "steal"
         self._opt_stream = None  # None: the update runs right after the (host-waited) reduction
         if self.overlap_opt and self.device.type == "cuda":
@@ -347,6 +366,18 @@ class DDP:
 
     def _setup_optimizer(self):
         r = self.rule
+        # a leading ClipNorm(p=2) / ClipGrad of a chain rides in the update kernels
+        self._clip_rule, self._chain_where = None, None
+        if isinstance(r, O.OptimiserChain):
+            plan = r.fused_plan()
+            if plan is None:
+                raise TypeError(f"DDP: no fused kernel for rule {r!r}; use the functional optimisers API")
+            self._clip_rule, r, self._chain_where = plan
+        self._per_leaf = isinstance(self._clip_rule, O.ClipNorm)
+        if self._per_leaf and self.clip_global_norm is not None:
+            raise ValueError("DDP: clip_global_norm and a ClipNorm chain both rescale by a norm; use one of them")
+        self._norms = self._per_leaf or self.clip_global_norm is not None
+        self._upd = r  # the update rule behind the clip
         if isinstance(r, O.OptimiserChain) and len(r.opts) == 2 and isinstance(r.opts[0], O.Adam) \
                 and isinstance(r.opts[1], O.WeightDecay):
             self.kind, self.adam, self.wd = "adam", r.opts[0], r.opts[1].gamma
@@ -372,12 +403,33 @@ class DDP:
                 b.exp_avg_sq = torch.zeros(b.numel, dtype=sdt, device=dev)
             elif self.kind in ("momentum", "nesterov"):
                 b.exp_avg = torch.zeros(b.numel, dtype=sdt, device=dev)
+        # gradient norms: per bucket dtype one [2, leaves] buffer of per-leaf sums of squares and
+        # scales and one of the sum-of-squares kernel's partials; every bucket owns a slice, so the
+        # norms of all buckets can be taken in one multi-tensor call (step()) or bucket by bucket
+        # (overlap_opt)
+        self._clip_groups = []
+        if self._norms:
+            by_dtype: dict = {}
+            for b in self.buckets:
+                by_dtype.setdefault(b.dtype, []).append(b)
+            for dt, bs in by_dtype.items():
+                at = torch.float64 if dt == torch.float64 else torch.float32
+                buf = torch.zeros(2, sum(len(b.params) for b in bs), dtype=at, device=dev)
+                parts = torch.zeros(sum(fused.sumsq_partials(b.params) for b in bs), dtype=at, device=dev)
+                off = poff = 0
+                for b in bs:
+                    k, kp = len(b.params), fused.sumsq_partials(b.params)
+                    b.clip, b.partials = buf[:, off:off + k], parts[poff:poff + kp]
+                    off, poff = off + k, poff + kp
+                self._clip_groups.append((bs, buf, parts))
+        # [sum of squares, norm, global clip scale] of the step's whole gradient (device, fp32)
+        self._clip_slot = torch.zeros(3, dtype=torch.float32, device=dev) if self._norms else None
         if self.kind == "adam":
             a = self.adam
             # device hyper block [lr, beta1^t, beta2^t]; beta^t starts at beta (Optimisers.jl init)
             self.hyper = torch.tensor([a.eta, a.beta[0], a.beta[1]], dtype=torch.float32, device=dev)
         else:
-            self.hyper = torch.tensor([self.rule.eta], dtype=torch.float32, device=dev)
+            self.hyper = torch.tensor([self._upd.eta], dtype=torch.float32, device=dev)
 
     def broadcast_parameters(self, root_rank: int = 0):
         """One broadcast per flat bucket (+ its fp32 master) + module buffers (``synchronize``
@@ -534,6 +586,8 @@ class DDP:
                     graddst.rearm(p)
         self._next_launch = 0
         self._masters_synced = False
+        self._norm_started = False  # clipping: the step's first bucket starts the global sum afresh
+        self._deferred = []  # norm clipping in step(): the updates wait for all buckets' norms
 
     def _note_copy(self, p) -> None:
         self.pack_copies += 1
@@ -743,6 +797,17 @@ class DDP:
             self._comm_events.append((e0, e1))
 
     def _finish_step(self, zero_grad: bool):
+        if self._deferred:
+            # gradient norms with the updates in step(): ONE multi-tensor sum of squares over the
+            # leaves of all buckets of a dtype (two launches per 24 leaves instead of per bucket)
+            # and one fold into the global sum, then every bucket's update
+            grads = {b.index: (gs, gscale) for b, _, gs, gscale in self._deferred}
+            for bs, buf, parts in self._clip_groups:
+                gs_all = [g for b in bs for g in grads[b.index][0]]
+                self._enqueue_norms(gs_all, buf, parts, grads[bs[0].index][1])
+            for b, st, gs, gscale in self._deferred:
+                self._run_update(st, gs, gscale, b)
+            self._deferred = []
         if self.kind == "adam":
             fused.adam_advance_(self.hyper, self.adam.beta[0], self.adam.beta[1])
         self.step_count += 1
@@ -793,18 +858,66 @@ class DDP:
             self._comm_events.clear()
         return sum(ms) / len(ms)
 
-    def _apply(self, b: _Bucket, gscale: float):
-        masters = [b.master] if b.master is not None else None
+    def _slices(self, b: _Bucket) -> tuple:
+        """Per-leaf slices (memory order) of the bucket's flat parameters, moments and masters (cached)."""
+        st = self._direct_cache.get(b.index)
+        if st is None:
+            def sl(flat):
+                return [flat[o:o + p.numel()] for p, o in zip(b.params, b.offsets)] if flat is not None else None
+            st = (sl(b.flat_param), sl(b.exp_avg), sl(b.exp_avg_sq), sl(b.master))
+            self._direct_cache[b.index] = st
+        return st
+
+    def _run_update(self, st: tuple, gs: list, gscale: float, b: _Bucket):
+        """One fused update launch over ``st = (params, m, v, masters)`` lists and their gradients."""
+        ps, ms, vs, ws = st
+        kw = {}
+        if isinstance(self._clip_rule, O.ClipGrad):
+            kw["clip_delta"] = self._clip_rule.delta
+        elif self._per_leaf:
+            kw["tscale"] = b.clip[1]
+        if self.clip_global_norm is not None:
+            kw["dev_gscale"] = self._clip_slot[2:3]
         if self.kind == "adam":
             a = self.adam
-            fused.adam_([b.flat_param], [b.flat_grad], [b.exp_avg], [b.exp_avg_sq], lr=a.eta, beta1=a.beta[0],
-                        beta2=a.beta[1], eps=a.epsilon, bc1=0.0, bc2=0.0, weight_decay=self.wd,
-                        grad_scale=gscale, masters=masters, dev_hyper=self.hyper)
+            fused.adam_(ps, gs, ms, vs, lr=a.eta, beta1=a.beta[0], beta2=a.beta[1], eps=a.epsilon, bc1=0.0,
+                        bc2=0.0, weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_hyper=self.hyper, **kw)
         else:
-            mom = {"descent": 0.0}.get(self.kind, getattr(self.rule, "rho", 0.0))
-            fused.sgd_([b.flat_param], [b.flat_grad], [b.exp_avg] if b.exp_avg is not None else None,
-                       lr=self.rule.eta, momentum=mom, nesterov=self.kind == "nesterov", weight_decay=self.wd,
-                       grad_scale=gscale, masters=masters, dev_lr=self.hyper)
+            mom = {"descent": 0.0}.get(self.kind, getattr(self._upd, "rho", 0.0))
+            fused.sgd_(ps, gs, ms, lr=self._upd.eta, momentum=mom, nesterov=self.kind == "nesterov",
+                       weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_lr=self.hyper, **kw)
+
+    def _enqueue_norms(self, gs: list, buf: torch.Tensor, parts: torch.Tensor, gscale: float):
+        """Per-leaf sums of squares of ``gs`` into ``buf[0]`` (two deterministic launches per 24
+        leaves) with the ClipNorm scales into ``buf[1]``, then the fold into the step's global sum
+        / norm / global scale (one workgroup; the step's first call starts the sum afresh) — all on
+        the current stream, no host read."""
+        fused.sumsq_(gs, buf[0], scales=buf[1] if self._per_leaf else None,
+                     omega=self._clip_rule.omega if self._per_leaf else 0.0, grad_scale=gscale, partials=parts)
+        fused.clip_total_(buf[0], self._clip_slot, accumulate=self._norm_started,
+                          omega=self.clip_global_norm or 0.0, grad_scale=gscale)
+        self._norm_started = True
+
+    def _update(self, b: _Bucket, st: tuple, gs: list, gscale: float):
+        """The bucket's update on the current stream. With norm clipping and ``overlap_opt`` the
+        bucket's norms are enqueued right in front of it (a leaf never spans buckets); otherwise
+        the update waits for ``_finish_step``, which takes the norms of all buckets at once —
+        ``clip_global_norm`` needs the last bucket's norm before the first update anyway."""
+        if self._norms:
+            if not self.overlap_opt:
+                self._deferred.append((b, st, gs, gscale))
+                return
+            self._enqueue_norms(gs, b.clip, b.partials, gscale)
+        self._run_update(st, gs, gscale, b)
+
+    def _apply(self, b: _Bucket, gscale: float):
+        if self._norms:
+            # per-leaf norms: the update reads the flat bucket leaf by leaf (as _apply_direct does)
+            self._update(b, self._slices(b), [v.as_strided((v.numel(),), (1,)) for _, v, _ in self._grad_views(b)],
+                         gscale)
+            return
+        one = lambda t: [t] if t is not None else None  # noqa: E731
+        self._update(b, ([b.flat_param], one(b.exp_avg), one(b.exp_avg_sq), one(b.master)), [b.flat_grad], gscale)
 
     def _apply_direct(self, b: _Bucket, gscale: float) -> bool:
         """Fused optimiser on the autograd gradients in place (no pack). False if some gradient
@@ -818,24 +931,20 @@ class DDP:
                 if g.dtype != b.dtype or g.device != b.device or not _same_layout(g, p) or not _is_dense(g):
                     return False
             grads.append(g)
-        st = self._direct_cache.get(b.index)
-        if st is None:
-            def sl(flat):
-                return [flat[o:o + p.numel()] for p, o in zip(b.params, b.offsets)] if flat is not None else None
-            st = (sl(b.flat_param), sl(b.exp_avg), sl(b.exp_avg_sq), sl(b.master))
-            self._direct_cache[b.index] = st
-        ps, ms, vs, ws = st
         # the flat slices are in memory order; a gradient with its parameter's strides is too
         gs = [g.view(-1) if g.is_contiguous() else g.as_strided((g.numel(),), (1,)) for g in grads]
-        if self.kind == "adam":
-            a = self.adam
-            fused.adam_(ps, gs, ms, vs, lr=a.eta, beta1=a.beta[0], beta2=a.beta[1], eps=a.epsilon, bc1=0.0,
-                        bc2=0.0, weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_hyper=self.hyper)
-        else:
-            mom = {"descent": 0.0}.get(self.kind, getattr(self.rule, "rho", 0.0))
-            fused.sgd_(ps, gs, ms, lr=self.rule.eta, momentum=mom, nesterov=self.kind == "nesterov",
-                       weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_lr=self.hyper)
+        self._update(b, self._slices(b), gs, gscale)
         return True
+
+    def grad_norm(self) -> torch.Tensor:
+        """The last step's global L2 norm of the gradient the rule saw — after reduction, carry and
+        the ``average`` scale, before clipping — as a 0-dim fp32 tensor on the engine's device.
+        Never synchronises (read it after ``step()``, on the stream ``step()`` ran on). Available
+        with a ``ClipNorm`` chain or ``clip_global_norm``."""
+        if not self._norms:
+            raise RuntimeError("DDP.grad_norm: the engine computes gradient norms only when it clips by one: "
+                               "use an OptimiserChain(ClipNorm(omega), rule) or clip_global_norm=...")
+        return self._clip_slot[1]
 
     def set_lr(self, lr: float):
         """Change the learning rate (device-side, so captured graphs see it)."""
@@ -843,7 +952,7 @@ class DDP:
         if self.kind == "adam":
             self.adam.eta = lr
         else:
-            self.rule.eta = lr
+            self._upd.eta = lr
 
     # ------------------------------------------------------------------ state
     def optimiser_state(self):
@@ -861,6 +970,12 @@ class DDP:
                     st = _strided_view(b.exp_avg, p, o)
                 else:
                     st = None
+                if self._clip_rule is not None:
+                    # the chain's tuple of member states: (clip: None, update rule's state...)
+                    if isinstance(self._upd, O.OptimiserChain):  # Adam + WeightDecay behind the clip
+                        st = (None, (st, None)) if self._chain_where == 1 else (None, st, None)
+                    else:
+                        st = (None, st)
                 out[name] = O.Leaf(self.rule, st)
         return out
 

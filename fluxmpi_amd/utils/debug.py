@@ -20,6 +20,7 @@ default error handler. Here:
 """
 from __future__ import annotations
 
+import atexit
 import hashlib
 import threading
 import time
@@ -193,6 +194,13 @@ def stop_all() -> None:
     """Stop every live watchdog (``Finalize`` calls this before destroying communicators)."""
     for w in list(_WATCHDOGS):
         w.stop()
+
+
+# A process that ends without Finalize() must not leave the polling threads to the interpreter's
+# shutdown: a daemon thread that is inside (or returns from) a call into the native library once
+# the interpreter finalises is ended by unwinding through C++ frames, which terminates the
+# process ("terminate called without an active exception") after the program's work is done.
+atexit.register(stop_all)
 
 
 __all__ = ["ReplicaDivergenceError", "CollectiveMismatchError", "checksum", "check_replicas", "structure_hash",
