@@ -148,6 +148,15 @@ void attn_bwd(const void* q, const void* k, const void* v, const void* o, const 
 // dK / dV rows it writes; their reduce is the packed QKV bias gradient), 0 if this call's variant
 // does not write them
 int attn_bwd_colpart_rows(int B, int T, int H, int64_t sq_t, int64_t sg_t);
+// the kernels attn_fwd / attn_bwd launch for this shape in this process (the FLUXMPI_ATTN_*
+// switches are read once): their names ("a+b" for a two-kernel backward) and the workgroups per
+// (batch, head); the launchers take their choice from the same function
+struct AttnDispatch {
+  const char* fwd;
+  const char* bwd;
+  int fwd_parts, bwd_parts;
+};
+AttnDispatch attn_dispatch(int B, int T, int H);
 // dx[n,h,w,c] = sum of dy over the windows whose idx points at (h,w) (gather; dx fully written)
 void maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int64_t N, int64_t H, int64_t W, int64_t C, int K,
                  int S, int P, int dtype, hipStream_t stream);

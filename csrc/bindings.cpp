@@ -190,6 +190,10 @@ PYBIND11_MODULE(_C, m) {
      py::arg("so_h"), py::arg("sg_b"), py::arg("sg_t"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("Dh"),
      py::arg("scale"), py::arg("stream"), py::arg("colpart") = 0);
   m.def("attn_bwd_colpart_rows", &attn_bwd_colpart_rows);
+  m.def("attn_dispatch", [](int B, int T, int H) {
+    const AttnDispatch d = attn_dispatch(B, T, H);
+    return py::make_tuple(std::string(d.fwd), std::string(d.bwd), d.fwd_parts, d.bwd_parts);
+  });
   m.def("pad_c3_to_c4", [](uintptr_t x, uintptr_t y, int64_t npix, int dtype, uintptr_t stream) {
     pad_c3_to_c4(reinterpret_cast<const void*>(x), reinterpret_cast<void*>(y), npix, dtype,
                  reinterpret_cast<hipStream_t>(stream));

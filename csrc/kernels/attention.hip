@@ -23,10 +23,15 @@
 //                S = Q K^T, P = exp2(S c - lse2), dP = dO V^T, dS = P (dP - D),
 //                dV^T += dO^T P, dK^T += Q^T dS  (dO^T, Q^T from transposed LDS images).
 //
-// Masking of rows >= T: staged rows past the end are zero, so a padded key contributes
-// nothing to O, dQ (its K^T / V^T columns are zero) or anything stored; only the softmax
-// denominator of the forward needs an explicit mask, in the last chunk. Padded queries get
-// lse = +inf in the dK/dV sweep (P = 0).
+// Masking of rows >= T: staged rows past the end are zero, but a zero row is not a zero
+// contribution. A padded key has score 0, so the forward masks it out of the softmax
+// denominator (last chunk / tile), and in the backward its weight P = exp2(0 - lse2) overflows
+// to +inf once a row's real scores are all strongly negative (lse2 < -128): dS = +-inf or NaN,
+// and 0 * inf = NaN. A padded key sits in one MFMA column (one lane's accumulators), which stays
+// apart from the real keys' columns and is never stored; wherever that column meets other data
+// it is selected away, never multiplied by zero: dS^T as the B operand of dQ^T = K^T dS^T (the
+// dq kernels' last tile, the fused kernel's dS image) and the row sums of colpart_store.
+// Padded queries get lse = +inf in the dK/dV sweep (P = 0).
 //
 // MFMA: v_mfma_f32_16x16x32_bf16 (A[row l&15][k = 8(l>>4)+j], B[k = 8(l>>4)+j][col l&15],
 // C[row 4(l>>4)+r][col l&15]). An accumulator pair (rows 0-15, 16-31 of a 32-row chunk) is
@@ -274,6 +279,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) ds[kt][r] = fast_exp2(fmaf(s[r], c2, -lse)) * (dp[r] - dsum);
     }
+    if ((c + 1) * CH > a.T) {  // last, partial chunk: a padded key's dS (P may be +inf) is selected away
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (c * CH + kt * 16 + 4 * g + r >= a.T) ds[kt][r] = 0.f;
+    }
     const bf16x8 bop = pack(ds[0], ds[1]);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) acc[dt] = mfma(ld_tr(sKt, dt * 16 + col, g), bop, acc[dt]);
@@ -459,17 +471,17 @@ __device__ __forceinline__ float* colpart_row(const AttnBwdArgs& a, int b, int h
 }
 
 // sums over the wave's 16 rows (lane & 15) of acc[dt][r] = gradient[row][16 dt + 4 (lane >> 4) + r],
-// rows with ok == false excluded; one float4 store per (dt, lane group)
+// rows with ok == false excluded by selection (a padded key's accumulators may hold inf / NaN, which
+// a multiplication by zero would keep); one float4 store per (dt, lane group)
 __device__ __forceinline__ void colpart_store(float* row, const f32x4 (&acc)[4], float scale, bool ok) {
   const int lane = threadIdx.x & 63, g = lane >> 4;
-  const float keep = ok ? scale : 0.f;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
     float4 v;
-    v.x = row_sum16(acc[dt][0] * keep);
-    v.y = row_sum16(acc[dt][1] * keep);
-    v.z = row_sum16(acc[dt][2] * keep);
-    v.w = row_sum16(acc[dt][3] * keep);
+    v.x = row_sum16(ok ? acc[dt][0] * scale : 0.f);
+    v.y = row_sum16(ok ? acc[dt][1] * scale : 0.f);
+    v.z = row_sum16(ok ? acc[dt][2] * scale : 0.f);
+    v.w = row_sum16(ok ? acc[dt][3] * scale : 0.f);
     if ((lane & 15) == 0) *reinterpret_cast<float4*>(row + 16 * dt + 4 * g) = v;
   }
 }
@@ -1022,10 +1034,12 @@ __global__ __launch_bounds__(1024) void attn_bwd_fused_kernel(AttnBwdArgs a) {
         dsv[half][r] = pv * (dp[r] - sD[qq]);
       }
       if (32 * ks + 16 * half < NQ) {  // compile-time: rows past the waves' queries are not in the image
+        // a padded key's column is written as zero: its dS (P may be +inf) must not meet K^T's zero
+        // rows in phase 2. (Masking the phase-2 operand instead costs the kernel 3 spilled registers.)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           *reinterpret_cast<bf16*>(dsimg + (32 * ks + 16 * half + 4 * g + r) * kDsRow + (k0 + col) * 2) =
-              static_cast<bf16>(dsv[half][r]);
+              static_cast<bf16>(kok ? dsv[half][r] : 0.f);
       }
     }
     const bf16x8 pb = pack(p[0], p[1]), db = pack(dsv[0], dsv[1]);
@@ -1137,25 +1151,75 @@ int fwd_parts(int tiles) {
   return parts < tiles ? parts : tiles;
 }
 
-}  // namespace
-
-namespace {
 // FLUXMPI_ATTN_BWD=blocked / FLUXMPI_ATTN_FWD=blocked: the non-resident kernels for every T (A/B)
 bool blocked_env(const char* name) {
   const char* e = std::getenv(name);
   return e != nullptr && std::string(e) == "blocked";
 }
+
+// The one place that chooses the kernels of a call (both launchers, attn_bwd_colpart_rows and
+// attn_dispatch read it): resident (T <= 256) or blocked, compile-time tile count 13 (T 193..208) or
+// the runtime-count kernels, fused backward or the dq / dkv pair, the pair's dkv pipeline, and the
+// workgroups per (b, h).
+enum class FwdKind { kBlocked, kRes0, kRes13 };
+enum class BwdKind { kBlocked, kPair0, kPair13, kPair13Pipe, kFused13 };
+struct AttnPlan {
+  FwdKind fwd;
+  BwdKind bwd;
+  int fwd_parts, bwd_parts;  // workgroups per (b, h): row-tile parts (resident) or 64-row blocks
+  int fwd_waves, bwd_waves;  // waves per workgroup
+};
+
+AttnPlan attn_plan(int T) {
+  static const bool fwd_resident = !blocked_env("FLUXMPI_ATTN_FWD");
+  static const bool bwd_resident = !blocked_env("FLUXMPI_ATTN_BWD");
+  const int tiles = (T + 15) / 16;
+  const bool vit = tiles == 13 && !attn_generic();  // T 193..208 (ViT: 197): compile-time tile count
+  AttnPlan p{FwdKind::kBlocked, BwdKind::kBlocked, (T + 63) / 64, (T + 63) / 64, 4, 4};
+  if (fwd_resident && T <= kResMaxT) {
+    p.fwd = vit ? FwdKind::kRes13 : FwdKind::kRes0;
+    p.fwd_parts = fwd_parts(tiles);
+    p.fwd_waves = (tiles + p.fwd_parts - 1) / p.fwd_parts;
+  }
+  if (bwd_resident && T <= kResMaxT) {
+    if (vit && attn_fused_env()) {
+      p.bwd = BwdKind::kFused13;  // one workgroup of 13 waves per (b, h)
+      p.bwd_parts = 1;
+      p.bwd_waves = 13;
+    } else {
+      p.bwd = !vit ? BwdKind::kPair0 : (dkv_pipe() ? BwdKind::kPair13Pipe : BwdKind::kPair13);
+      p.bwd_parts = res_parts(tiles);
+      p.bwd_waves = (tiles + p.bwd_parts - 1) / p.bwd_parts;
+    }
+  }
+  return p;
+}
+
 }  // namespace
 
+AttnDispatch attn_dispatch(int B, int T, int H) {
+  if (B <= 0 || T <= 0 || H <= 0) throw std::runtime_error("attn_dispatch: empty problem");
+  const AttnPlan p = attn_plan(T);
+  const char* fwd = p.fwd == FwdKind::kBlocked ? "attn_fwd_kernel"
+                    : p.fwd == FwdKind::kRes13 ? "attn_fwd_res_kernel<13>"
+                                               : "attn_fwd_res_kernel<0>";
+  const char* bwd = "attn_bwd_dq_kernel+attn_bwd_dkv_kernel";
+  switch (p.bwd) {
+    case BwdKind::kBlocked: break;
+    case BwdKind::kPair0: bwd = "attn_bwd_dq_res_kernel<0>+attn_bwd_dkv_res_kernel<0,0>"; break;
+    case BwdKind::kPair13: bwd = "attn_bwd_dq_res_kernel<13>+attn_bwd_dkv_res_kernel<13,0>"; break;
+    case BwdKind::kPair13Pipe: bwd = "attn_bwd_dq_res_kernel<13>+attn_bwd_dkv_res_kernel<13,1>"; break;
+    case BwdKind::kFused13: bwd = "attn_bwd_fused_kernel<13>"; break;
+  }
+  return AttnDispatch{fwd, bwd, p.fwd_parts, p.bwd_parts};
+}
+
 int attn_bwd_colpart_rows(int B, int T, int H, int64_t sq_t, int64_t sg_t) {
-  // the resident dq / dkv pair writes the column-sum partials; every other variant does not
-  if (blocked_env("FLUXMPI_ATTN_BWD") || T > kResMaxT || T <= 0 || (sq_t % 8) != 0 || (sg_t % 8) != 0) return 0;
-  const int tiles = (T + 15) / 16;
-  if (attn_fused_env() && tiles == 13 && !attn_generic()) return B * tiles;  // the fused kernel: one part of 13 waves
-  const int nblk = res_parts(tiles);
-  const int waves = (tiles + nblk - 1) / nblk;
+  // the resident backward kernels write the column-sum partials; the blocked pair does not
+  if (T <= 0 || (sq_t % 8) != 0 || (sg_t % 8) != 0) return 0;
+  const AttnPlan p = attn_plan(T);
   (void)H;
-  return B * nblk * waves;
+  return p.bwd == BwdKind::kBlocked ? 0 : B * p.bwd_parts * p.bwd_waves;
 }
 
 void attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, void* dq, void* dk,
@@ -1172,46 +1236,40 @@ void attn_bwd(const void* q, const void* k, const void* v, const void* o, const 
                 static_cast<const bf16*>(o), static_cast<const bf16*>(dout), nullptr, static_cast<bf16*>(dq),
                 static_cast<bf16*>(dk), static_cast<bf16*>(dv), stats, sq_b, sq_t, so_b, so_t, so_h, sg_b, sg_t,
                 B, T, H, (T + 63) / 64, scale};
-  static const bool resident = !blocked_env("FLUXMPI_ATTN_BWD");
-  if (resident && T <= kResMaxT && (sq_t % 8) == 0 && (sg_t % 8) == 0) {
-    const int tiles = (T + 15) / 16;
-    if (attn_fused_env() && tiles == 13 && !attn_generic()) {
-      a.nblk = 1;
-      const int64_t bh = static_cast<int64_t>(B) * H;
-      if (bh > 0x7fffffff) throw std::runtime_error("attn_bwd: grid too large");
-      a.colpart = colpart;  // [B * 13][3 * H * 64] (attn_bwd_colpart_rows), or nullptr
-      static const bool attr = [] {
-        FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<13>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              static_cast<int>(fused_lds(13))));
-        return true;
-      }();
-      (void)attr;
-      attn_bwd_fused_kernel<13><<<static_cast<unsigned>(bh), 13 * 64, fused_lds(13), s>>>(a);
-      FLUXMPI_HIP_CHECK(hipGetLastError());
-      return;
-    }
-    a.nblk = res_parts(tiles);
-    const int64_t bh = static_cast<int64_t>(B) * H * a.nblk;
-    if (bh > 0x7fffffff) throw std::runtime_error("attn_bwd: grid too large");
-    const int waves = (tiles + a.nblk - 1) / a.nblk;
-    const int TP = (T + 15) & ~15, TV = (T + 31) & ~31;
-    a.colpart = colpart;  // [B * nblk * waves][3 * H * 64] (attn_bwd_colpart_rows), or nullptr
-    const bool vit = tiles == 13 && !attn_generic();  // T 193..208 (ViT: 197): compile-time tile count
-    auto kdq = vit ? attn_bwd_dq_res_kernel<13> : attn_bwd_dq_res_kernel<0>;
-    auto kdkv = !vit ? attn_bwd_dkv_res_kernel<0> : (dkv_pipe() ? attn_bwd_dkv_res_kernel<13, 1> : attn_bwd_dkv_res_kernel<13, 0>);
-    kdq<<<static_cast<unsigned>(bh), waves * 64, static_cast<size_t>(TV + TP) * 128, s>>>(a);
-    FLUXMPI_HIP_CHECK(hipGetLastError());
-    kdkv<<<static_cast<unsigned>(bh), waves * 64, static_cast<size_t>(2 * TV) * 128 + 2 * TV * 4,
-                              s>>>(a);
+  const AttnPlan plan = attn_plan(T);
+  a.nblk = plan.bwd_parts;
+  const int64_t total = static_cast<int64_t>(B) * H * a.nblk;
+  if (total > 0x7fffffff) throw std::runtime_error("attn_bwd: grid too large");
+  const unsigned grid = static_cast<unsigned>(total), threads = static_cast<unsigned>(plan.bwd_waves) * 64;
+  if (plan.bwd == BwdKind::kFused13) {
+    a.colpart = colpart;  // [B * 13][3 * H * 64] (attn_bwd_colpart_rows), or nullptr
+    static const bool attr = [] {
+      FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<13>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            static_cast<int>(fused_lds(13))));
+      return true;
+    }();
+    (void)attr;
+    attn_bwd_fused_kernel<13><<<grid, threads, fused_lds(13), s>>>(a);
     FLUXMPI_HIP_CHECK(hipGetLastError());
     return;
   }
-  const int64_t total = static_cast<int64_t>(B) * H * a.nblk;
-  if (total > 0x7fffffff) throw std::runtime_error("attn_bwd: grid too large");
-  attn_bwd_dq_kernel<<<static_cast<unsigned>(total), 256, 0, s>>>(a);
+  if (plan.bwd != BwdKind::kBlocked) {
+    const int TP = (T + 15) & ~15, TV = (T + 31) & ~31;
+    a.colpart = colpart;  // [B * nblk * waves][3 * H * 64] (attn_bwd_colpart_rows), or nullptr
+    auto kdq = plan.bwd == BwdKind::kPair0 ? attn_bwd_dq_res_kernel<0> : attn_bwd_dq_res_kernel<13>;
+    auto kdkv = plan.bwd == BwdKind::kPair0 ? attn_bwd_dkv_res_kernel<0>
+                : plan.bwd == BwdKind::kPair13Pipe ? attn_bwd_dkv_res_kernel<13, 1>
+                                                   : attn_bwd_dkv_res_kernel<13, 0>;
+    kdq<<<grid, threads, static_cast<size_t>(TV + TP) * 128, s>>>(a);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    kdkv<<<grid, threads, static_cast<size_t>(2 * TV) * 128 + 2 * TV * 4, s>>>(a);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  attn_bwd_dq_kernel<<<grid, 256, 0, s>>>(a);
   FLUXMPI_HIP_CHECK(hipGetLastError());
-  attn_bwd_dkv_kernel<<<static_cast<unsigned>(total), 256, 0, s>>>(a);
+  attn_bwd_dkv_kernel<<<grid, 256, 0, s>>>(a);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -1237,25 +1295,21 @@ void attn_fwd(const void* q, const void* k, const void* v, void* o, float* stats
   a.B = B;
   a.T = T;
   a.H = H;
-  a.nblk = (T + 63) / 64;
   a.scale = scale;
-  static const bool resident = !blocked_env("FLUXMPI_ATTN_FWD");
-  if (resident && T <= kResMaxT && (sq_t % 8) == 0) {
+  const AttnPlan plan = attn_plan(T);
+  a.nblk = plan.fwd_parts;
+  const int64_t total = static_cast<int64_t>(B) * H * a.nblk;
+  if (total > 0x7fffffff) throw std::runtime_error("attn_fwd: grid too large");
+  const unsigned grid = static_cast<unsigned>(total), threads = static_cast<unsigned>(plan.fwd_waves) * 64;
+  if (plan.fwd != FwdKind::kBlocked) {
     // whole head resident in LDS: fwd_parts() workgroups per (b, h), one wave per 16 queries
-    const int tiles = (T + 15) / 16;
-    a.nblk = fwd_parts(tiles);
-    const int64_t total = static_cast<int64_t>(B) * H * a.nblk;
-    if (total > 0x7fffffff) throw std::runtime_error("attn_fwd: grid too large");
-    const int waves = (tiles + a.nblk - 1) / a.nblk;
     const size_t lds = static_cast<size_t>(2 * ((T + 15) & ~15)) * 128;
-    auto kf = (tiles == 13 && !attn_generic()) ? attn_fwd_res_kernel<13> : attn_fwd_res_kernel<0>;
-    kf<<<static_cast<unsigned>(total), waves * 64, lds, s>>>(a);
+    auto kf = plan.fwd == FwdKind::kRes13 ? attn_fwd_res_kernel<13> : attn_fwd_res_kernel<0>;
+    kf<<<grid, threads, lds, s>>>(a);
     FLUXMPI_HIP_CHECK(hipGetLastError());
     return;
   }
-  const int64_t total = static_cast<int64_t>(B) * H * a.nblk;
-  if (total > 0x7fffffff) throw std::runtime_error("attn_fwd: grid too large");
-  attn_fwd_kernel<<<static_cast<unsigned>(total), 256, 0, s>>>(a);
+  attn_fwd_kernel<<<grid, threads, 0, s>>>(a);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
