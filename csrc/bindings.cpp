@@ -69,6 +69,22 @@ PYBIND11_MODULE(_C, m) {
         py::arg("weight_decay"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"),
         py::arg("stream"), py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0),
         py::arg("clip_delta") = 0.f);
+  m.def("mt_rule",
+        [](int kind, const std::vector<uintptr_t>& p, const std::vector<uintptr_t>& g, const std::vector<uintptr_t>& s1,
+           const std::vector<uintptr_t>& s2, const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,
+           const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
+           double beta2, double eps, double bt1, double bt2, double weight_decay, float grad_scale,
+           uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta, uintptr_t stream) {
+          RuleHyper h{kind, lr, beta1, beta2, eps, bt1, bt2, weight_decay, grad_scale,
+                      reinterpret_cast<const float*>(dev_hyper), reinterpret_cast<const float*>(dev_gscale),
+                      reinterpret_cast<const void*>(tscale), clip_delta};
+          mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, S(stream));
+        },
+        py::arg("kind"), py::arg("param"), py::arg("grad"), py::arg("s1"), py::arg("s2"), py::arg("s3"),
+        py::arg("master"), py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("bt1"), py::arg("bt2"),
+        py::arg("weight_decay"), py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"),
+        py::arg("tscale"), py::arg("clip_delta"), py::arg("stream"));
   m.def("sumsq_partials", &sumsq_partials, py::arg("numel"));
   m.def("mt_leaf_sumsq",
         [](const std::vector<uintptr_t>& g, const std::vector<int64_t>& numel, int g_dtype, uintptr_t partials,

@@ -1,0 +1,107 @@
+// Shared by the fused multi-tensor optimiser kernels (optim.hip: Adam, SGD, sums of squares;
+// optim_rules.hip: the rest of the rule set): the job layout — 4096-element chunks of up to 24
+// leaves per launch, the chunk -> leaf map a prefix table in the kernel arguments — the compute
+// type, the gradient clamp and the dtype combinations every update kernel is built for.
+#pragma once
+#include <stdexcept>
+#include <vector>
+
+#include "common.h"
+
+namespace fluxmpi {
+
+constexpr int kThreads = 256;
+constexpr int kVec = 8;
+constexpr int kIters = 2;
+constexpr int kChunk = kThreads * kVec * kIters;  // 4096 elements per workgroup
+constexpr int kMaxT = 24;
+
+struct OptArgs {
+  uintptr_t p[kMaxT];
+  uintptr_t g[kMaxT];
+  uintptr_t s1[kMaxT];
+  uintptr_t s2[kMaxT];
+  uintptr_t s3[kMaxT];  // third state tensor (AMSGrad), else 0
+  uintptr_t w[kMaxT];   // fp32 master (or 0)
+  int64_t numel[kMaxT];
+  int32_t start[kMaxT + 1];
+  int32_t tidx[kMaxT];  // position of the leaf in the CALL's lists (per-leaf scales, sums)
+  int64_t pbase;        // workgroups of the call's earlier launches (index of this one's first partial)
+  int n;
+};
+
+template <typename P> struct Comp { using type = float; };
+template <> struct Comp<double> { using type = double; };
+
+// clamp(g, -delta, delta) with torch.clamp's NaN behaviour (a NaN stays a NaN); delta == 0: off
+template <typename C>
+__device__ __forceinline__ C clip_grad(C g, C delta) {
+  if (delta > C(0)) g = g < -delta ? -delta : (g > delta ? delta : g);
+  return g;
+}
+
+template <typename F>
+void for_each_group(const std::vector<uintptr_t>& p, const std::vector<uintptr_t>& g,
+                    const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
+                    const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& w,
+                    const std::vector<int64_t>& numel, F&& launch) {
+  const size_t N = numel.size();
+  if (p.size() != N || g.size() != N) throw std::runtime_error("optimizer kernel: list length mismatch");
+  if ((!s1.empty() && s1.size() != N) || (!s2.empty() && s2.size() != N) || (!s3.empty() && s3.size() != N) ||
+      (!w.empty() && w.size() != N))
+    throw std::runtime_error("optimizer kernel: state list length mismatch");
+  OptArgs a{};
+  int n = 0;
+  int32_t blocks = 0;
+  int64_t pbase = 0;
+  auto flush = [&]() {
+    if (n == 0) return;
+    a.n = n;
+    a.start[n] = blocks;
+    a.pbase = pbase;
+    launch(a, blocks);
+    pbase += blocks;
+    a = OptArgs{};
+    n = 0;
+    blocks = 0;
+  };
+  for (size_t i = 0; i < N; ++i) {
+    if (numel[i] <= 0) continue;
+    const int64_t nb = (numel[i] + kChunk - 1) / kChunk;
+    if (n == kMaxT || int64_t(blocks) + nb > (int64_t(1) << 30)) flush();
+    a.p[n] = p[i];
+    a.g[n] = g[i];
+    a.s1[n] = s1.empty() ? 0 : s1[i];
+    a.s2[n] = s2.empty() ? 0 : s2[i];
+    a.s3[n] = s3.empty() ? 0 : s3[i];
+    a.w[n] = w.empty() ? 0 : w[i];
+    a.numel[n] = numel[i];
+    a.tidx[n] = static_cast<int32_t>(i);
+    a.start[n] = blocks;
+    blocks += static_cast<int32_t>(nb);
+    ++n;
+  }
+  flush();
+}
+
+// (parameter, gradient, state, fp32 master) combinations of the update kernels
+#define OPT_DTYPE_COMBOS(X)            \
+  X(float, float, float, false)          \
+  X(float, bf16, float, false)           \
+  X(bf16, bf16, bf16, false)             \
+  X(bf16, bf16, float, false)            \
+  X(bf16, bf16, float, true)             \
+  X(bf16, float, float, true)            \
+  X(f16, f16, f16, false)                \
+  X(f16, f16, float, false)              \
+  X(f16, f16, float, true)               \
+  X(f16, float, float, true)             \
+  X(double, double, double, false)
+
+template <typename T> constexpr int code_of();
+template <> constexpr int code_of<float>() { return kF32; }
+template <> constexpr int code_of<bf16>() { return kBF16; }
+template <> constexpr int code_of<f16>() { return kF16; }
+template <> constexpr int code_of<double>() { return kF64; }
+
+}  // namespace fluxmpi

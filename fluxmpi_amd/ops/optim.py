@@ -1,4 +1,5 @@
-"""Fused multi-tensor optimiser steps (wrappers of ``csrc/kernels/optim.hip``).
+"""Fused multi-tensor optimiser steps (wrappers of ``csrc/kernels/optim.hip`` — Adam, the SGD
+family, sums of squares — and ``csrc/kernels/optim_rules.hip`` — the rest of the rule set).
 
 Each function updates many (param, grad, state...) tuples in one launch per
 dtype group. CPU tensors use the PyTorch reference math, which mirrors the
@@ -200,6 +201,145 @@ def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, wei
         p.copy_(x)
 
 
+# kind -> (code of the kernel's rule switch, state tensors per leaf, reads beta^t)
+RULES = {
+    "rmsprop": (0, 1, False),
+    "adagrad": (1, 1, False),
+    "lion": (2, 1, False),
+    "adamax": (3, 2, True),
+    "amsgrad": (4, 3, False),
+    "nadam": (5, 2, True),
+    "adabelief": (6, 2, True),
+    "adadelta": (7, 2, False),
+}
+
+
+def _rule_info(kind: str) -> tuple:
+    try:
+        return RULES[kind]
+    except KeyError:
+        raise ValueError(f"fused optimiser: unknown rule {kind!r} (one of {sorted(RULES)})") from None
+
+
+def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0.0, beta2: float = 0.0,
+          rho: float | None = None, eps: float = 0.0, bt1: float = 0.0, bt2: float = 0.0, masters=None,
+          dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
+          tscale: torch.Tensor | None = None, clip_delta: float = 0.0, weight_decay: float = 0.0,
+          grad_scale: float = 1.0) -> None:
+    """In-place fused step of one of :data:`RULES` over lists of tensors (``optim_rules.hip``).
+
+    ``states``: one list of tensors per state slot of the rule, in the order of its Optimisers.jl
+    state (RMSProp / AdaGrad ``[acc]``, Lion ``[m]``, AdaMax ``[m, u]``, AMSGrad ``[m, v, v̂]``,
+    NAdam ``[m, v]``, AdaBelief ``[m, s]``, AdaDelta ``[acc, Δ]``). ``rho`` (RMSProp, AdaDelta)
+    is another name of ``beta1``. ``bt1`` / ``bt2`` are ``beta^t`` (AdaMax, NAdam, AdaBelief:
+    Optimisers.jl keeps them in the state and starts them at ``beta``); ``dev_hyper`` (fp32
+    ``[lr, beta1^t, beta2^t]``, or ``[lr]`` for the rules without ``beta^t``) overrides them for
+    HIP-graph replay, advanced by :func:`adam_advance_`. ``weight_decay`` adds ``wd * x`` to the
+    rule's ``dx'`` (an ``OptimiserChain(rule, WeightDecay)``); the clip arguments are
+    :func:`adam_`'s."""
+    code, ns, has_bt = _rule_info(kind)
+    if rho is not None:
+        beta1 = rho
+    states = [list(s) for s in states]
+    if len(states) != ns or any(len(s) != len(params) for s in states) or len(grads) != len(params):
+        raise ValueError(f"fused {kind}: needs {ns} state list(s) and a gradient per parameter")
+    if masters is not None and len(masters) != len(params):
+        raise ValueError(f"fused {kind}: needs a master per parameter")
+    if dev_hyper is not None and (dev_hyper.dtype != torch.float32 or dev_hyper.numel() < (3 if has_bt else 1)
+                                  or not dev_hyper.is_contiguous()):
+        raise TypeError(f"fused {kind}: dev_hyper is a contiguous fp32 tensor of {3 if has_bt else 1} entries")
+    if not params:
+        return
+    if params[0].is_cuda:
+        C = _ext.get(required=True)
+        stream = torch.cuda.current_stream(params[0].device).cuda_stream
+        groups: dict = {}
+        for i, p in enumerate(params):
+            sd = states[0][i].dtype
+            if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
+                    or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
+                raise TypeError(f"fused {kind}: leaf {i}: gradient, states and master must match the parameter's "
+                                "size (states of one dtype, fp32 master)")
+            groups.setdefault((p.dtype, grads[i].dtype, sd, masters is not None), []).append(i)
+        for (pd, gd, sd, hm), idx in groups.items():
+            if not supported(pd, gd, sd, hm):
+                raise TypeError(f"fused {kind}: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
+            st = [[s[i].data_ptr() for i in idx] for s in states] + [[]] * (3 - ns)
+            C.mt_rule(code, [params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx], st[0], st[1], st[2],
+                      [masters[i].data_ptr() for i in idx] if hm else [],
+                      [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
+                      float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
+                      float(weight_decay), float(grad_scale),
+                      dev_hyper.data_ptr() if dev_hyper is not None else 0,
+                      dev_gscale.data_ptr() if dev_gscale is not None else 0,
+                      _tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), float(clip_delta), stream)
+        return
+    if dev_hyper is not None:
+        h = dev_hyper.tolist()
+        lr = h[0]
+        if has_bt:
+            bt1, bt2 = h[1], h[2]
+    if dev_gscale is not None:
+        grad_scale = grad_scale * float(dev_gscale)
+    rule_reference_(kind, params, grads, states, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
+                    masters=masters, tscale=tscale, clip_delta=clip_delta, weight_decay=weight_decay,
+                    grad_scale=grad_scale)
+
+
+def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta2=0.0, rho=None, eps=0.0, bt1=0.0,
+                    bt2=0.0, masters=None, tscale=None, clip_delta=0.0, weight_decay=0.0, grad_scale=1.0):
+    """PyTorch reference of :func:`rule_`, term by term as the rules of ``optimisers`` write them
+    (compute in fp32, or fp64 for fp64 params): the CPU path and the kernels' oracle."""
+    _, ns, _ = _rule_info(kind)
+    if rho is not None:
+        beta1 = rho
+    b1, b2 = beta1, beta2
+    for i, p in enumerate(params):
+        ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        g = grads[i].to(ct) * grad_scale if grad_scale != 1.0 else grads[i].to(ct)
+        g = _clip_reference(g, i, tscale, clip_delta)
+        s = [st[i].to(ct) for st in states]
+        x = masters[i].to(ct) if masters is not None else p.to(ct)
+        if kind == "rmsprop":
+            s[0] = s[0] * b1 + (1 - b1) * (g * g)
+            dx = g * lr / (torch.sqrt(s[0]) + eps)
+        elif kind == "adagrad":
+            s[0] = s[0] + g * g
+            dx = g * lr / (torch.sqrt(s[0]) + eps)
+        elif kind == "lion":
+            dx = lr * torch.sign(s[0] * b1 + (1 - b1) * g)
+            s[0] = s[0] * b2 + (1 - b2) * g
+        elif kind == "adamax":
+            s[0] = s[0] * b1 + (1 - b1) * g
+            s[1] = torch.maximum(s[1] * b2, g.abs())
+            dx = lr / (1 - bt1) * s[0] / (s[1] + eps)
+        elif kind == "amsgrad":
+            s[0] = s[0] * b1 + (1 - b1) * g
+            s[1] = s[1] * b2 + (1 - b2) * (g * g)
+            s[2] = torch.maximum(s[2], s[1])
+            dx = lr * s[0] / (torch.sqrt(s[2]) + eps)
+        elif kind == "nadam":
+            s[0] = s[0] * b1 + (1 - b1) * g
+            s[1] = s[1] * b2 + (1 - b2) * (g * g)
+            dx = (b1 * s[0] / (1 - b1 * bt1) + (1 - b1) * g / (1 - bt1)) / (torch.sqrt(s[1] * b2 / (1 - bt2)) + eps) * lr
+        elif kind == "adabelief":
+            s[0] = s[0] * b1 + (1 - b1) * g
+            s[1] = s[1] * b2 + (1 - b2) * (g - s[0]) ** 2 + eps
+            dx = lr * s[0] / (1 - bt1) / (torch.sqrt(s[1] / (1 - bt2)) + eps)
+        else:  # adadelta
+            s[0] = s[0] * b1 + (1 - b1) * (g * g)
+            dx = g * torch.sqrt(s[1] + eps) / torch.sqrt(s[0] + eps)
+            s[1] = s[1] * b1 + (1 - b1) * (dx * dx)
+        if weight_decay != 0.0:
+            dx = dx + weight_decay * x
+        x = x - dx
+        for k in range(ns):
+            states[k][i].copy_(s[k])
+        if masters is not None:
+            masters[i].copy_(x)
+        p.copy_(x)
+
+
 def sumsq_partials(grads) -> int:
     """Entries of the ``partials`` workspace :func:`sumsq_` needs for ``grads`` (one per 4096-element chunk)."""
     return sum((g.numel() + 4095) // 4096 for g in grads)
@@ -281,4 +421,5 @@ def bias_corrections(beta1_t: float, beta2_t: float) -> tuple[float, float]:
 
 
 __all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_", "supported", "bias_corrections",
+           "rule_", "rule_reference_", "RULES",
            "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_"]

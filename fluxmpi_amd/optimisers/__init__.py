@@ -11,8 +11,16 @@ Descent(η)     ``None``                                         ``η·dx``
 Momentum(η,ρ)  ``vel`` (zeros like x)                           ``vel = ρ·vel + η·dx``
 Nesterov(η,ρ)  ``vel``                                          ``-ρ²·vel + (1+ρ)·η·dx``
 RMSProp(η,ρ,ϵ) ``acc``                                          ``dx·η / (sqrt(acc)+ϵ)``
+AdaGrad(η,ϵ)   ``acc`` (filled with ϵ), ``acc += dx²``          ``dx·η / (sqrt(acc)+ϵ)``
 Adam(η,β,ϵ)    ``(mt, vt, (β1ᵗ, β2ᵗ))``, βᵗ starts at β         ``mt/(1-β1ᵗ)/(sqrt(vt/(1-β2ᵗ))+ϵ)·η``
 AdamW(η,β,γ,ϵ) ``OptimiserChain(Adam, WeightDecay(γ))``         Adam's dx' + γ·x
+Lion(η,β)      ``m``, then ``m = β2·m + (1-β2)·dx``             ``η·sign(β1·m + (1-β1)·dx)``
+AdaMax(η,β,ϵ)  ``(m, u, βᵗ)``, ``u = max(β2·u, |dx|)``          ``η/(1-β1ᵗ)·m/(u+ϵ)``
+AMSGrad(η,β,ϵ) ``(m, v, v̂)`` each filled with ϵ, v̂ = max(v̂,v)  ``η·m/(sqrt(v̂)+ϵ)``
+NAdam(η,β,ϵ)   ``(m, v, βᵗ)``                                   ``(β1·m/(1-β1·β1ᵗ) + (1-β1)·dx/(1-β1ᵗ))``
+                                                                ``/(sqrt(v·β2/(1-β2ᵗ))+ϵ)·η``
+AdaBelief(η,β,ϵ) ``(m, s, βᵗ)``, ``s = β2·s+(1-β2)·(dx-m)²+ϵ``  ``η·m/(1-β1ᵗ)/(sqrt(s/(1-β2ᵗ))+ϵ)``
+AdaDelta(ρ,ϵ)  ``(acc, Δ)``, ``Δ = ρ·Δ + (1-ρ)·dx'²``           ``dx·sqrt(Δ+ϵ)/sqrt(acc+ϵ)``
 WeightDecay(γ) ``None``                                         ``dx + γ·x``
 ClipGrad(δ)    ``None``                                         ``clamp(dx, -δ, δ)``
 ClipNorm(ω,p)  ``None``                                         ``dx · min(1, ω/‖dx‖ₚ)``
@@ -219,7 +227,37 @@ def _sgd_batch(rule, items, rho, nesterov, clip=None):
     return out
 
 
-class RMSProp(AbstractRule):
+class _KernelRule(AbstractRule):
+    """A rule with a fused multi-tensor form in ``ops.optim.rule_`` (``_kind``: its name there)."""
+
+    _kind = ""
+
+    def _tensors(self, state) -> list:
+        """The state's tensors in the kernel's slot order."""
+        return [state] if isinstance(state, torch.Tensor) else list(state[:_fused.RULES[self._kind][1]])
+
+    def _hyper(self, x=None) -> dict:
+        """The kernel's hyperparameters, rounded to ``x``'s precision as ``apply`` does (``_T``,
+        ``_eps``); ``x=None``: as given (the DDP engine computes in fp32)."""
+        raise NotImplementedError
+
+    def _r(self, x, v):
+        return float(v) if x is None else _T(x, v)
+
+    def _e(self, x, v):
+        return float(v) if x is None else _eps(x, v)
+
+
+class _FusedRule(_KernelRule):
+    """A kernel rule whose GPU leaves take the fused path in the functional API too."""
+
+    def apply_batch(self, items):
+        return _rule_batch(self, items, 0.0)
+
+
+class RMSProp(_KernelRule):
+    _kind = "rmsprop"
+
     def __init__(self, eta: float = 0.001, rho: float = 0.9, epsilon: float = 1e-8):
         self.eta, self.rho, self.epsilon = eta, rho, epsilon
 
@@ -231,8 +269,13 @@ class RMSProp(AbstractRule):
         acc.mul_(rho).addcmul_(dx, dx, value=1 - rho)
         return acc, dx * eta / (torch.sqrt(acc) + eps)
 
+    def _hyper(self, x=None):
+        return {"lr": self._r(x, self.eta), "rho": self._r(x, self.rho), "eps": self._e(x, self.epsilon)}
 
-class AdaGrad(AbstractRule):
+
+class AdaGrad(_KernelRule):
+    _kind = "adagrad"
+
     def __init__(self, eta: float = 0.1, epsilon: float = 1e-8):
         self.eta, self.epsilon = eta, epsilon
 
@@ -242,6 +285,142 @@ class AdaGrad(AbstractRule):
     def apply(self, acc, x, dx):
         acc.addcmul_(dx, dx)
         return acc, dx * _T(x, self.eta) / (torch.sqrt(acc) + _eps(x, self.epsilon))
+
+    def _hyper(self, x=None):
+        return {"lr": self._r(x, self.eta), "eps": self._e(x, self.epsilon)}
+
+
+class _BetaRule(_FusedRule):
+    """Shared by the rules with Adam's hyperparameters ``(η, β, ϵ)``."""
+
+    def __init__(self, eta: float = 0.001, beta: tuple = (0.9, 0.999), epsilon: float = 1e-8):
+        self.eta, self.beta, self.epsilon = eta, tuple(beta), epsilon
+
+    def _hyper(self, x=None):
+        return {"lr": self._r(x, self.eta), "beta1": self._r(x, self.beta[0]), "beta2": self._r(x, self.beta[1]),
+                "eps": self._e(x, self.epsilon)}
+
+    def _cast(self, x):
+        return _T(x, self.eta), _T(x, self.beta[0]), _T(x, self.beta[1]), _eps(x, self.epsilon)
+
+    def _bt0(self, x):
+        return (_T(x, self.beta[0]), _T(x, self.beta[1]))
+
+
+class Lion(_FusedRule):
+    """``Lion(η=0.001, β=(0.9, 0.999))``; state ``m``."""
+
+    _kind = "lion"
+
+    def __init__(self, eta: float = 0.001, beta: tuple = (0.9, 0.999)):
+        self.eta, self.beta = eta, tuple(beta)
+
+    def init(self, x):
+        return torch.zeros_like(x)
+
+    def apply(self, m, x, dx):
+        eta, b1, b2 = _T(x, self.eta), _T(x, self.beta[0]), _T(x, self.beta[1])
+        dxp = eta * torch.sign(b1 * m + (1 - b1) * dx)
+        m.mul_(b2).add_(dx, alpha=1 - b2)
+        return m, dxp
+
+    def _hyper(self, x=None):
+        return {"lr": self._r(x, self.eta), "beta1": self._r(x, self.beta[0]), "beta2": self._r(x, self.beta[1])}
+
+
+class AdaMax(_BetaRule):
+    """``AdaMax(η=0.001, β=(0.9, 0.999), ϵ=1e-8)``; state ``(m, u, βt)``."""
+
+    _kind = "adamax"
+
+    def init(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x), self._bt0(x))
+
+    def apply(self, state, x, dx):
+        eta, b1, b2, eps = self._cast(x)
+        m, u, bt = state
+        m.mul_(b1).add_(dx, alpha=1 - b1)
+        torch.maximum(u * b2, dx.abs(), out=u)
+        dxp = eta / (1 - bt[0]) * m / (u + eps)
+        return (m, u, (_T(x, bt[0] * b1), _T(x, bt[1] * b2))), dxp
+
+
+class AMSGrad(_BetaRule):
+    """``AMSGrad(η=0.001, β=(0.9, 0.999), ϵ=1e-8)``; state ``(m, v, v̂)``, each filled with ϵ."""
+
+    _kind = "amsgrad"
+
+    def init(self, x):
+        return (torch.full_like(x, self.epsilon), torch.full_like(x, self.epsilon), torch.full_like(x, self.epsilon))
+
+    def apply(self, state, x, dx):
+        eta, b1, b2, eps = self._cast(x)
+        m, v, vh = state
+        m.mul_(b1).add_(dx, alpha=1 - b1)
+        v.mul_(b2).addcmul_(dx, dx, value=1 - b2)
+        torch.maximum(vh, v, out=vh)
+        return (m, v, vh), eta * m / (torch.sqrt(vh) + eps)
+
+
+class NAdam(_BetaRule):
+    """``NAdam(η=0.001, β=(0.9, 0.999), ϵ=1e-8)``; state ``(m, v, βt)``."""
+
+    _kind = "nadam"
+
+    def init(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x), self._bt0(x))
+
+    def apply(self, state, x, dx):
+        eta, b1, b2, eps = self._cast(x)
+        m, v, bt = state
+        m.mul_(b1).add_(dx, alpha=1 - b1)
+        v.mul_(b2).addcmul_(dx, dx, value=1 - b2)
+        dxp = (b1 * m / (1 - b1 * bt[0]) + (1 - b1) * dx / (1 - bt[0])) / (torch.sqrt(v * b2 / (1 - bt[1])) + eps) * eta
+        return (m, v, (_T(x, bt[0] * b1), _T(x, bt[1] * b2))), dxp
+
+
+class AdaBelief(_BetaRule):
+    """``AdaBelief(η=0.001, β=(0.9, 0.999), ϵ=1e-16)``; state ``(m, s, βt)``."""
+
+    _kind = "adabelief"
+
+    def __init__(self, eta: float = 0.001, beta: tuple = (0.9, 0.999), epsilon: float = 1e-16):
+        super().__init__(eta, beta, epsilon)
+
+    def init(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x), self._bt0(x))
+
+    def apply(self, state, x, dx):
+        eta, b1, b2, eps = self._cast(x)
+        m, s, bt = state
+        m.mul_(b1).add_(dx, alpha=1 - b1)
+        d = dx - m
+        s.mul_(b2).addcmul_(d, d, value=1 - b2).add_(eps)
+        dxp = eta * m / (1 - bt[0]) / (torch.sqrt(s / (1 - bt[1])) + eps)
+        return (m, s, (_T(x, bt[0] * b1), _T(x, bt[1] * b2))), dxp
+
+
+class AdaDelta(_FusedRule):
+    """``AdaDelta(ρ=0.9, ϵ=1e-7)``; state ``(acc, Δ)``. No learning rate."""
+
+    _kind = "adadelta"
+
+    def __init__(self, rho: float = 0.9, epsilon: float = 1e-7):
+        self.rho, self.epsilon = rho, epsilon
+
+    def init(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x))
+
+    def apply(self, state, x, dx):
+        rho, eps = _T(x, self.rho), _eps(x, self.epsilon)
+        acc, delta = state
+        acc.mul_(rho).addcmul_(dx, dx, value=1 - rho)
+        dxp = dx * torch.sqrt(delta + eps) / torch.sqrt(acc + eps)
+        delta.mul_(rho).addcmul_(dxp, dxp, value=1 - rho)
+        return (acc, delta), dxp
+
+    def _hyper(self, x=None):
+        return {"rho": self._r(x, self.rho), "eps": self._e(x, self.epsilon)}
 
 
 class Adam(AbstractRule):
@@ -347,6 +526,48 @@ def _adam_batch(rule: Adam, items, weight_decay: float, clip=None):
     return out
 
 
+def _rule_batch(rule: _KernelRule, items, weight_decay: float, clip=None):
+    """Fused multi-tensor step of a kernel rule on GPU leaves (x updated in place, dx' = None), the
+    per-leaf ``apply`` elsewhere; ``weight_decay``: a WeightDecay behind the rule; ``clip`` as in
+    :func:`_adam_batch`."""
+    _, ns, has_bt = _fused.RULES[rule._kind]
+    out: list = [None] * len(items)
+    fused: dict = {}
+    for i, (leaf, x, dx) in enumerate(items):
+        st = leaf.state
+        ts = rule._tensors(st) if isinstance(st, (tuple, torch.Tensor)) else []
+        ok = (x.is_cuda and dx is not None and len(ts) == ns and all(isinstance(t, torch.Tensor) for t in ts)
+              and (not has_bt or len(st) == 3) and _same_dense(x, dx, *ts)
+              and all(t.dtype == ts[0].dtype for t in ts) and _fused.supported(x.dtype, dx.dtype, ts[0].dtype, False))
+        if ok:
+            # same precision and beta^t -> one launch (the sum of squares takes one gradient dtype)
+            fused.setdefault((x.device, x.dtype, dx.dtype, tuple(st[2]) if has_bt else None), []).append(i)
+        else:
+            if clip is not None:
+                dx = clip.apply(None, x, dx)[1]
+            st, d = rule.apply(st, x, dx)
+            if weight_decay:
+                d = d + _T(x, weight_decay) * x
+            leaf.state, out[i] = st, d
+    for (_, _, _, bt), idx in fused.items():
+        x0 = items[idx[0]][1]
+        xs = [items[i][1] for i in idx]
+        gs = [items[i][2] for i in idx]
+        per_leaf = [rule._tensors(items[i][0].state) for i in idx]
+        kw = rule._hyper(x0)  # rounded to the leaves' precision, as in Julia (``_T``)
+        if has_bt:
+            kw.update(bt1=bt[0], bt2=bt[1])
+        _fused.rule_(rule._kind, xs, gs, [[t[k] for t in per_leaf] for k in range(ns)],
+                     weight_decay=_T(x0, weight_decay) if weight_decay else 0.0, **kw, **_clip_kwargs(clip, x0, gs))
+        for i in idx:
+            leaf, x = items[i][0], items[i][1]
+            if has_bt:
+                a, b, t = leaf.state
+                leaf.state = (a, b, (_T(x, t[0] * _T(x, rule.beta[0])), _T(x, t[1] * _T(x, rule.beta[1]))))
+            out[i] = None
+    return out
+
+
 class WeightDecay(AbstractRule):
     def __init__(self, gamma: float = 5e-4):
         self.gamma = gamma
@@ -394,31 +615,41 @@ class OptimiserChain(AbstractRule):
             new.append(s)
         return tuple(new), dx
 
-    def _is_adamw(self) -> bool:
-        return len(self.opts) == 2 and isinstance(self.opts[0], Adam) and isinstance(self.opts[1], WeightDecay)
+    @staticmethod
+    def _decays(r, engine: bool = False) -> bool:
+        """``r`` takes a fused ``WeightDecay`` behind it (the kernels' ``dx' += γ·x`` epilogue)."""
+        return isinstance(r, (Adam, _KernelRule if engine else _FusedRule))
 
-    def fused_plan(self):
+    def _is_adamw(self, engine: bool = False) -> bool:
+        return len(self.opts) == 2 and self._decays(self.opts[0], engine) and isinstance(self.opts[1], WeightDecay)
+
+    def fused_plan(self, engine: bool = False):
         """``(clip, inner, where)`` when the chain has a fused batch form, else ``None``.
 
         ``clip``: a leading ``ClipNorm(p=2)`` / ``ClipGrad`` (or None); ``inner``: the update rule
-        — Adam, an Adam + WeightDecay chain, Descent, Momentum or Nesterov; ``where``: the
-        position of ``inner``'s state in the chain's state tuple (None: the tuple itself, the
-        flat ``(clip, Adam, WeightDecay)`` spelling, whose Adam state is ``states[1]``)."""
-        if self._is_adamw():
+        — Adam, Lion, AdaMax, AMSGrad, NAdam, AdaBelief or AdaDelta, one of them in a chain with
+        WeightDecay, or Descent, Momentum or Nesterov; ``where``: the position of ``inner``'s
+        state in the chain's state tuple (None: the tuple itself, the flat ``(clip, rule,
+        WeightDecay)`` spelling, whose rule state is ``states[1]``). ``engine``: the plan of the
+        DDP engine, which also runs RMSProp and AdaGrad fused (in the functional API a chain
+        around them keeps its per-leaf results)."""
+        if self._is_adamw(engine):
             return None, self, None
         o = self.opts
         if len(o) < 2 or not (isinstance(o[0], ClipGrad) or (isinstance(o[0], ClipNorm) and o[0].p == 2)):
             return None
         if len(o) == 2 and (type(o[1]) in (Adam, Descent, Momentum, Nesterov)
-                            or (isinstance(o[1], OptimiserChain) and o[1]._is_adamw())):
+                            or isinstance(o[1], _KernelRule if engine else _FusedRule)
+                            or (isinstance(o[1], OptimiserChain) and o[1]._is_adamw(engine))):
             return o[0], o[1], 1
-        if len(o) == 3 and isinstance(o[1], Adam) and isinstance(o[2], WeightDecay):
+        if len(o) == 3 and self._decays(o[1], engine) and isinstance(o[2], WeightDecay):
             return o[0], OptimiserChain(o[1], o[2]), None
         return None
 
     def apply_batch(self, items):
-        # Fuse the common shapes into one kernel per dtype group: AdamW (Adam then WeightDecay),
-        # and a leading ClipNorm(p=2) / ClipGrad in front of Adam, AdamW, Descent, Momentum or
+        # Fuse the common shapes into one kernel per dtype group: a rule with a decaying kernel
+        # (Adam, Lion, AdaMax, AMSGrad, NAdam, AdaBelief, AdaDelta) then WeightDecay, and a leading
+        # ClipNorm(p=2) / ClipGrad in front of such a rule, such a pair, Descent, Momentum or
         # Nesterov (the clip rides in the update kernel; ClipNorm's per-leaf scales come from a
         # multi-tensor sum of squares). The state keeps the chain's tuple-of-member-states layout.
         plan = self.fused_plan()
@@ -441,6 +672,8 @@ class OptimiserChain(AbstractRule):
         sub = [(Leaf(rule, get(leaf.state)[0] if adamw else get(leaf.state)), x, dx) for leaf, x, dx in items]
         if isinstance(rule, Adam):
             out = _adam_batch(rule, sub, inner.opts[1].gamma if adamw else 0.0, clip)
+        elif isinstance(rule, _KernelRule):
+            out = _rule_batch(rule, sub, inner.opts[1].gamma if adamw else 0.0, clip)
         else:
             out = _sgd_batch(rule, sub, getattr(rule, "rho", 0.0), isinstance(rule, Nesterov), clip)
         for (leaf, _, _), (sl, _, _) in zip(items, sub):
@@ -650,6 +883,7 @@ def _leaves_of(tree):
 
 __all__ = [
     "AbstractRule", "Leaf", "Descent", "Momentum", "Nesterov", "RMSProp", "AdaGrad", "Adam", "AdamW",
+    "Lion", "AdaMax", "AMSGrad", "NAdam", "AdaBelief", "AdaDelta",
     "WeightDecay", "ClipGrad", "ClipNorm", "OptimiserChain", "OptimizerChain", "setup", "update", "update_",
     "update_inplace", "freeze_", "thaw_", "adjust_",
 ]

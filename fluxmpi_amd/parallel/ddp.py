@@ -26,8 +26,9 @@ for MI355X + RCCL over xGMI:
    the compute stream). Buckets are launched strictly in index order on every
    rank, so collectives can never be mismatched across ranks.
 4. **Fused optimiser.** ``step()`` waits per bucket and runs one fused
-   multi-tensor HIP kernel per bucket (Adam/AdamW/Descent/Momentum/Nesterov
-   with Optimisers.jl numerics; optional fp32 master weights for bf16
+   multi-tensor HIP kernel per bucket (Adam/AdamW/Descent/Momentum/Nesterov,
+   RMSProp/AdaGrad/Lion/AdaMax/AMSGrad/NAdam/AdaBelief/AdaDelta, each also with
+   WeightDecay, with Optimisers.jl numerics; optional fp32 master weights for bf16
    models). Step-dependent scalars (``beta^t``) live on the device, so the
    whole step can be captured in a HIP graph.
 5. **Semantics.** Gradients are SUMmed like the reference; ``average=True``
@@ -88,6 +89,7 @@ class _Bucket:
     master: torch.Tensor | None = None
     exp_avg: torch.Tensor | None = None
     exp_avg_sq: torch.Tensor | None = None
+    state3: torch.Tensor | None = None  # third state buffer (AMSGrad's running maximum)
     pending: int = 0
     ready: bool = False
     launched: bool = False
@@ -130,7 +132,9 @@ class DDP:
     Parameters
     ----------
     module: the model (already on its device, in its compute dtype/memory format).
-    rule:   an ``optimisers`` rule (Adam, AdamW chain, Descent, Momentum, Nesterov), optionally
+    rule:   an ``optimisers`` rule (Adam, Descent, Momentum, Nesterov, RMSProp, AdaGrad, Lion, AdaMax,
+            AMSGrad, NAdam, AdaBelief, AdaDelta; all but the SGD family also in a chain with
+            WeightDecay, as AdamW is), optionally
             behind a clip: ``OptimiserChain(ClipNorm(omega), rule)`` (per-leaf L2 norm) or
             ``OptimiserChain(ClipGrad(delta), rule)``; the engine runs it with fused flat-buffer
             kernels (the clip inside the update kernel, the norms from a deterministic
@@ -369,7 +373,7 @@ class DDP:
         # a leading ClipNorm(p=2) / ClipGrad of a chain rides in the update kernels
         self._clip_rule, self._chain_where = None, None
         if isinstance(r, O.OptimiserChain):
-            plan = r.fused_plan()
+            plan = r.fused_plan(engine=True)
             if plan is None:
                 raise TypeError(f"DDP: no fused kernel for rule {r!r}; use the functional optimisers API")
             self._clip_rule, r, self._chain_where = plan
@@ -378,19 +382,24 @@ class DDP:
             raise ValueError("DDP: clip_global_norm and a ClipNorm chain both rescale by a norm; use one of them")
         self._norms = self._per_leaf or self.clip_global_norm is not None
         self._upd = r  # the update rule behind the clip
-        if isinstance(r, O.OptimiserChain) and len(r.opts) == 2 and isinstance(r.opts[0], O.Adam) \
-                and isinstance(r.opts[1], O.WeightDecay):
-            self.kind, self.adam, self.wd = "adam", r.opts[0], r.opts[1].gamma
-        elif isinstance(r, O.Adam):
-            self.kind, self.adam, self.wd = "adam", r, 0.0
+        self.wd = 0.0
+        if isinstance(r, O.OptimiserChain):  # the plan's (rule, WeightDecay) pair
+            r, self.wd = r.opts[0], r.opts[1].gamma
+        self._inner = r  # the rule whose kernel runs
+        if isinstance(r, O.Adam):
+            self.kind, self.adam = "adam", r
+        elif isinstance(r, O._KernelRule):
+            self.kind = r._kind
         elif isinstance(r, O.Nesterov):
-            self.kind, self.wd = "nesterov", 0.0
+            self.kind = "nesterov"
         elif isinstance(r, O.Momentum):
-            self.kind, self.wd = "momentum", 0.0
+            self.kind = "momentum"
         elif isinstance(r, O.Descent):
-            self.kind, self.wd = "descent", 0.0
+            self.kind = "descent"
         else:
             raise TypeError(f"DDP: no fused kernel for rule {r!r}; use the functional optimisers API")
+        # the kernel rules of ops.optim.rule_: state buffers per bucket, and whether beta^t is kept
+        _, self._nstate, self._has_bt = fused.RULES.get(self.kind, (None, 0, self.kind == "adam"))
         dev = self.device
         for b in self.buckets:
             low = b.dtype in (torch.bfloat16, torch.float16)
@@ -403,6 +412,11 @@ class DDP:
                 b.exp_avg_sq = torch.zeros(b.numel, dtype=sdt, device=dev)
             elif self.kind in ("momentum", "nesterov"):
                 b.exp_avg = torch.zeros(b.numel, dtype=sdt, device=dev)
+            elif self._nstate:
+                # AdaGrad's and AMSGrad's states start at epsilon (Optimisers.jl init), the rest at 0
+                fill = float(r.epsilon) if self.kind in ("adagrad", "amsgrad") else 0.0
+                bufs = [torch.full((b.numel,), fill, dtype=sdt, device=dev) for _ in range(self._nstate)]
+                b.exp_avg, b.exp_avg_sq, b.state3 = (bufs + [None, None])[:3]
         # gradient norms: per bucket dtype one [2, leaves] buffer of per-leaf sums of squares and
         # scales and one of the sum-of-squares kernel's partials; every bucket owns a slice, so the
         # norms of all buckets can be taken in one multi-tensor call (step()) or bucket by bucket
@@ -424,12 +438,12 @@ class DDP:
                 self._clip_groups.append((bs, buf, parts))
         # [sum of squares, norm, global clip scale] of the step's whole gradient (device, fp32)
         self._clip_slot = torch.zeros(3, dtype=torch.float32, device=dev) if self._norms else None
-        if self.kind == "adam":
-            a = self.adam
+        if self._has_bt:
+            a = self._inner
             # device hyper block [lr, beta1^t, beta2^t]; beta^t starts at beta (Optimisers.jl init)
             self.hyper = torch.tensor([a.eta, a.beta[0], a.beta[1]], dtype=torch.float32, device=dev)
-        else:
-            self.hyper = torch.tensor([self._upd.eta], dtype=torch.float32, device=dev)
+        else:  # [lr]; AdaDelta has no learning rate (the entry is not read)
+            self.hyper = torch.tensor([getattr(self._inner, "eta", 0.0)], dtype=torch.float32, device=dev)
 
     def broadcast_parameters(self, root_rank: int = 0):
         """One broadcast per flat bucket (+ its fp32 master) + module buffers (``synchronize``
@@ -808,8 +822,8 @@ class DDP:
             for b, st, gs, gscale in self._deferred:
                 self._run_update(st, gs, gscale, b)
             self._deferred = []
-        if self.kind == "adam":
-            fused.adam_advance_(self.hyper, self.adam.beta[0], self.adam.beta[1])
+        if self._has_bt:
+            fused.adam_advance_(self.hyper, self._inner.beta[0], self._inner.beta[1])
         self.step_count += 1
         if self.watchdog is not None:
             self.watchdog.check()
@@ -864,13 +878,14 @@ class DDP:
         if st is None:
             def sl(flat):
                 return [flat[o:o + p.numel()] for p, o in zip(b.params, b.offsets)] if flat is not None else None
-            st = (sl(b.flat_param), sl(b.exp_avg), sl(b.exp_avg_sq), sl(b.master))
+            st = (sl(b.flat_param), sl(b.exp_avg), sl(b.exp_avg_sq), sl(b.master), sl(b.state3))
             self._direct_cache[b.index] = st
         return st
 
     def _run_update(self, st: tuple, gs: list, gscale: float, b: _Bucket):
-        """One fused update launch over ``st = (params, m, v, masters)`` lists and their gradients."""
-        ps, ms, vs, ws = st
+        """One fused update launch over ``st = (params, m, v, masters, third state)`` lists and their
+        gradients."""
+        ps, ms, vs, ws, s3 = st
         kw = {}
         if isinstance(self._clip_rule, O.ClipGrad):
             kw["clip_delta"] = self._clip_rule.delta
@@ -882,6 +897,9 @@ class DDP:
             a = self.adam
             fused.adam_(ps, gs, ms, vs, lr=a.eta, beta1=a.beta[0], beta2=a.beta[1], eps=a.epsilon, bc1=0.0,
                         bc2=0.0, weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_hyper=self.hyper, **kw)
+        elif self._nstate:
+            fused.rule_(self.kind, ps, gs, [ms, vs, s3][:self._nstate], weight_decay=self.wd, grad_scale=gscale,
+                        masters=ws, dev_hyper=self.hyper, **self._inner._hyper(), **kw)
         else:
             mom = {"descent": 0.0}.get(self.kind, getattr(self._upd, "rho", 0.0))
             fused.sgd_(ps, gs, ms, lr=self._upd.eta, momentum=mom, nesterov=self.kind == "nesterov",
@@ -917,7 +935,8 @@ class DDP:
                          gscale)
             return
         one = lambda t: [t] if t is not None else None  # noqa: E731
-        self._update(b, ([b.flat_param], one(b.exp_avg), one(b.exp_avg_sq), one(b.master)), [b.flat_grad], gscale)
+        self._update(b, ([b.flat_param], one(b.exp_avg), one(b.exp_avg_sq), one(b.master), one(b.state3)),
+                     [b.flat_grad], gscale)
 
     def _apply_direct(self, b: _Bucket, gscale: float) -> bool:
         """Fused optimiser on the autograd gradients in place (no pack). False if some gradient
@@ -948,39 +967,42 @@ class DDP:
 
     def set_lr(self, lr: float):
         """Change the learning rate (device-side, so captured graphs see it)."""
+        if not hasattr(self._inner, "eta"):
+            raise ValueError(f"DDP.set_lr: {type(self._inner).__name__} has no learning rate")
         self.hyper[0].fill_(lr)
-        if self.kind == "adam":
-            self.adam.eta = lr
-        else:
-            self._upd.eta = lr
+        self._inner.eta = lr
 
     # ------------------------------------------------------------------ state
     def optimiser_state(self):
         """Optimisers.jl-layout state tree ``{name: Leaf(rule, state)}`` (views, no copies)."""
         out = {}
-        if self.kind == "adam":
+        if self._has_bt:
             bt = self.hyper[1:].tolist()
         for b in self.buckets:
             for name, p, o in zip(b.names, b.params, b.offsets):
                 n = p.numel()
                 # moments follow the parameter's memory order (NHWC for channels_last weights)
-                if self.kind == "adam":
+                if self._has_bt:  # Adam, AdaMax, NAdam, AdaBelief: (m, v, βt)
                     st = (_strided_view(b.exp_avg, p, o), _strided_view(b.exp_avg_sq, p, o), tuple(bt))
+                elif self._nstate > 1:  # AdaDelta (acc, Δ), AMSGrad (m, v, v̂)
+                    st = tuple(_strided_view(t, p, o) for t in (b.exp_avg, b.exp_avg_sq, b.state3)[:self._nstate])
                 elif b.exp_avg is not None:
                     st = _strided_view(b.exp_avg, p, o)
                 else:
                     st = None
                 if self._clip_rule is not None:
                     # the chain's tuple of member states: (clip: None, update rule's state...)
-                    if isinstance(self._upd, O.OptimiserChain):  # Adam + WeightDecay behind the clip
+                    if isinstance(self._upd, O.OptimiserChain):  # rule + WeightDecay behind the clip
                         st = (None, (st, None)) if self._chain_where == 1 else (None, st, None)
                     else:
                         st = (None, st)
+                elif isinstance(self._upd, O.OptimiserChain) and self.kind != "adam":
+                    st = (st, None)  # (rule, WeightDecay); an unclipped AdamW keeps its bare Adam state
                 out[name] = O.Leaf(self.rule, st)
         return out
 
     def state_dict(self):
-        return {
+        sd = {
             "module": self.module.state_dict(),
             "step": self.step_count,
             "hyper": self.hyper.detach().cpu(),
@@ -989,6 +1011,10 @@ class DDP:
                          "v": b.exp_avg_sq.detach().cpu() if b.exp_avg_sq is not None else None}
                         for b in self.buckets],
         }
+        for b, s in zip(self.buckets, sd["buckets"]):
+            if b.state3 is not None:  # only the rules with a third state buffer (AMSGrad) add the key
+                s["s3"] = b.state3.detach().cpu()
+        return sd
 
     def load_state_dict(self, sd):
         with torch.no_grad():
@@ -1005,6 +1031,8 @@ class DDP:
                     b.exp_avg.copy_(s["m"])
                 if s["v"] is not None:
                     b.exp_avg_sq.copy_(s["v"])
+                if b.state3 is not None:
+                    b.state3.copy_(s["s3"])
         self._record_versions()
 
     def num_parameters(self) -> int:
