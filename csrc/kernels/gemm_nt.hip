@@ -647,10 +647,10 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_nt_kernel(NTArgs p) {
             for (int e = 0; e < 8; ++e) {
               const float x = static_cast<float>(v8[e]);
               if constexpr (GF == 1) {
-                constexpr float kK0 = 0.79788456080286536f, kK3 = 3.f * 0.044715f;
+                constexpr float kK0 = 0.79788456080286536f;
                 const float t = gelu_tanh_t(x), hx = 0.5f * x;
                 gg[e] = static_cast<bf16>(fmaf(hx, t, hx));
-                dd[e] = static_cast<bf16>(fmaf(hx * fmaf(-t, t, 1.f), kK0 * fmaf(kK3 * x, x, 1.f), fmaf(0.5f, t, 0.5f)));
+                dd[e] = static_cast<bf16>(fmaf(hx * fmaf(-t, t, 1.f), kK0 * gelu_tanh_poly3(x), fmaf(0.5f, t, 0.5f)));
               } else {
                 float cdf, ee;
                 gelu_parts(x, cdf, ee);
