@@ -83,16 +83,26 @@ def pad_c3_to_c4(x: torch.Tensor) -> torch.Tensor:
     return y.permute(0, 3, 1, 2)
 
 
-def supported(x: torch.Tensor) -> bool:
-    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16, torch.float32)
-            and x.shape[1] % 8 == 0 and 8 <= x.shape[1] <= 2048)
+def geometry_supported(k: int, s: int, p: int) -> bool:
+    """Window geometries both kernels run: the 1-byte index holds ``k * k <= 255`` taps, the padding
+    is smaller than the window, and the backward gathers from at most 3 x 3 windows per input
+    position (``ceil(k / s) <= 3``). Anything else takes the reference composition in the forward
+    (the forward kernel alone would accept ``k = 4, s = 1`` and the backward then raise mid-autograd)."""
+    return 1 <= k and k * k <= 255 and s >= 1 and 0 <= p < k and -(-k // s) <= 3
+
+
+def supported(x: torch.Tensor, k: int = 3, s: int = 2, p: int = 1) -> bool:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and x.shape[1] % 8 == 0 and 8 <= x.shape[1] <= 2048 and geometry_supported(k, s, p)):
+        return False
+    return _out(x.shape[2], k, s, p) >= 1 and _out(x.shape[3], k, s, p) >= 1
 
 
 def bn_relu_maxpool(x: torch.Tensor, bn, k: int = 3, s: int = 2, p: int = 1) -> torch.Tensor:
     """``max_pool2d(relu(bn(x)), k, s, p)`` for a training-mode BatchNorm module ``bn``."""
     from .batchnorm import bn_counter
     mom, nbt = bn_counter(bn)
-    if not (bn.training and supported(x)):
+    if not (bn.training and supported(x, k, s, p)):
         if nbt is not None:
             nbt.add_(1)
         y = F.batch_norm(x.float(), bn.running_mean, bn.running_var,

@@ -23,7 +23,8 @@ def test_global_avg_pool_cpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(2, 3, 224, 224), (3, 3, 7, 5), (1, 3, 1, 3)])
+@pytest.mark.parametrize("shape", [(2, 3, 224, 224), (3, 3, 7, 5), (1, 3, 1, 3),
+                                   (1, 3, 1, 1), (1, 3, 1, 7), (1, 3, 2, 4), (1, 3, 3, 3)])  # npix 1, 7, 8, 9
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_pad_c3_to_c4(gpu_ext, shape, dtype):
     from fluxmpi_amd.ops.pool import pad_c3_to_c4
