@@ -128,6 +128,34 @@ void bn_stats_finalize(const void* x, const float* w, const float* b, float* run
 void bn_apply(const void* x, void* y, const void* residual, const float* w, const float* b,
               const float* save_mean, const float* save_invstd, int64_t rows, int64_t C, int relu,
               uint8_t* relu_mask, int dtype, hipStream_t stream);
+// Synchronised (cross-rank) BatchNorm on the same kernels, stopped at the seams where a collective
+// belongs, with deterministic reductions (per-workgroup partials in `part`, folded in a fixed order:
+// no float atomics, bit-identical run to run). `part`: bn_sync_workspace_floats(rows, C) floats, no
+// zero fill needed. rows >= 1 (an empty shard sends a zero message and launches nothing).
+//   bn_sync_stats: msg[2C + 2] = (sum x [C], sum x^2 [C], n_hi, n_lo), rows = 4096 n_hi + n_lo.
+//     With save_mean != nullptr the finalize from the LOCAL sums runs in the same launch (world size 1).
+//   bn_sync_finalize_fwd: mean / invstd / running statistics / num_batches_tracked from a (summed)
+//     message; the count is read on the device. Follow with bn_apply.
+//   bn_sync_bwd_reduce: msg[2C] = (sum g [C], sum g xhat [C]) of this shard, also written to dbias / dweight.
+//   bn_sync_bwd_dx: dx (and dres) from a (summed) backward message. count = the (n_hi, n_lo) pair of the
+//     summed forward message and coef = 2C floats of scratch; count == nullptr: msg holds the sums of
+//     these `rows` rows alone (world size 1).
+size_t bn_sync_workspace_floats(int64_t rows, int64_t C);
+void bn_sync_stats(const void* x, float* part, float* msg, int64_t rows, int64_t C, int dtype, hipStream_t stream,
+                   float* save_mean = nullptr, float* save_invstd = nullptr, float* running_mean = nullptr,
+                   float* running_var = nullptr, float momentum = 0.f, float eps = 0.f,
+                   int64_t* num_batches_tracked = nullptr);
+void bn_sync_finalize_fwd(const float* msg, float* running_mean, float* running_var, float* save_mean,
+                          float* save_invstd, int64_t C, float momentum, float eps, hipStream_t stream,
+                          int64_t* num_batches_tracked = nullptr);
+void bn_sync_bwd_reduce(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
+                        const float* bias, const float* save_mean, const float* save_invstd, float* part, float* msg,
+                        float* dweight, float* dbias, int64_t rows, int64_t C, int relu, int dtype,
+                        hipStream_t stream);
+void bn_sync_bwd_dx(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
+                    const float* bias, const float* save_mean, const float* save_invstd, const float* msg,
+                    const float* count, float* coef, void* dx, void* dres, int64_t rows, int64_t C, int relu,
+                    int dtype, hipStream_t stream);
 // Dual BatchNorm of a downsample block: y = relu(BN(x) + BN2(x2)) (+ 1-bit ReLU mask), and its
 // backward: dx, dx2 and both BatchNorms' dweight/dbias from one reduce + one dx pass over
 // (dy, mask, x, x2). ws/ws2: two zeroed statistics workspaces. C/8 must divide 256.

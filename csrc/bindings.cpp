@@ -155,6 +155,43 @@ PYBIND11_MODULE(_C, m) {
                    reinterpret_cast<uint8_t*>(mask), dtype, S(stream));
         });
 
+  // ---- synchronised BatchNorm (deterministic reductions, split at the collectives) ----
+  m.def("bn_sync_workspace_floats", [](int64_t rows, int64_t C) { return bn_sync_workspace_floats(rows, C); });
+  m.def("bn_sync_stats",
+        [](uintptr_t x, uintptr_t part, uintptr_t msg, int64_t rows, int64_t C, int dtype, uintptr_t stream,
+           uintptr_t sm, uintptr_t si, uintptr_t rm, uintptr_t rv, float momentum, float eps, uintptr_t nbt) {
+          auto W = [](uintptr_t p) { return reinterpret_cast<float*>(p); };
+          bn_sync_stats(reinterpret_cast<const void*>(x), W(part), W(msg), rows, C, dtype, S(stream), W(sm), W(si),
+                        W(rm), W(rv), momentum, eps, reinterpret_cast<int64_t*>(nbt));
+        });
+  m.def("bn_sync_finalize_fwd",
+        [](uintptr_t msg, uintptr_t rm, uintptr_t rv, uintptr_t sm, uintptr_t si, int64_t C, float momentum, float eps,
+           uintptr_t stream, uintptr_t nbt) {
+          auto W = [](uintptr_t p) { return reinterpret_cast<float*>(p); };
+          bn_sync_finalize_fwd(reinterpret_cast<const float*>(msg), W(rm), W(rv), W(sm), W(si), C, momentum, eps,
+                               S(stream), reinterpret_cast<int64_t*>(nbt));
+        });
+  m.def("bn_sync_bwd_reduce",
+        [](uintptr_t dy, uintptr_t x, uintptr_t y, uintptr_t mask, uintptr_t w, uintptr_t b, uintptr_t sm, uintptr_t si,
+           uintptr_t part, uintptr_t msg, uintptr_t dw, uintptr_t db, int64_t rows, int64_t C, int relu, int dtype,
+           uintptr_t stream) {
+          auto F = [](uintptr_t p) { return reinterpret_cast<const float*>(p); };
+          auto W = [](uintptr_t p) { return reinterpret_cast<float*>(p); };
+          bn_sync_bwd_reduce(reinterpret_cast<const void*>(dy), reinterpret_cast<const void*>(x),
+                             reinterpret_cast<const void*>(y), reinterpret_cast<const uint8_t*>(mask), F(w), F(b), F(sm),
+                             F(si), W(part), W(msg), W(dw), W(db), rows, C, relu, dtype, S(stream));
+        });
+  m.def("bn_sync_bwd_dx",
+        [](uintptr_t dy, uintptr_t x, uintptr_t y, uintptr_t mask, uintptr_t w, uintptr_t b, uintptr_t sm, uintptr_t si,
+           uintptr_t msg, uintptr_t count, uintptr_t coef, uintptr_t dx, uintptr_t dres, int64_t rows, int64_t C,
+           int relu, int dtype, uintptr_t stream) {
+          auto F = [](uintptr_t p) { return reinterpret_cast<const float*>(p); };
+          bn_sync_bwd_dx(reinterpret_cast<const void*>(dy), reinterpret_cast<const void*>(x),
+                         reinterpret_cast<const void*>(y), reinterpret_cast<const uint8_t*>(mask), F(w), F(b), F(sm),
+                         F(si), F(msg), F(count), reinterpret_cast<float*>(coef), reinterpret_cast<void*>(dx),
+                         reinterpret_cast<void*>(dres), rows, C, relu, dtype, S(stream));
+        });
+
   m.def("bn_apply_dual",
         [](uintptr_t x, uintptr_t x2, uintptr_t y, uintptr_t w, uintptr_t b, uintptr_t sm, uintptr_t si, uintptr_t w2,
            uintptr_t b2, uintptr_t sm2, uintptr_t si2, int64_t rows, int64_t C, uintptr_t mask, int dtype,

@@ -70,13 +70,14 @@ struct Geo {
   int blocks;
 };
 
-Geo geometry(int64_t rows, int64_t C, int64_t max_blocks = 2048) {
+Geo geometry(int64_t rows, int64_t C, int64_t max_blocks = 2048, int64_t floor_rows = 1) {
   Geo g;
   g.cv = static_cast<int>(C / 8);
   g.rpi = kThreads / g.cv;
   if (g.rpi < 1) g.rpi = 1;
   // >= 32K elements per workgroup, at most one full round of resident workgroups
   int64_t min_rows = (32768 + C - 1) / C;
+  if (min_rows < floor_rows) min_rows = floor_rows;
   int64_t blocks = (rows + min_rows - 1) / min_rows;
   if (blocks > max_blocks) blocks = max_blocks;
   if (blocks < 1) blocks = 1;
@@ -122,6 +123,195 @@ __device__ __forceinline__ void block_reduce_atomic(float (&a)[8], float (&b)[8]
     atomicAdd(shard + c, x);
     atomicAdd(shard + C + c, y);
   }
+}
+
+// The deterministic tail (synchronised BatchNorm, and a run-to-run repeatable BatchNorm at world
+// size 1): the same LDS meeting of the lanes, but every workgroup STORES its [2][C] partial at
+// part[blockIdx.x] instead of adding it to a shard. No float atomics, so the bits do not depend on
+// arrival order; every workgroup writes its whole partial, so the buffer needs no zero fill and
+// nothing re-zeroes it. bn_sync_fold_*_kernel sums the partials in a fixed order.
+__device__ __forceinline__ void block_reduce_store(float (&a)[8], float (&b)[8], int cv, int rpi, int C,
+                                                   float* __restrict__ part, float* smem) {
+  const int t = threadIdx.x;
+  const int r0 = t / cv, c8 = t % cv;
+  const bool active = r0 < rpi;
+  float* sa = smem;
+  float* sb = smem + rpi * C;
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      sa[r0 * C + c8 * 8 + j] = a[j];
+      sb[r0 * C + c8 * 8 + j] = b[j];
+    }
+  }
+  __syncthreads();
+  float* mine = part + static_cast<size_t>(blockIdx.x) * 2 * C;
+  for (int c = t; c < C; c += kThreads) {
+    float x = 0.f, y = 0.f;
+    for (int r = 0; r < rpi; ++r) {
+      x += sa[r * C + c];
+      y += sb[r * C + c];
+    }
+    mine[c] = x;
+    mine[C + c] = y;
+  }
+}
+
+template <bool DET>
+__device__ __forceinline__ void block_reduce(float (&a)[8], float (&b)[8], int cv, int rpi, int C,
+                                             float* __restrict__ acc, float* smem) {
+  if (DET) block_reduce_store(a, b, cv, rpi, C, acc, smem);
+  else block_reduce_atomic(a, b, cv, rpi, C, acc, smem);
+}
+
+// Geometry of the deterministic reductions: a function of (rows, C) alone (no occupancy query), so
+// the order of every sum is the same on every device. At least 32 rows per workgroup keep the
+// partial a workgroup writes (8 C bytes) under 1/8 of the 16-bit rows it reads; at most 512
+// partials bound the fold (measured on ResNet-50's nine shapes at batch 256 against the atomic path:
+// a cap of 256 costs 0.87-1.14x, 512 0.88-1.08x, 1024 0.88-1.18x; profiles/syncbn_resnet50_caps.jsonl).
+constexpr int kDetMaxBlocks = 512, kDetFloorRows = 32;
+
+// FLUXMPI_BN_DET_BLOCKS (1 .. 1024, read once) sets another cap for measurements (scripts/bench_syncbn.py);
+// the tests' closed forms assume the default.
+int det_max_blocks() {
+  static const int cap = [] {
+    const char* e = std::getenv("FLUXMPI_BN_DET_BLOCKS");
+    const int v = e ? std::atoi(e) : 0;
+    return (v >= 1 && v <= 1024) ? v : kDetMaxBlocks;
+  }();
+  return cap;
+}
+
+Geo det_geometry(int64_t rows, int64_t C) { return geometry(rows, C, det_max_blocks(), kDetFloorRows); }
+
+// Sum the `blocks` partials of a channel in an order that depends only on (blocks, C): a fold
+// workgroup is 64 channels x 16 groups, group g adds partials g, g + 16, ... in sequence (the loads
+// do not depend on the sums, so they stay in flight together: see the finalize note below on one
+// lane walking everything), the 16 group sums meet in LDS and are added 0, 1, ... 15.
+constexpr int kFoldCh = 64, kFoldGroups = 16;
+
+__device__ __forceinline__ bool fold_partials(const float* __restrict__ part, int blocks, int C, float& a, float& b,
+                                              int& c_out) {
+  __shared__ float red[2][kFoldGroups][kFoldCh];
+  const int cl = threadIdx.x % kFoldCh, g = threadIdx.x / kFoldCh;
+  const int c = blockIdx.x * kFoldCh + cl;
+  float sa = 0.f, sb = 0.f;
+  if (c < C) {
+#pragma unroll 4
+    for (int k = g; k < blocks; k += kFoldGroups) {
+      const float* p = part + static_cast<size_t>(k) * 2 * C;
+      sa += p[c];
+      sb += p[C + c];
+    }
+  }
+  red[0][g][cl] = sa;
+  red[1][g][cl] = sb;
+  __syncthreads();
+  c_out = c;
+  if (g != 0 || c >= C) return false;
+  a = red[0][0][cl];
+  b = red[1][0][cl];
+#pragma unroll
+  for (int k = 1; k < kFoldGroups; ++k) {
+    a += red[0][k][cl];
+    b += red[1][k][cl];
+  }
+  return true;
+}
+
+int fold_blocks(int64_t C) { return static_cast<int>((C + kFoldCh - 1) / kFoldCh); }
+
+// The local row count travels as two fp32 slots, n = 4096 n_hi + n_lo with n_lo < 4096: one slot
+// is exact only below 2^24 rows (ResNet-50's first BatchNorm at batch 256 over 8 ranks has 25.7 M),
+// while a SUM over W ranks keeps n_lo < 4096 W and n_hi < rows / 4096 exact.
+constexpr int64_t kCountRadix = 4096;
+
+__device__ __forceinline__ int64_t message_count(const float* __restrict__ cnt) {
+  return static_cast<int64_t>(cnt[0]) * kCountRadix + static_cast<int64_t>(cnt[1]);
+}
+
+// mean / invstd / running statistics of one channel from (sum, sum of squares, count): the fp32
+// arithmetic of bn_finalize_fwd_kernel, with the count of the whole (global) batch
+__device__ __forceinline__ void sync_finalize_channel(float s, float q, int64_t n, int c, float momentum, float eps,
+                                                      float* __restrict__ smean, float* __restrict__ sinv,
+                                                      float* __restrict__ rmean, float* __restrict__ rvar) {
+  const bool any = n >= 1;  // every shard empty: sums are 0, mean 0, running statistics kept
+  if (!any) n = 1;
+  const float inv_n = 1.f / static_cast<float>(n);
+  const float mean = s * inv_n;
+  float var = q * inv_n - mean * mean;
+  var = var > 0.f ? var : 0.f;
+  smean[c] = mean;
+  sinv[c] = rsqrtf(var + eps);
+  if (rmean != nullptr && any) {
+    const float unbiased = n > 1 ? var * static_cast<float>(n) / static_cast<float>(n - 1) : var;
+    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+    rvar[c] = (1.f - momentum) * rvar[c] + momentum * unbiased;
+  }
+}
+
+// Forward fold: msg[0:C] = sum x, msg[C:2C] = sum x^2, msg[2C:2C+2] = (n_hi, n_lo) of this shard.
+// smean != nullptr (world size 1): the finalize in the same launch, from the local sums and count.
+__global__ __launch_bounds__(kFoldCh * kFoldGroups) void bn_sync_fold_fwd_kernel(
+    const float* __restrict__ part, int blocks, int C, int64_t rows, float* __restrict__ msg, float momentum, float eps,
+    float* __restrict__ smean, float* __restrict__ sinv, float* __restrict__ rmean, float* __restrict__ rvar,
+    int64_t* __restrict__ nbt) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    msg[2 * C] = static_cast<float>(rows / kCountRadix);
+    msg[2 * C + 1] = static_cast<float>(rows % kCountRadix);
+    if (nbt != nullptr) *nbt += 1;  // num_batches_tracked, no launch of its own
+  }
+  float s, q;
+  int c;
+  if (!fold_partials(part, blocks, C, s, q, c)) return;
+  msg[c] = s;
+  msg[C + c] = q;
+  if (smean != nullptr) sync_finalize_channel(s, q, rows, c, momentum, eps, smean, sinv, rmean, rvar);
+}
+
+// Finalize from a (summed) message; the count is read here, on the device.
+__global__ __launch_bounds__(kThreads) void bn_sync_finalize_fwd_kernel(const float* __restrict__ msg, int C,
+                                                                        float momentum, float eps,
+                                                                        float* __restrict__ smean,
+                                                                        float* __restrict__ sinv,
+                                                                        float* __restrict__ rmean,
+                                                                        float* __restrict__ rvar,
+                                                                        int64_t* __restrict__ nbt) {
+  if (nbt != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= C) return;
+  sync_finalize_channel(msg[c], msg[C + c], message_count(msg + 2 * C), c, momentum, eps, smean, sinv, rmean, rvar);
+}
+
+// Backward fold: msg[0:C] = sum g, msg[C:2C] = sum g xhat of this shard, also written as the local
+// db / dw (the parameter gradients stay local sums: the data-parallel engine's SUM completes them).
+__global__ __launch_bounds__(kFoldCh * kFoldGroups) void bn_sync_fold_bwd_kernel(const float* __restrict__ part,
+                                                                                  int blocks, int C,
+                                                                                  float* __restrict__ msg,
+                                                                                  float* __restrict__ dw,
+                                                                                  float* __restrict__ db) {
+  float s, q;
+  int c;
+  if (!fold_partials(part, blocks, C, s, q, c)) return;
+  msg[c] = s;
+  msg[C + c] = q;
+  db[c] = s;
+  dw[c] = q;
+}
+
+// coef[0:C] = sum g / n, coef[C:2C] = sum g xhat / n from the summed backward message and the global
+// count: exactly the k2 / k3 a one-shard bn_bwd_dx_kernel forms from the same sums, so that kernel
+// is then launched unchanged with rows = 1 (its 1 / rows is 1.f and its products are exact).
+__global__ __launch_bounds__(kThreads) void bn_sync_scale_kernel(const float* __restrict__ msg,
+                                                                 const float* __restrict__ cnt, int C,
+                                                                 float* __restrict__ coef) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= C) return;
+  int64_t n = message_count(cnt);
+  if (n < 1) n = 1;
+  const float inv_n = 1.f / static_cast<float>(n);
+  coef[c] = msg[c] * inv_n;
+  coef[C + c] = msg[C + c] * inv_n;
 }
 
 // Sum the shards of a channel and re-zero them (the workspace is left zeroed for the next call,
@@ -219,7 +409,8 @@ __global__ __launch_bounds__(kFinCh * kFinGroups) void bn_finalize_bwd2_kernel(f
 }
 
 // ---------------------------------------------------------------- forward
-template <typename T>
+// DET: the workgroup stores its partial at acc[blockIdx.x] (block_reduce_store) instead of adding it to a shard
+template <typename T, bool DET = false>
 __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const T* __restrict__ x, int64_t rows, int C, Geo g,
                                                             float* __restrict__ acc) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -256,7 +447,7 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const T* __restrict_
       }
     }
   }
-  block_reduce_atomic(s, q, g.cv, g.rpi, C, acc, smem);
+  block_reduce<DET>(s, q, g.cv, g.rpi, C, acc, smem);
 }
 
 // y = act(x*scale + shift [+ res]); scale/shift derived from (mean, invstd) = batch
@@ -356,7 +547,8 @@ __global__ __launch_bounds__(kThreads) void bn_norm_kernel(const T* __restrict__
 // was added before the ReLU); 2 mask recomputed from x as fmaf(x, scale, shift) > 0
 // with scale/shift computed bit-identically to the forward prologue, so y is
 // neither saved nor re-read (one fewer activation read per element, both passes).
-template <typename T, int RM>
+// DET: as in bn_stats_kernel
+template <typename T, int RM, bool DET = false>
 __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                                  const T* __restrict__ y,
                                                                  const uint8_t* __restrict__ mask,
@@ -427,7 +619,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
       }
     }
   }
-  block_reduce_atomic(s, q, g.cv, g.rpi, C, acc, smem);
+  block_reduce<DET>(s, q, g.cv, g.rpi, C, acc, smem);
 }
 
 // dx = w*invstd * (dy_eff - sum_dy/R - xhat * sum_dy_xhat/R); dres = dy_eff
@@ -820,6 +1012,11 @@ void fwd_train_t(const void* x, void* y, const void* res, const float* w, const 
 }
 
 template <typename T>
+void dx_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
+          const float* sm, const float* si, const float* dw, const float* db, void* dx, void* dres, int64_t rows,
+          int64_t div_rows, int64_t C, int rm, hipStream_t s);
+
+template <typename T>
 void bwd_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
            const float* sm, const float* si, void* dx, void* dres, float* dw, float* db, float* ws, int64_t rows,
            int64_t C, int relu, int stats_ready, hipStream_t s) {
@@ -845,6 +1042,18 @@ void bwd_t(const void* dy, const void* x, const void* y, const uint8_t* mask, co
   FLUXMPI_HIP_CHECK(hipGetLastError());
   bn_finalize_bwd_kernel<<<finalize_blocks(C), kFinCh * kFinGroups, 0, s>>>(ws, (int)C, dw, db);
   FLUXMPI_HIP_CHECK(hipGetLastError());
+  dx_t<T>(dy, x, y, mask, w, b, sm, si, dw, db, dx, dres, rows, rows, C, rm, s);
+}
+
+// The dx pass from finished per-channel sums (dw, db), which the kernel divides by `div_rows`: the
+// row count of the batch the sums run over (bn_bwd), or 1 when they are already means (bn_sync_bwd_dx).
+template <typename T>
+void dx_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
+          const float* sm, const float* si, const float* dw, const float* db, void* dx, void* dres, int64_t rows,
+          int64_t div_rows, int64_t C, int rm, hipStream_t s) {
+  const T* dyr = static_cast<const T*>(dy);
+  const T* xr = static_cast<const T*>(x);
+  const T* yr = static_cast<const T*>(y);
   const int64_t nvec = rows * C / 8;
   T* dxr = static_cast<T*>(dx);
   T* drr = static_cast<T*>(dres);
@@ -854,7 +1063,7 @@ void bwd_t(const void* dy, const void* x, const void* y, const uint8_t* mask, co
     const size_t lds = FX ? 0 : C * sizeof(DxCoef);                                                            \
     auto k = bn_bwd_dx_kernel<T, RM, DRES, FX, 2>;   \
     k<<<elementwise_grid(reinterpret_cast<const void*>(k), lds, nvec), kThreads, lds, s>>>(                    \
-        dyr, xr, yr, mask, w, b, sm, si, dw, db, dxr, drr, rows, (int)C, nvec);                                \
+        dyr, xr, yr, mask, w, b, sm, si, dw, db, dxr, drr, div_rows, (int)C, nvec);                            \
   }
 #define LAUNCH_F(RM, DRES)             \
   {                                    \
@@ -903,6 +1112,50 @@ void bwd_dual_t(const void* dy, const uint8_t* mask, const void* x, const void* 
       dyr, mask, xr, x2r, w, sm, si, dw, db, w2, sm2, si2, dw2, db2, static_cast<T*>(dx), static_cast<T*>(dx2), rows,
       (int)C, nvec);
   FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- synchronised (deterministic) path
+template <typename T>
+void sync_stats_t(const void* x, float* part, float* msg, int64_t rows, int64_t C, float momentum, float eps,
+                  float* sm, float* si, float* rm, float* rv, int64_t* nbt, hipStream_t s) {
+  const Geo g = det_geometry(rows, C);
+  bn_stats_kernel<T, true><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(x), rows, (int)C, g,
+                                                                         part);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+  bn_sync_fold_fwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, s>>>(part, g.blocks, (int)C, rows, msg, momentum,
+                                                                           eps, sm, si, rm, rv, nbt);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
+int relu_mode(int relu, const void* y, const uint8_t* mask) {
+  return relu == 0 ? 0 : (mask != nullptr ? 3 : (y != nullptr ? 1 : 2));
+}
+
+template <typename T>
+void sync_bwd_reduce_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w,
+                       const float* b, const float* sm, const float* si, float* part, float* msg, float* dw,
+                       float* db, int64_t rows, int64_t C, int relu, hipStream_t s) {
+  const T* dyr = static_cast<const T*>(dy);
+  const T* xr = static_cast<const T*>(x);
+  const T* yr = static_cast<const T*>(y);
+  const Geo g = det_geometry(rows, C);
+#define RED(RM)                                                                                                     \
+  bn_bwd_reduce_kernel<T, RM, true><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(dyr, xr, yr, mask, w, b, sm, si, \
+                                                                                  rows, (int)C, g, part);
+  switch (relu_mode(relu, y, mask)) {
+    case 0: RED(0) break;
+    case 1: RED(1) break;
+    case 2: RED(2) break;
+    default: RED(3) break;
+  }
+#undef RED
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+  bn_sync_fold_bwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, s>>>(part, g.blocks, (int)C, msg, dw, db);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
+void check_rows(int64_t rows) {
+  if (rows < 1) throw std::runtime_error("sync batchnorm: an empty shard launches nothing (rows must be >= 1)");
 }
 
 void check_dual(int64_t C, const uint8_t* mask) {
@@ -1033,6 +1286,85 @@ void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_ma
     case kF32: bwd_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dx, dres, dweight, dbias, workspace, rows, C,
                             relu, stats_ready, stream); break;
     default: throw std::runtime_error("fused batchnorm: unsupported dtype");
+  }
+}
+
+size_t bn_sync_workspace_floats(int64_t rows, int64_t C) {
+  check(C);
+  return static_cast<size_t>(det_geometry(rows, C).blocks) * 2 * static_cast<size_t>(C);
+}
+
+void bn_sync_stats(const void* x, float* part, float* msg, int64_t rows, int64_t C, int dtype, hipStream_t stream,
+                   float* save_mean, float* save_invstd, float* running_mean, float* running_var, float momentum,
+                   float eps, int64_t* nbt) {
+  check(C);
+  check_rows(rows);
+  check_aligned({msg, save_mean, save_invstd});
+  switch (dtype) {
+    case kBF16: sync_stats_t<bf16>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
+                                   running_var, nbt, stream); break;
+    case kF16: sync_stats_t<f16>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
+                                 running_var, nbt, stream); break;
+    case kF32: sync_stats_t<float>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
+                                   running_var, nbt, stream); break;
+    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
+  }
+}
+
+void bn_sync_finalize_fwd(const float* msg, float* running_mean, float* running_var, float* save_mean,
+                          float* save_invstd, int64_t C, float momentum, float eps, hipStream_t stream,
+                          int64_t* nbt) {
+  check(C);
+  check_aligned({save_mean, save_invstd});
+  bn_sync_finalize_fwd_kernel<<<static_cast<int>((C + kThreads - 1) / kThreads), kThreads, 0, stream>>>(
+      msg, (int)C, momentum, eps, save_mean, save_invstd, running_mean, running_var, nbt);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
+void bn_sync_bwd_reduce(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
+                        const float* bias, const float* save_mean, const float* save_invstd, float* part, float* msg,
+                        float* dweight, float* dbias, int64_t rows, int64_t C, int relu, int dtype,
+                        hipStream_t stream) {
+  check(C);
+  check_rows(rows);
+  check_aligned({weight, bias, save_mean, save_invstd, msg});
+  switch (dtype) {
+    case kBF16: sync_bwd_reduce_t<bf16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
+                                        dbias, rows, C, relu, stream); break;
+    case kF16: sync_bwd_reduce_t<f16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
+                                      dbias, rows, C, relu, stream); break;
+    case kF32: sync_bwd_reduce_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
+                                        dbias, rows, C, relu, stream); break;
+    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
+  }
+}
+
+void bn_sync_bwd_dx(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
+                    const float* bias, const float* save_mean, const float* save_invstd, const float* msg,
+                    const float* count, float* coef, void* dx, void* dres, int64_t rows, int64_t C, int relu,
+                    int dtype, hipStream_t stream) {
+  check(C);
+  check_rows(rows);
+  check_aligned({weight, bias, save_mean, save_invstd, msg, coef});
+  const float* sums = msg;
+  int64_t div_rows = rows;
+  if (count != nullptr) {  // sums of the global batch: turn them into means with the global count
+    if (coef == nullptr) throw std::runtime_error("sync batchnorm: a global count needs the coef scratch");
+    bn_sync_scale_kernel<<<static_cast<int>((C + kThreads - 1) / kThreads), kThreads, 0, stream>>>(msg, count, (int)C,
+                                                                                                    coef);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    sums = coef;
+    div_rows = 1;
+  }
+  const int rm = relu_mode(relu, y, relu_mask);
+  switch (dtype) {
+    case kBF16: dx_t<bf16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
+                           div_rows, C, rm, stream); break;
+    case kF16: dx_t<f16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
+                         div_rows, C, rm, stream); break;
+    case kF32: dx_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
+                           div_rows, C, rm, stream); break;
+    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
   }
 }
 

@@ -16,7 +16,9 @@ MI355X choices:
   hipBLASLt matmuls on that NHWC view instead of MIOpen;
 * ``norm="fused"`` uses the hand-written gfx950 NHWC BatchNorm kernels with
   the ReLU (and the residual add of each block) fused into the normalisation
-  pass (``fluxmpi_amd.ops.batchnorm``); ``norm="torch"`` uses ``nn.BatchNorm2d``.
+  pass (``fluxmpi_amd.ops.batchnorm``); ``norm="sync"`` uses the same kernels with the batch
+  statistics summed over every rank (``fluxmpi_amd.ops.syncbn``); ``norm="torch"`` uses
+  ``nn.BatchNorm2d``.
 """
 from __future__ import annotations
 
@@ -91,6 +93,9 @@ def _norm(c, kind):
     if kind == "fused":
         from ..ops.batchnorm import FusedBatchNorm2d
         return FusedBatchNorm2d(c)
+    if kind == "sync":
+        from ..ops.syncbn import SyncBatchNorm2d
+        return SyncBatchNorm2d(c)
     return nn.BatchNorm2d(c)
 
 
@@ -116,7 +121,7 @@ class Bottleneck(nn.Module):
         self.conv3 = conv1x1(width, cout, 1, conv_impl)
         self.bn3 = _norm(cout, norm)
         self.downsample = downsample
-        self.fused = norm == "fused"
+        self.fused = norm in ("fused", "sync")  # both take bn(x, relu=..., residual=...)
 
     def _fused_downsample(self) -> bool:
         ds = self.downsample
@@ -219,6 +224,9 @@ class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, conv_impl="gemm", norm="torch", zero_init_residual=False):
         super().__init__()
         if conv_impl in ("fused", "hybrid"):
+            if norm == "sync":
+                raise ValueError(f"norm='sync' cannot be combined with conv_impl={conv_impl!r}: those blocks and the "
+                                 "stem compute BatchNorm statistics in GEMM epilogues, local to the rank")
             norm = "fused"
         self.conv_impl, self.norm_kind = conv_impl, norm
         self.inplanes = 64
@@ -290,6 +298,9 @@ class ResNet(nn.Module):
                 x = pool.bn_relu_maxpool(c, self.bn1, 3, 2, 1)
             else:
                 x = self.maxpool(self.bn1(c, relu=True))
+        elif self.norm_kind == "sync":
+            # the fused stem / pool kernels carry statistics of their own (local to the rank)
+            x = self.maxpool(self.bn1(self.conv1(x), relu=True))
         else:
             x = self.maxpool(F.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))

@@ -336,3 +336,11 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
                                 self.running_mean if self.track_running_stats else None,
                                 self.running_var if self.track_running_stats else None,
                                 use_batch, mom, self.eps, relu, residual, link, nbt, bnlink)
+
+
+def __getattr__(name):
+    # the synchronised variants live in ops/syncbn.py (which imports this module): exported here too
+    if name in ("SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm"):
+        from . import syncbn
+        return getattr(syncbn, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
