@@ -225,7 +225,7 @@ void layernorm_fwd(const void* x, const void* residual, void* h, void* y, const 
 // column sums of dx.
 int layernorm_bwd(const void* dy, const void* x, const void* dh_ext, const float* mean, const float* rstd,
                   const void* w, void* dx, float* partials, int max_blocks, int64_t rows, int64_t D, int dtype,
-                  int wdtype, bool colsum, hipStream_t stream);
+                  int wdtype, hipStream_t stream, bool colsum);
 
 // ---- MFMA bf16 GEMM with BatchNorm fusions (1x1 convolutions) --------------------
 // C[M,N] = A[M,K] * B[N,K]^T. a_kmajor: A stored [M][lda] (K contiguous), else [K][lda]

@@ -355,31 +355,16 @@ int anderson_gram_chunks(int64_t bsz, int64_t d) {
   return static_cast<int>(chunks);
 }
 
-template <int N, bool ONE, typename HT>
-void gram_launch(const HT* X, const void* F, int fdt, HT* G, float* part, dim3 grid, int64_t d4, int64_t rs,
-                 int64_t bs, int64_t chunk4, int last, int fr, hipStream_t s) {
-  if (fdt == kBF16)
-    gram_kernel<N, ONE, bf16, HT><<<grid, kThreads, 0, s>>>(X, static_cast<const bf16*>(F), G, part, d4, rs, bs, chunk4,
-                                                            last, fr);
-  else
-    gram_kernel<N, ONE, float, HT><<<grid, kThreads, 0, s>>>(X, static_cast<const float*>(F), G, part, d4, rs, bs,
-                                                             chunk4, last, fr);
+// X / G and F are fp32 or bf16 (checked by the callers): f(TypeTag<T>)
+template <typename F>
+void dispatch_f32_bf16(int dtype, F&& f) {
+  dispatch_bool(dtype == kBF16, [&](auto bf) { f(TypeTag<std::conditional_t<decltype(bf)::value, bf16, float>>{}); });
 }
 
-template <typename HT>
-void gram_dispatch(const HT* X, const void* F, int f_dtype, HT* G, bool one, float* partials, dim3 grid, int64_t d4,
-                   int64_t row_stride, int64_t batch_stride, int64_t chunk4, int n, int last, hipStream_t stream) {
-#define GRAM_CASE(NN)                                                                                              \
-  case NN:                                                                                                         \
-    if (one) gram_launch<NN, true>(X, F, f_dtype, G, partials, grid, d4, row_stride, batch_stride, chunk4, last,  \
-                                   last, stream);                                                                  \
-    else gram_launch<NN, false>(X, F, f_dtype, G, partials, grid, d4, row_stride, batch_stride, chunk4, last, 0,  \
-                                stream);                                                                           \
-    break;
-  switch (n) {
-    GRAM_CASE(1) GRAM_CASE(2) GRAM_CASE(3) GRAM_CASE(4) GRAM_CASE(5) GRAM_CASE(6) GRAM_CASE(7) GRAM_CASE(8)
-  }
-#undef GRAM_CASE
+// the kernels are compiled for every history length n = 1 .. kMaxRows (checked by the callers)
+template <typename F>
+void dispatch_rows(int n, F&& f) {
+  dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(n, "anderson: need 1 <= n <= 8", f);
 }
 
 void anderson_gram(const void* X, const void* F, int f_dtype, void* G, unsigned fresh, float* partials, int64_t bsz,
@@ -397,47 +382,21 @@ void anderson_gram(const void* X, const void* F, int f_dtype, void* G, unsigned 
   dim3 grid(chunks, static_cast<unsigned>(bsz));
   // one new row (the steady state): the others come from G; otherwise every row from F - X
   const bool one = G != nullptr && fresh == (1u << last);
-  if (h_dtype == kBF16)
-    gram_dispatch(static_cast<const bf16*>(X), F, f_dtype, static_cast<bf16*>(G), one, partials, grid, d4, row_stride,
-                  batch_stride, chunk4, n, last, stream);
-  else
-    gram_dispatch(static_cast<const float*>(X), F, f_dtype, static_cast<float*>(G), one, partials, grid, d4,
-                  row_stride, batch_stride, chunk4, n, last, stream);
+  dispatch_f32_bf16(h_dtype, [&](auto ht) {
+    dispatch_f32_bf16(f_dtype, [&](auto ft) {
+      dispatch_rows(n, [&](auto n_c) {
+        dispatch_bool(one, [&](auto one_c) {
+          using HT = typename decltype(ht)::type;
+          using FT = typename decltype(ft)::type;
+          constexpr bool ONE = decltype(one_c)::value;
+          gram_kernel<decltype(n_c)::value, ONE, FT, HT><<<grid, kThreads, 0, stream>>>(
+              static_cast<const HT*>(X), static_cast<const FT*>(F), static_cast<HT*>(G), partials, d4, row_stride,
+              batch_stride, chunk4, last, ONE ? last : 0);
+        });
+      });
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
-}
-
-template <int N, bool MIXX, typename FT, typename HT>
-void mix_launch(HT* X, const FT* F, const float* alpha, void* z, int zdt, int64_t bsz, int64_t d4, int64_t rs,
-                int64_t bs, int slot, float beta, hipStream_t s) {
-  dim3 grid(static_cast<unsigned>((d4 + kThreads - 1) / kThreads), static_cast<unsigned>(bsz));
-  switch (zdt) {
-    case kBF16: mix_kernel<N, MIXX, bf16, FT, HT><<<grid, kThreads, 0, s>>>(X, F, alpha, static_cast<bf16*>(z), d4, rs, bs, slot, beta); break;
-    case kF16: mix_kernel<N, MIXX, f16, FT, HT><<<grid, kThreads, 0, s>>>(X, F, alpha, static_cast<f16*>(z), d4, rs, bs, slot, beta); break;
-    case kF32: mix_kernel<N, MIXX, float, FT, HT><<<grid, kThreads, 0, s>>>(X, F, alpha, static_cast<float*>(z), d4, rs, bs, slot, beta); break;
-    default: throw std::runtime_error("anderson_mix: unsupported z dtype");
-  }
-}
-
-template <typename HT>
-void mix_dispatch(HT* X, const void* F, int f_dtype, const float* alpha, void* z, int zdt, int64_t bsz, int64_t d4,
-                  int64_t row_stride, int64_t batch_stride, int n, int slot, float beta, hipStream_t stream) {
-  const bool mixx = beta != 1.f;
-  const bf16* fh = static_cast<const bf16*>(F);
-  const float* ff = static_cast<const float*>(F);
-#define MIX_CASE(NN)                                                                                              \
-  case NN:                                                                                                        \
-    if (f_dtype == kBF16) {                                                                                       \
-      if (mixx) mix_launch<NN, true>(X, fh, alpha, z, zdt, bsz, d4, row_stride, batch_stride, slot, beta, stream); \
-      else mix_launch<NN, false>(X, fh, alpha, z, zdt, bsz, d4, row_stride, batch_stride, slot, beta, stream);    \
-    } else {                                                                                                      \
-      if (mixx) mix_launch<NN, true>(X, ff, alpha, z, zdt, bsz, d4, row_stride, batch_stride, slot, beta, stream); \
-      else mix_launch<NN, false>(X, ff, alpha, z, zdt, bsz, d4, row_stride, batch_stride, slot, beta, stream);    \
-    }                                                                                                             \
-    break;
-  switch (n) {
-    MIX_CASE(1) MIX_CASE(2) MIX_CASE(3) MIX_CASE(4) MIX_CASE(5) MIX_CASE(6) MIX_CASE(7) MIX_CASE(8)
-  }
-#undef MIX_CASE
 }
 
 void anderson_mix(void* X, const void* F, int f_dtype, const float* alpha, void* z, int z_dtype, int64_t bsz,
@@ -452,12 +411,23 @@ void anderson_mix(void* X, const void* F, int f_dtype, const float* alpha, void*
     throw std::runtime_error("anderson_mix: z must be 8-byte aligned");
   const int64_t d4 = d / 4;
   const int zdt = z != nullptr ? z_dtype : kF32;
-  if (h_dtype == kBF16)
-    mix_dispatch(static_cast<bf16*>(X), F, f_dtype, alpha, z, zdt, bsz, d4, row_stride, batch_stride, n, slot, beta,
-                 stream);
-  else
-    mix_dispatch(static_cast<float*>(X), F, f_dtype, alpha, z, zdt, bsz, d4, row_stride, batch_stride, n, slot, beta,
-                 stream);
+  const dim3 grid(static_cast<unsigned>((d4 + kThreads - 1) / kThreads), static_cast<unsigned>(bsz));
+  dispatch_f32_bf16(h_dtype, [&](auto ht) {
+    dispatch_f32_bf16(f_dtype, [&](auto ft) {
+      dispatch_float(zdt, "anderson_mix: unsupported z dtype", [&](auto zt) {
+        dispatch_rows(n, [&](auto n_c) {
+          dispatch_bool(beta != 1.f, [&](auto mixx_c) {
+            using HT = typename decltype(ht)::type;
+            using FT = typename decltype(ft)::type;
+            using ZT = typename decltype(zt)::type;
+            mix_kernel<decltype(n_c)::value, decltype(mixx_c)::value, ZT, FT, HT><<<grid, kThreads, 0, stream>>>(
+                static_cast<HT*>(X), static_cast<const FT*>(F), alpha, static_cast<ZT*>(z), d4, row_stride,
+                batch_stride, slot, beta);
+          });
+        });
+      });
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -467,12 +437,10 @@ void anderson_solve(const float* partials, int chunks, int64_t bsz, int n, int l
   if (bsz < 1 || bsz > 1024) throw std::runtime_error("anderson_solve: need 1 <= bsz <= 1024 (one workgroup)");
   if (chunks < 1 || last < 0 || last >= n) throw std::runtime_error("anderson_solve: bad chunks / last row");
   const unsigned threads = static_cast<unsigned>((bsz + 63) / 64 * 64);
-#define SOLVE_CASE(NN) \
-  case NN: solve_kernel<NN><<<1, threads, 0, stream>>>(partials, chunks, static_cast<int>(bsz), last, lam, alpha, res); break;
-  switch (n) {
-    SOLVE_CASE(1) SOLVE_CASE(2) SOLVE_CASE(3) SOLVE_CASE(4) SOLVE_CASE(5) SOLVE_CASE(6) SOLVE_CASE(7) SOLVE_CASE(8)
-  }
-#undef SOLVE_CASE
+  dispatch_rows(n, [&](auto n_c) {
+    solve_kernel<decltype(n_c)::value><<<1, threads, 0, stream>>>(partials, chunks, static_cast<int>(bsz), last, lam,
+                                                                  alpha, res);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -489,25 +457,12 @@ void adjoint_step(const void* vjp, const void* grad, const void* u, void* u_new,
   if (((reinterpret_cast<uintptr_t>(vjp) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(u) |
         reinterpret_cast<uintptr_t>(u_new)) & 15u) != 0)
     throw std::runtime_error("adjoint_step: tensors must be 16-byte aligned");
-  switch (dtype) {
-    case kBF16:
-      adjoint_step_kernel<bf16><<<blocks, kThreads, 0, stream>>>(static_cast<const bf16*>(vjp), static_cast<const bf16*>(grad),
-                                                                  static_cast<const bf16*>(u), static_cast<bf16*>(u_new),
-                                                                  partials, n / 8);
-      break;
-    case kF16:
-      adjoint_step_kernel<f16><<<blocks, kThreads, 0, stream>>>(static_cast<const f16*>(vjp), static_cast<const f16*>(grad),
-                                                                 static_cast<const f16*>(u), static_cast<f16*>(u_new),
-                                                                 partials, n / 8);
-      break;
-    case kF32:
-      adjoint_step_kernel<float><<<blocks, kThreads, 0, stream>>>(static_cast<const float*>(vjp), static_cast<const float*>(grad),
-                                                                   static_cast<const float*>(u), static_cast<float*>(u_new),
-                                                                   partials, n / 8);
-      break;
-    default:
-      throw std::runtime_error("adjoint_step: bf16 / fp16 / fp32 only");
-  }
+  dispatch_float(dtype, "adjoint_step: bf16 / fp16 / fp32 only", [&](auto t) {
+    using T = typename decltype(t)::type;
+    adjoint_step_kernel<T><<<blocks, kThreads, 0, stream>>>(static_cast<const T*>(vjp), static_cast<const T*>(grad),
+                                                            static_cast<const T*>(u), static_cast<T*>(u_new), partials,
+                                                            n / 8);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 

@@ -63,8 +63,26 @@ __device__ __forceinline__ void ld8ch(const float* __restrict__ p, int c0, float
   v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
+// The forward affine y = fmaf(x, sc, sh) of a lane's 8 channels from vector loads. The backward
+// recomputes fmaf(x, sc, sh) > 0 to rebuild the ReLU mask, so this arithmetic is bit-identical to the
+// prologue of bn_norm_kernel (which keeps its own copy: it also turns a running variance into invstd).
+__device__ __forceinline__ void coef8(const float* __restrict__ w, const float* __restrict__ b,
+                                      const float* __restrict__ mean, const float* __restrict__ inv, int c0,
+                                      float (&sc)[8], float (&sh)[8]) {
+  float mu[8], iv[8], ww[8], bb[8];
+  ld8ch(mean, c0, mu);
+  ld8ch(inv, c0, iv);
+  ld8ch(w ? w : mean, c0, ww);  // unconditional: see bn_norm_kernel
+  ld8ch(b ? b : mean, c0, bb);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sc[j] = (w ? ww[j] : 1.f) * iv[j];
+    sh[j] = fmaf(-mu[j], sc[j], b ? bb[j] : 0.f);
+  }
+}
+
 struct Geo {
-  int cv;    // channel vectors per row (C / 8)
+  int cv;   // channel vectors per row (C / 8)
   int rpi;   // rows handled concurrently by a workgroup (kThreads / cv)
   int64_t rows_per_block;
   int blocks;
@@ -98,70 +116,42 @@ constexpr int kShards = 64;  // <= ~200 same-address atomics even for 12k-block 
 // shards keep <= 128 same-address atomics and make the finalize kernel's read 4x smaller.
 constexpr int kRedShards = 16;
 
-__device__ __forceinline__ void block_reduce_atomic(float (&a)[8], float (&b)[8], int cv, int rpi, int C,
-                                                    float* __restrict__ acc, float* smem) {
-  const int t = threadIdx.x;
-  const int r0 = t / cv, c8 = t % cv;
-  const bool active = r0 < rpi;
-  float* sa = smem;
-  float* sb = smem + rpi * C;
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sa[r0 * C + c8 * 8 + j] = a[j];
-      sb[r0 * C + c8 * 8 + j] = b[j];
-    }
-  }
-  __syncthreads();
-  float* shard = acc + static_cast<size_t>(blockIdx.x % kRedShards) * 2 * C;
-  for (int c = t; c < C; c += kThreads) {
-    float x = 0.f, y = 0.f;
-    for (int r = 0; r < rpi; ++r) {
-      x += sa[r * C + c];
-      y += sb[r * C + c];
-    }
-    atomicAdd(shard + c, x);
-    atomicAdd(shard + C + c, y);
-  }
-}
-
-// The deterministic tail (synchronised BatchNorm, and a run-to-run repeatable BatchNorm at world
+// DET, the deterministic tail (synchronised BatchNorm, and a run-to-run repeatable BatchNorm at world
 // size 1): the same LDS meeting of the lanes, but every workgroup STORES its [2][C] partial at
-// part[blockIdx.x] instead of adding it to a shard. No float atomics, so the bits do not depend on
+// acc[blockIdx.x] instead of adding it to a shard. No float atomics, so the bits do not depend on
 // arrival order; every workgroup writes its whole partial, so the buffer needs no zero fill and
 // nothing re-zeroes it. bn_sync_fold_*_kernel sums the partials in a fixed order.
-__device__ __forceinline__ void block_reduce_store(float (&a)[8], float (&b)[8], int cv, int rpi, int C,
-                                                   float* __restrict__ part, float* smem) {
-  const int t = threadIdx.x;
-  const int r0 = t / cv, c8 = t % cv;
-  const bool active = r0 < rpi;
-  float* sa = smem;
-  float* sb = smem + rpi * C;
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sa[r0 * C + c8 * 8 + j] = a[j];
-      sb[r0 * C + c8 * 8 + j] = b[j];
-    }
-  }
-  __syncthreads();
-  float* mine = part + static_cast<size_t>(blockIdx.x) * 2 * C;
-  for (int c = t; c < C; c += kThreads) {
-    float x = 0.f, y = 0.f;
-    for (int r = 0; r < rpi; ++r) {
-      x += sa[r * C + c];
-      y += sb[r * C + c];
-    }
-    mine[c] = x;
-    mine[C + c] = y;
-  }
-}
-
 template <bool DET>
 __device__ __forceinline__ void block_reduce(float (&a)[8], float (&b)[8], int cv, int rpi, int C,
                                              float* __restrict__ acc, float* smem) {
-  if (DET) block_reduce_store(a, b, cv, rpi, C, acc, smem);
-  else block_reduce_atomic(a, b, cv, rpi, C, acc, smem);
+  const int t = threadIdx.x;
+  const int r0 = t / cv, c8 = t % cv;
+  const bool active = r0 < rpi;
+  float* sa = smem;
+  float* sb = smem + rpi * C;
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      sa[r0 * C + c8 * 8 + j] = a[j];
+      sb[r0 * C + c8 * 8 + j] = b[j];
+    }
+  }
+  __syncthreads();
+  float* mine = acc + static_cast<size_t>(DET ? blockIdx.x : blockIdx.x % kRedShards) * 2 * C;
+  for (int c = t; c < C; c += kThreads) {
+    float x = 0.f, y = 0.f;
+    for (int r = 0; r < rpi; ++r) {
+      x += sa[r * C + c];
+      y += sb[r * C + c];
+    }
+    if (DET) {
+      mine[c] = x;
+      mine[C + c] = y;
+    } else {
+      atomicAdd(mine + c, x);
+      atomicAdd(mine + C + c, y);
+    }
+  }
 }
 
 // Geometry of the deterministic reductions: a function of (rows, C) alone (no occupancy query), so
@@ -409,7 +399,7 @@ __global__ __launch_bounds__(kFinCh * kFinGroups) void bn_finalize_bwd2_kernel(f
 }
 
 // ---------------------------------------------------------------- forward
-// DET: the workgroup stores its partial at acc[blockIdx.x] (block_reduce_store) instead of adding it to a shard
+// DET: the workgroup stores its partial at acc[blockIdx.x] (block_reduce<true>) instead of adding it to a shard
 template <typename T, bool DET = false>
 __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const T* __restrict__ x, int64_t rows, int C, Geo g,
                                                             float* __restrict__ acc) {
@@ -500,7 +490,7 @@ __global__ __launch_bounds__(kThreads) void bn_norm_kernel(const T* __restrict__
     ld8ch(w ? w : mean_in, c0, ww);
     ld8ch(b ? b : mean_in, c0, bb);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < 8; ++j) {  // == coef8, with the running variance turned into invstd
       const float invstd = train ? s2[j] : rsqrtf(s2[j] + eps);  // save_invstd | running_var
       rsc[j] = (w ? ww[j] : 1.f) * invstd;
       rsh[j] = fmaf(-mu[j], rsc[j], b ? bb[j] : 0.f);
@@ -562,16 +552,10 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
   const int r0 = t / g.cv, c8 = t % g.cv;
   float s[8] = {0}, q[8] = {0};
   if (r0 < g.rpi) {
-    float mu[8], is[8], sc[8], sh[8], ww[8], bb[8];
+    float mu[8], is[8], sc[8], sh[8];
     ld8ch(smean, c8 * 8, mu);
     ld8ch(sinv, c8 * 8, is);
-    ld8ch(w ? w : smean, c8 * 8, ww);  // unconditional: see bn_norm_kernel
-    ld8ch(b ? b : smean, c8 * 8, bb);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sc[j] = (w ? ww[j] : 1.f) * is[j];
-      sh[j] = fmaf(-mu[j], sc[j], b ? bb[j] : 0.f);
-    }
+    coef8(w, b, smean, sinv, c8 * 8, sc, sh);
     const int64_t start = static_cast<int64_t>(blockIdx.x) * g.rows_per_block;
     int64_t end = start + g.rows_per_block;
     if (end > rows) end = rows;
@@ -738,21 +722,6 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict
 // one pass from (dy, relu mask, x, x2) (dy_eff is the same for both BatchNorms) instead of
 // bn3 writing dres and the branch BN reading it twice. FIXED channel mapping only
 // (C/8 divides the workgroup), per-lane coefficients of both BatchNorms in registers.
-__device__ __forceinline__ void coef8(const float* __restrict__ w, const float* __restrict__ b,
-                                      const float* __restrict__ mean, const float* __restrict__ inv, int c0,
-                                      float (&sc)[8], float (&sh)[8]) {
-  float mu[8], iv[8], ww[8], bb[8];
-  ld8ch(mean, c0, mu);
-  ld8ch(inv, c0, iv);
-  ld8ch(w ? w : mean, c0, ww);  // unconditional: see bn_norm_kernel
-  ld8ch(b ? b : mean, c0, bb);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    sc[j] = (w ? ww[j] : 1.f) * iv[j];
-    sh[j] = fmaf(-mu[j], sc[j], b ? bb[j] : 0.f);
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(kThreads) void bn_norm_dual_kernel(
     const T* __restrict__ x, const T* __restrict__ x2, T* __restrict__ y, const float* __restrict__ w,
@@ -855,9 +824,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_dual_kernel(
       }
     }
   }
-  block_reduce_atomic(s, q, g.cv, g.rpi, C, acc, smem);
+  block_reduce<false>(s, q, g.cv, g.rpi, C, acc, smem);
   __syncthreads();  // the LDS staging is reused
-  block_reduce_atomic(s, q2, g.cv, g.rpi, C, acc2, smem);
+  block_reduce<false>(s, q2, g.cv, g.rpi, C, acc2, smem);
 }
 
 // dx = A*dy_eff + B*x + D, dx2 = A2*dy_eff + B2*x2 + D2 (coefficients as in bn_bwd_dx_kernel)
@@ -966,83 +935,52 @@ Geo reduce_geometry(const void* kernel, int64_t rows, int64_t C) {
   return geometry(rows, C, resident_blocks(kernel, kThreads, reduce_smem(g0, C)));
 }
 
+constexpr char kBadDtype[] = "fused batchnorm: unsupported dtype";
+constexpr char kBadSyncDtype[] = "sync batchnorm: unsupported dtype";
+constexpr char kBadDualDtype[] = "dual batchnorm: unsupported dtype";
+
+// relu: 0 none; 1 mask from y; 2 mask recomputed from x (no residual); 3 mask from saved bits
+int relu_mode(int relu, const void* y, const uint8_t* mask) {
+  return relu == 0 ? 0 : (mask != nullptr ? 3 : (y != nullptr ? 1 : 2));
+}
+
+template <typename F> void dispatch_relu_mode(int rm, F&& f) {
+  dispatch_int<0, 1, 2, 3>(rm, "fused batchnorm: bad ReLU mode", f);
+}
+
+template <typename T>
+void stats_t(const void* x, float* ws, int64_t rows, int64_t C, hipStream_t s) {
+  const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_stats_kernel<T>), rows, C);
+  bn_stats_kernel<T><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(x), rows, (int)C, g, ws);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
+void finalize_fwd(float* ws, int64_t rows, int64_t C, float momentum, float eps, float* sm, float* si, float* rm,
+                  float* rv, const float* w, const float* b, float* scale, float* shift, int64_t* nbt,
+                  hipStream_t s) {
+  bn_finalize_fwd_kernel<<<finalize_blocks(C), kFinCh * kFinGroups, 0, s>>>(ws, (int)C, rows, momentum, eps, sm, si, rm,
+                                                                            rv, w, b, scale, shift, nbt);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
 
 template <typename T>
 void norm_t(const void* x, void* y, const void* res, const float* w, const float* b, const float* mean,
             const float* stat2, int64_t rows, int64_t C, float eps, int train, int relu, uint8_t* mask,
             hipStream_t s) {
   const int64_t nvec = rows * C / 8;
-  const T* xr = static_cast<const T*>(x);
-  T* yr = static_cast<T*>(y);
-  const T* rr = static_cast<const T*>(res);
-  const bool fixed = fixed_channels(C);
-#define LAUNCH(RELU, RES, FX)                                                                                   \
-  {                                                                                                            \
-    const size_t sm = FX ? 0 : 2 * C * sizeof(float);                                                          \
-    auto k = bn_norm_kernel<T, RELU, RES, FX, 2>;   \
-    k<<<elementwise_grid(reinterpret_cast<const void*>(k), sm, nvec), kThreads, sm, s>>>(                      \
-        xr, yr, rr, w, b, mean, stat2, (int)C, eps, train, nvec, mask);                                        \
-  }
-#define LAUNCH_F(RELU, RES)                \
-  {                                        \
-    if (fixed) LAUNCH(RELU, RES, true)     \
-    else LAUNCH(RELU, RES, false)          \
-  }
-  const bool has_res = res != nullptr;
-  if (relu && has_res) LAUNCH_F(true, true)
-  else if (relu) LAUNCH_F(true, false)
-  else if (has_res) LAUNCH_F(false, true)
-  else LAUNCH_F(false, false)
-#undef LAUNCH_F
-#undef LAUNCH
+  dispatch_bool(relu != 0, [&](auto relu_c) {
+    dispatch_bool(res != nullptr, [&](auto res_c) {
+      dispatch_bool(fixed_channels(C), [&](auto fixed_c) {
+        constexpr bool FX = decltype(fixed_c)::value;
+        const size_t sm = FX ? 0 : 2 * C * sizeof(float);
+        auto k = bn_norm_kernel<T, decltype(relu_c)::value, decltype(res_c)::value, FX, 2>;
+        k<<<elementwise_grid(reinterpret_cast<const void*>(k), sm, nvec), kThreads, sm, s>>>(
+            static_cast<const T*>(x), static_cast<T*>(y), static_cast<const T*>(res), w, b, mean, stat2, (int)C, eps,
+            train, nvec, mask);
+      });
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
-}
-
-template <typename T>
-void fwd_train_t(const void* x, void* y, const void* res, const float* w, const float* b, float* rm, float* rv,
-                 float* sm, float* si, float* ws, int64_t rows, int64_t C, float momentum, float eps, int relu,
-                 uint8_t* mask, int64_t* nbt, hipStream_t s) {
-  const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_stats_kernel<T>), rows, C);
-  bn_stats_kernel<T><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(x), rows, (int)C, g, ws);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  bn_finalize_fwd_kernel<<<finalize_blocks(C), kFinCh * kFinGroups, 0, s>>>(ws, (int)C, rows, momentum, eps, sm, si, rm,
-                                                                            rv, nullptr, nullptr, nullptr, nullptr, nbt);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  norm_t<T>(x, y, res, w, b, sm, si, rows, C, eps, 1, relu, mask, s);
-}
-
-template <typename T>
-void dx_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
-          const float* sm, const float* si, const float* dw, const float* db, void* dx, void* dres, int64_t rows,
-          int64_t div_rows, int64_t C, int rm, hipStream_t s);
-
-template <typename T>
-void bwd_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
-           const float* sm, const float* si, void* dx, void* dres, float* dw, float* db, float* ws, int64_t rows,
-           int64_t C, int relu, int stats_ready, hipStream_t s) {
-  const T* dyr = static_cast<const T*>(dy);
-  const T* xr = static_cast<const T*>(x);
-  const T* yr = static_cast<const T*>(y);
-  // relu: 0 none; 1 mask from y; 2 mask recomputed from x (no residual); 3 mask from saved bits
-  const int rm = relu == 0 ? 0 : (mask != nullptr ? 3 : (y != nullptr ? 1 : 2));
-#define RED(RM)                                                                                                  \
-  {                                                                                                             \
-    const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_bwd_reduce_kernel<T, RM>), rows, C);          \
-    bn_bwd_reduce_kernel<T, RM><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(dyr, xr, yr, mask, w, b, sm, si,   \
-                                                                              rows, (int)C, g, ws);             \
-  }
-  // stats_ready: the reductions were accumulated into ws by the producer of dy (the GEMM's
-  // BN-backward epilogue), so the reduce pass over (dy, x) is skipped
-  if (stats_ready) {}
-  else if (rm == 0) RED(0)
-  else if (rm == 1) RED(1)
-  else if (rm == 2) RED(2)
-  else RED(3)
-#undef RED
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  bn_finalize_bwd_kernel<<<finalize_blocks(C), kFinCh * kFinGroups, 0, s>>>(ws, (int)C, dw, db);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  dx_t<T>(dy, x, y, mask, w, b, sm, si, dw, db, dx, dres, rows, rows, C, rm, s);
 }
 
 // The dx pass from finished per-channel sums (dw, db), which the kernel divides by `div_rows`: the
@@ -1051,107 +989,37 @@ template <typename T>
 void dx_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
           const float* sm, const float* si, const float* dw, const float* db, void* dx, void* dres, int64_t rows,
           int64_t div_rows, int64_t C, int rm, hipStream_t s) {
-  const T* dyr = static_cast<const T*>(dy);
-  const T* xr = static_cast<const T*>(x);
-  const T* yr = static_cast<const T*>(y);
   const int64_t nvec = rows * C / 8;
-  T* dxr = static_cast<T*>(dx);
-  T* drr = static_cast<T*>(dres);
-  const bool fixed = fixed_channels(C);
-#define LAUNCH(RM, DRES, FX)                                                                                    \
-  {                                                                                                            \
-    const size_t lds = FX ? 0 : C * sizeof(DxCoef);                                                            \
-    auto k = bn_bwd_dx_kernel<T, RM, DRES, FX, 2>;   \
-    k<<<elementwise_grid(reinterpret_cast<const void*>(k), lds, nvec), kThreads, lds, s>>>(                    \
-        dyr, xr, yr, mask, w, b, sm, si, dw, db, dxr, drr, div_rows, (int)C, nvec);                            \
-  }
-#define LAUNCH_F(RM, DRES)             \
-  {                                    \
-    if (fixed) LAUNCH(RM, DRES, true)  \
-    else LAUNCH(RM, DRES, false)       \
-  }
-  const bool has_dres = dres != nullptr;
-  if (rm == 0) { if (has_dres) LAUNCH_F(0, true) else LAUNCH_F(0, false) }
-  else if (rm == 1) { if (has_dres) LAUNCH_F(1, true) else LAUNCH_F(1, false) }
-  else if (rm == 2) { if (has_dres) LAUNCH_F(2, true) else LAUNCH_F(2, false) }
-  else { if (has_dres) LAUNCH_F(3, true) else LAUNCH_F(3, false) }
-#undef LAUNCH_F
-#undef LAUNCH
+  dispatch_relu_mode(rm, [&](auto rm_c) {
+    dispatch_bool(dres != nullptr, [&](auto dres_c) {
+      dispatch_bool(fixed_channels(C), [&](auto fixed_c) {
+        constexpr bool FX = decltype(fixed_c)::value;
+        const size_t lds = FX ? 0 : C * sizeof(DxCoef);
+        auto k = bn_bwd_dx_kernel<T, decltype(rm_c)::value, decltype(dres_c)::value, FX, 2>;
+        k<<<elementwise_grid(reinterpret_cast<const void*>(k), lds, nvec), kThreads, lds, s>>>(
+            static_cast<const T*>(dy), static_cast<const T*>(x), static_cast<const T*>(y), mask, w, b, sm, si, dw, db,
+            static_cast<T*>(dx), static_cast<T*>(dres), div_rows, (int)C, nvec);
+      });
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
-template <typename T>
-void apply_dual_t(const void* x, const void* x2, void* y, const float* w, const float* b, const float* sm,
-                  const float* si, const float* w2, const float* b2, const float* sm2, const float* si2, int64_t rows,
-                  int64_t C, uint8_t* mask, hipStream_t s) {
-  const int64_t nvec = rows * C / 8;
-  auto k = bn_norm_dual_kernel<T>;
-  k<<<elementwise_grid(reinterpret_cast<const void*>(k), 0, nvec), kThreads, 0, s>>>(
-      static_cast<const T*>(x), static_cast<const T*>(x2), static_cast<T*>(y), w, b, sm, si, w2, b2, sm2, si2,
-      (int)C, nvec, mask);
+// DET: the deterministic geometry and a stored partial per workgroup (acc = part), else one round
+// of resident workgroups adding into the shards (acc = ws). Returns the number of workgroups.
+template <typename T, bool DET>
+int bwd_reduce_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w, const float* b,
+                 const float* sm, const float* si, float* acc, int64_t rows, int64_t C, int rm, hipStream_t s) {
+  int blocks = 0;
+  dispatch_relu_mode(rm, [&](auto rm_c) {
+    auto k = bn_bwd_reduce_kernel<T, decltype(rm_c)::value, DET>;
+    const Geo g = DET ? det_geometry(rows, C) : reduce_geometry(reinterpret_cast<const void*>(k), rows, C);
+    k<<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(dy), static_cast<const T*>(x),
+                                                    static_cast<const T*>(y), mask, w, b, sm, si, rows, (int)C, g, acc);
+    blocks = g.blocks;
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
-}
-
-template <typename T>
-void bwd_dual_t(const void* dy, const uint8_t* mask, const void* x, const void* x2, const float* w, const float* sm,
-                const float* si, const float* w2, const float* sm2, const float* si2, void* dx, void* dx2, float* dw,
-                float* db, float* dw2, float* db2, float* ws, float* ws2, int64_t rows, int64_t C, hipStream_t s) {
-  const T* dyr = static_cast<const T*>(dy);
-  const T* xr = static_cast<const T*>(x);
-  const T* x2r = static_cast<const T*>(x2);
-  const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_bwd_reduce_dual_kernel<T>), rows, C);
-  bn_bwd_reduce_dual_kernel<T><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(dyr, mask, xr, x2r, sm, si, sm2, si2,
-                                                                             rows, (int)C, g, ws, ws2);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  bn_finalize_bwd2_kernel<<<dim3(finalize_blocks(C), 2), kFinCh * kFinGroups, 0, s>>>(ws, ws2, (int)C, dw, db, dw2,
-                                                                                      db2);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  const int64_t nvec = rows * C / 8;
-  auto k = bn_bwd_dx_dual_kernel<T>;
-  k<<<elementwise_grid(reinterpret_cast<const void*>(k), 0, nvec), kThreads, 0, s>>>(
-      dyr, mask, xr, x2r, w, sm, si, dw, db, w2, sm2, si2, dw2, db2, static_cast<T*>(dx), static_cast<T*>(dx2), rows,
-      (int)C, nvec);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-}
-
-// ---------------------------------------------------------------- synchronised (deterministic) path
-template <typename T>
-void sync_stats_t(const void* x, float* part, float* msg, int64_t rows, int64_t C, float momentum, float eps,
-                  float* sm, float* si, float* rm, float* rv, int64_t* nbt, hipStream_t s) {
-  const Geo g = det_geometry(rows, C);
-  bn_stats_kernel<T, true><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(x), rows, (int)C, g,
-                                                                         part);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  bn_sync_fold_fwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, s>>>(part, g.blocks, (int)C, rows, msg, momentum,
-                                                                           eps, sm, si, rm, rv, nbt);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-}
-
-int relu_mode(int relu, const void* y, const uint8_t* mask) {
-  return relu == 0 ? 0 : (mask != nullptr ? 3 : (y != nullptr ? 1 : 2));
-}
-
-template <typename T>
-void sync_bwd_reduce_t(const void* dy, const void* x, const void* y, const uint8_t* mask, const float* w,
-                       const float* b, const float* sm, const float* si, float* part, float* msg, float* dw,
-                       float* db, int64_t rows, int64_t C, int relu, hipStream_t s) {
-  const T* dyr = static_cast<const T*>(dy);
-  const T* xr = static_cast<const T*>(x);
-  const T* yr = static_cast<const T*>(y);
-  const Geo g = det_geometry(rows, C);
-#define RED(RM)                                                                                                     \
-  bn_bwd_reduce_kernel<T, RM, true><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(dyr, xr, yr, mask, w, b, sm, si, \
-                                                                                  rows, (int)C, g, part);
-  switch (relu_mode(relu, y, mask)) {
-    case 0: RED(0) break;
-    case 1: RED(1) break;
-    case 2: RED(2) break;
-    default: RED(3) break;
-  }
-#undef RED
-  FLUXMPI_HIP_CHECK(hipGetLastError());
-  bn_sync_fold_bwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, s>>>(part, g.blocks, (int)C, msg, dw, db);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
+  return blocks;
 }
 
 void check_rows(int64_t rows) {
@@ -1172,12 +1040,15 @@ void bn_apply_dual(const void* x, const void* x2, void* y, const float* w, const
                    int64_t rows, int64_t C, uint8_t* mask, int dtype, hipStream_t s) {
   check_dual(C, mask);
   check_aligned({w, b, sm, si, w2, b2, sm2, si2});
-  switch (dtype) {
-    case kBF16: apply_dual_t<bf16>(x, x2, y, w, b, sm, si, w2, b2, sm2, si2, rows, C, mask, s); break;
-    case kF16: apply_dual_t<f16>(x, x2, y, w, b, sm, si, w2, b2, sm2, si2, rows, C, mask, s); break;
-    case kF32: apply_dual_t<float>(x, x2, y, w, b, sm, si, w2, b2, sm2, si2, rows, C, mask, s); break;
-    default: throw std::runtime_error("dual batchnorm: unsupported dtype");
-  }
+  const int64_t nvec = rows * C / 8;
+  dispatch_float(dtype, kBadDualDtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto k = bn_norm_dual_kernel<T>;
+    k<<<elementwise_grid(reinterpret_cast<const void*>(k), 0, nvec), kThreads, 0, s>>>(
+        static_cast<const T*>(x), static_cast<const T*>(x2), static_cast<T*>(y), w, b, sm, si, w2, b2, sm2, si2,
+        (int)C, nvec, mask);
+  });
+  FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 void bn_bwd_dual(const void* dy, const uint8_t* mask, const void* x, const void* x2, const float* w, const float* sm,
@@ -1186,12 +1057,25 @@ void bn_bwd_dual(const void* dy, const uint8_t* mask, const void* x, const void*
                  hipStream_t s) {
   check_dual(C, mask);
   check_aligned({w, sm, si, w2, sm2, si2, dw, db, dw2, db2});
-  switch (dtype) {
-    case kBF16: bwd_dual_t<bf16>(dy, mask, x, x2, w, sm, si, w2, sm2, si2, dx, dx2, dw, db, dw2, db2, ws, ws2, rows, C, s); break;
-    case kF16: bwd_dual_t<f16>(dy, mask, x, x2, w, sm, si, w2, sm2, si2, dx, dx2, dw, db, dw2, db2, ws, ws2, rows, C, s); break;
-    case kF32: bwd_dual_t<float>(dy, mask, x, x2, w, sm, si, w2, sm2, si2, dx, dx2, dw, db, dw2, db2, ws, ws2, rows, C, s); break;
-    default: throw std::runtime_error("dual batchnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, kBadDualDtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const T* dyr = static_cast<const T*>(dy);
+    const T* xr = static_cast<const T*>(x);
+    const T* x2r = static_cast<const T*>(x2);
+    const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_bwd_reduce_dual_kernel<T>), rows, C);
+    bn_bwd_reduce_dual_kernel<T><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(dyr, mask, xr, x2r, sm, si, sm2, si2,
+                                                                               rows, (int)C, g, ws, ws2);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    bn_finalize_bwd2_kernel<<<dim3(finalize_blocks(C), 2), kFinCh * kFinGroups, 0, s>>>(ws, ws2, (int)C, dw, db, dw2,
+                                                                                        db2);
+    FLUXMPI_HIP_CHECK(hipGetLastError());
+    const int64_t nvec = rows * C / 8;
+    auto k = bn_bwd_dx_dual_kernel<T>;
+    k<<<elementwise_grid(reinterpret_cast<const void*>(k), 0, nvec), kThreads, 0, s>>>(
+        dyr, mask, xr, x2r, w, sm, si, dw, db, w2, sm2, si2, dw2, db2, static_cast<T*>(dx), static_cast<T*>(dx2), rows,
+        (int)C, nvec);
+  });
+  FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 size_t bn_workspace_floats(int64_t rows, int64_t C) {
@@ -1205,15 +1089,13 @@ void bn_fwd_train(const void* x, void* y, const void* residual, const float* wei
                   hipStream_t stream, int64_t* nbt) {
   check(C);
   check_aligned({weight, bias, save_mean, save_invstd});
-  switch (dtype) {
-    case kBF16: fwd_train_t<bf16>(x, y, residual, weight, bias, running_mean, running_var, save_mean, save_invstd,
-                                  workspace, rows, C, momentum, eps, relu, relu_mask, nbt, stream); break;
-    case kF16: fwd_train_t<f16>(x, y, residual, weight, bias, running_mean, running_var, save_mean, save_invstd,
-                                workspace, rows, C, momentum, eps, relu, relu_mask, nbt, stream); break;
-    case kF32: fwd_train_t<float>(x, y, residual, weight, bias, running_mean, running_var, save_mean, save_invstd,
-                                  workspace, rows, C, momentum, eps, relu, relu_mask, nbt, stream); break;
-    default: throw std::runtime_error("fused batchnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, kBadDtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    stats_t<T>(x, workspace, rows, C, stream);
+    finalize_fwd(workspace, rows, C, momentum, eps, save_mean, save_invstd, running_mean, running_var, nullptr, nullptr,
+                 nullptr, nullptr, nbt, stream);
+    norm_t<T>(x, y, residual, weight, bias, save_mean, save_invstd, rows, C, eps, 1, relu, relu_mask, stream);
+  });
 }
 
 void bn_finalize_bwd(float* ws, int64_t C, float* dw, float* db, hipStream_t s) {
@@ -1226,37 +1108,18 @@ void bn_stats_finalize(const void* x, const float* w, const float* b, float* rm,
                        float* scale, float* shift, float* ws, int64_t rows, int64_t C, float momentum, float eps,
                        int stats_ready, int dtype, hipStream_t s, int64_t* nbt) {
   check(C);
-  if (!stats_ready) {
-#define STATS(T)                                                                                              \
-  {                                                                                                          \
-    const Geo g = reduce_geometry(reinterpret_cast<const void*>(bn_stats_kernel<T>), rows, C);               \
-    bn_stats_kernel<T><<<g.blocks, kThreads, reduce_smem(g, C), s>>>(static_cast<const T*>(x), rows, (int)C, g, \
-                                                                     ws);                                      \
-  }
-    switch (dtype) {
-      case kBF16: STATS(bf16) break;
-      case kF16: STATS(f16) break;
-      case kF32: STATS(float) break;
-      default: throw std::runtime_error("fused batchnorm: unsupported dtype");
-    }
-#undef STATS
-    FLUXMPI_HIP_CHECK(hipGetLastError());
-  }
-  bn_finalize_fwd_kernel<<<finalize_blocks(C), kFinCh * kFinGroups, 0, s>>>(ws, (int)C, rows, momentum, eps, sm, si, rm,
-                                                                            rv, w, b, scale, shift, nbt);
-  FLUXMPI_HIP_CHECK(hipGetLastError());
+  if (!stats_ready)
+    dispatch_float(dtype, kBadDtype, [&](auto tag) { stats_t<typename decltype(tag)::type>(x, ws, rows, C, s); });
+  finalize_fwd(ws, rows, C, momentum, eps, sm, si, rm, rv, w, b, scale, shift, nbt, s);
 }
 
 void bn_apply(const void* x, void* y, const void* res, const float* w, const float* b, const float* sm,
               const float* si, int64_t rows, int64_t C, int relu, uint8_t* mask, int dtype, hipStream_t s) {
   check(C);
   check_aligned({w, b, sm, si});
-  switch (dtype) {
-    case kBF16: norm_t<bf16>(x, y, res, w, b, sm, si, rows, C, 0.f, 1, relu, mask, s); break;
-    case kF16: norm_t<f16>(x, y, res, w, b, sm, si, rows, C, 0.f, 1, relu, mask, s); break;
-    case kF32: norm_t<float>(x, y, res, w, b, sm, si, rows, C, 0.f, 1, relu, mask, s); break;
-    default: throw std::runtime_error("fused batchnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, kBadDtype, [&](auto tag) {
+    norm_t<typename decltype(tag)::type>(x, y, res, w, b, sm, si, rows, C, 0.f, 1, relu, mask, s);
+  });
 }
 
 void bn_fwd_infer(const void* x, void* y, const void* residual, const float* weight, const float* bias,
@@ -1264,12 +1127,10 @@ void bn_fwd_infer(const void* x, void* y, const void* residual, const float* wei
                   int dtype, hipStream_t stream) {
   check(C);
   check_aligned({weight, bias, running_mean, running_var});
-  switch (dtype) {
-    case kBF16: norm_t<bf16>(x, y, residual, weight, bias, running_mean, running_var, rows, C, eps, 0, relu, nullptr, stream); break;
-    case kF16: norm_t<f16>(x, y, residual, weight, bias, running_mean, running_var, rows, C, eps, 0, relu, nullptr, stream); break;
-    case kF32: norm_t<float>(x, y, residual, weight, bias, running_mean, running_var, rows, C, eps, 0, relu, nullptr, stream); break;
-    default: throw std::runtime_error("fused batchnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, kBadDtype, [&](auto tag) {
+    norm_t<typename decltype(tag)::type>(x, y, residual, weight, bias, running_mean, running_var, rows, C, eps, 0, relu,
+                                         nullptr, stream);
+  });
 }
 
 void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
@@ -1278,15 +1139,17 @@ void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_ma
             int64_t rows, int64_t C, int relu, int dtype, hipStream_t stream, int stats_ready) {
   check(C);
   check_aligned({weight, bias, save_mean, save_invstd, dweight, dbias});
-  switch (dtype) {
-    case kBF16: bwd_t<bf16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dx, dres, dweight, dbias, workspace, rows, C,
-                            relu, stats_ready, stream); break;
-    case kF16: bwd_t<f16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dx, dres, dweight, dbias, workspace, rows, C,
-                          relu, stats_ready, stream); break;
-    case kF32: bwd_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dx, dres, dweight, dbias, workspace, rows, C,
-                            relu, stats_ready, stream); break;
-    default: throw std::runtime_error("fused batchnorm: unsupported dtype");
-  }
+  const int rm = relu_mode(relu, y, relu_mask);
+  dispatch_float(dtype, kBadDtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    // stats_ready: the reductions were accumulated into the workspace by the producer of dy (the
+    // GEMM's BN-backward epilogue), so the reduce pass over (dy, x) is skipped
+    if (!stats_ready)
+      bwd_reduce_t<T, false>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, workspace, rows, C, rm, stream);
+    bn_finalize_bwd(workspace, C, dweight, dbias, stream);
+    dx_t<T>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dweight, dbias, dx, dres, rows, rows, C, rm,
+            stream);
+  });
 }
 
 size_t bn_sync_workspace_floats(int64_t rows, int64_t C) {
@@ -1300,15 +1163,16 @@ void bn_sync_stats(const void* x, float* part, float* msg, int64_t rows, int64_t
   check(C);
   check_rows(rows);
   check_aligned({msg, save_mean, save_invstd});
-  switch (dtype) {
-    case kBF16: sync_stats_t<bf16>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
-                                   running_var, nbt, stream); break;
-    case kF16: sync_stats_t<f16>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
-                                 running_var, nbt, stream); break;
-    case kF32: sync_stats_t<float>(x, part, msg, rows, C, momentum, eps, save_mean, save_invstd, running_mean,
-                                   running_var, nbt, stream); break;
-    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
-  }
+  const Geo g = det_geometry(rows, C);
+  dispatch_float(dtype, kBadSyncDtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    bn_stats_kernel<T, true><<<g.blocks, kThreads, reduce_smem(g, C), stream>>>(static_cast<const T*>(x), rows, (int)C,
+                                                                                g, part);
+  });
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+  bn_sync_fold_fwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, stream>>>(
+      part, g.blocks, (int)C, rows, msg, momentum, eps, save_mean, save_invstd, running_mean, running_var, nbt);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 void bn_sync_finalize_fwd(const float* msg, float* running_mean, float* running_var, float* save_mean,
@@ -1328,15 +1192,13 @@ void bn_sync_bwd_reduce(const void* dy, const void* x, const void* y, const uint
   check(C);
   check_rows(rows);
   check_aligned({weight, bias, save_mean, save_invstd, msg});
-  switch (dtype) {
-    case kBF16: sync_bwd_reduce_t<bf16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
-                                        dbias, rows, C, relu, stream); break;
-    case kF16: sync_bwd_reduce_t<f16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
-                                      dbias, rows, C, relu, stream); break;
-    case kF32: sync_bwd_reduce_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, part, msg, dweight,
-                                        dbias, rows, C, relu, stream); break;
-    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
-  }
+  const int blocks = dispatch_float(dtype, kBadSyncDtype, [&](auto tag) {
+    return bwd_reduce_t<typename decltype(tag)::type, true>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd,
+                                                            part, rows, C, relu_mode(relu, y, relu_mask), stream);
+  });
+  bn_sync_fold_bwd_kernel<<<fold_blocks(C), kFoldCh * kFoldGroups, 0, stream>>>(part, blocks, (int)C, msg, dweight,
+                                                                                dbias);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 void bn_sync_bwd_dx(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
@@ -1356,16 +1218,10 @@ void bn_sync_bwd_dx(const void* dy, const void* x, const void* y, const uint8_t*
     sums = coef;
     div_rows = 1;
   }
-  const int rm = relu_mode(relu, y, relu_mask);
-  switch (dtype) {
-    case kBF16: dx_t<bf16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
-                           div_rows, C, rm, stream); break;
-    case kF16: dx_t<f16>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
-                         div_rows, C, rm, stream); break;
-    case kF32: dx_t<float>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx, dres, rows,
-                           div_rows, C, rm, stream); break;
-    default: throw std::runtime_error("sync batchnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, kBadSyncDtype, [&](auto tag) {
+    dx_t<typename decltype(tag)::type>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, sums + C, sums, dx,
+                                       dres, rows, div_rows, C, relu_mode(relu, y, relu_mask), stream);
+  });
 }
 
 }  // namespace fluxmpi

@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <type_traits>
 
 namespace fluxmpi {
 
@@ -178,6 +179,40 @@ __device__ __forceinline__ int find_tensor(const int32_t (&start)[N], int n, int
     if (start[mid] <= b) lo = mid; else hi = mid - 1;
   }
   return lo;
+}
+
+// ---- runtime value -> template parameter (host) ----------------------------------------------
+// f is a generic lambda: it receives a tag (TypeTag<T>, std::bool_constant, std::integral_constant)
+// and names the launch's argument list once; its return value is passed on. An unsupported value
+// throws std::runtime_error(what); `what` is a string, or a callable that builds one when needed.
+template <typename T> struct TypeTag { using type = T; };
+
+template <typename W> [[noreturn]] void dispatch_fail(const W& what) {
+  if constexpr (std::is_invocable_v<W>) throw std::runtime_error(what());
+  else throw std::runtime_error(what);
+}
+
+template <typename W, typename F> decltype(auto) dispatch_float(int dtype, const W& what, F&& f) {
+  switch (dtype) {
+    case kBF16: return f(TypeTag<bf16>{});
+    case kF16: return f(TypeTag<f16>{});
+    case kF32: return f(TypeTag<float>{});
+    default: dispatch_fail(what);
+  }
+}
+
+template <typename W, typename F> decltype(auto) dispatch_float64(int dtype, const W& what, F&& f) {
+  return dtype == kF64 ? f(TypeTag<double>{}) : dispatch_float(dtype, what, f);
+}
+
+template <typename F> decltype(auto) dispatch_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <int V0, int... V, typename W, typename F> decltype(auto) dispatch_int(int v, const W& what, F&& f) {
+  if (v == V0) return f(std::integral_constant<int, V0>{});
+  if constexpr (sizeof...(V) > 0) return dispatch_int<V...>(v, what, f);
+  else dispatch_fail(what);
 }
 
 }  // namespace fluxmpi

@@ -187,6 +187,17 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const T* __restrict__ x, f
   }
 }
 
+// the GELU kernels are compiled for the 16-bit types only, in both forms: f(TypeTag<T>, tanh form?)
+template <typename F>
+void dispatch_half(int dtype, const char* what, F&& f) {
+  if (dtype != kBF16 && dtype != kF16) throw std::runtime_error(what);
+  dispatch_bool(dtype == kBF16, [&](auto bf) {
+    dispatch_bool(g_gelu_tanh != 0, [&](auto tanh_c) {
+      f(TypeTag<std::conditional_t<decltype(bf)::value, bf16, f16>>{}, tanh_c);
+    });
+  });
+}
+
 }  // namespace
 
 int colsum_blocks(int64_t rows) {
@@ -207,19 +218,10 @@ void colsum(const void* x, float* partials, int blocks, int64_t rows, int64_t N,
   const int64_t rpw = (rows + blocks - 1) / blocks;
   const unsigned threads = static_cast<unsigned>(V * R);
   const size_t smem = static_cast<size_t>(R) * N * sizeof(float);
-  switch (dtype) {
-    case kBF16:
-      colsum_kernel<bf16><<<blocks, threads, smem, stream>>>(static_cast<const bf16*>(x), partials, rows, N, rpw, R);
-      break;
-    case kF16:
-      colsum_kernel<f16><<<blocks, threads, smem, stream>>>(static_cast<const f16*>(x), partials, rows, N, rpw, R);
-      break;
-    case kF32:
-      colsum_kernel<float><<<blocks, threads, smem, stream>>>(static_cast<const float*>(x), partials, rows, N, rpw, R);
-      break;
-    default:
-      throw std::runtime_error("colsum: bf16 / fp16 / fp32 only");
-  }
+  dispatch_float(dtype, "colsum: bf16 / fp16 / fp32 only", [&](auto t) {
+    using T = typename decltype(t)::type;
+    colsum_kernel<T><<<blocks, threads, smem, stream>>>(static_cast<const T*>(x), partials, rows, N, rpw, R);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -238,21 +240,11 @@ void gelu_fwd(const void* h, void* g, int64_t n, int dtype, hipStream_t stream) 
   const int64_t nvec = n / 8;
   int64_t blocks = (nvec + 256 * 4 - 1) / (256 * 4);
   if (blocks > 4096) blocks = 4096;
-  const bool t = g_gelu_tanh != 0;
-  switch (dtype) {
-    case kBF16: {
-      auto k = t ? gelu_fwd_kernel<bf16, true> : gelu_fwd_kernel<bf16, false>;
-      k<<<static_cast<unsigned>(blocks), 256, 0, stream>>>(static_cast<const bf16*>(h), static_cast<bf16*>(g), nvec);
-      break;
-    }
-    case kF16: {
-      auto k = t ? gelu_fwd_kernel<f16, true> : gelu_fwd_kernel<f16, false>;
-      k<<<static_cast<unsigned>(blocks), 256, 0, stream>>>(static_cast<const f16*>(h), static_cast<f16*>(g), nvec);
-      break;
-    }
-    default:
-      throw std::runtime_error("gelu_fwd: bf16 / fp16 only");
-  }
+  dispatch_half(dtype, "gelu_fwd: bf16 / fp16 only", [&](auto t, auto tanh_c) {
+    using T = typename decltype(t)::type;
+    gelu_fwd_kernel<T, decltype(tanh_c)::value><<<static_cast<unsigned>(blocks), 256, 0, stream>>>(
+        static_cast<const T*>(h), static_cast<T*>(g), nvec);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -268,23 +260,11 @@ void gelu_bwd_bias(const void* dy, const void* h, void* dh, float* partials, int
     throw std::runtime_error("gelu_bwd_bias: tensors must be 16-byte aligned");
   const int64_t rpw = (rows + blocks - 1) / blocks;
   const unsigned threads = static_cast<unsigned>(N / 8);
-  const bool tanh_form = g_gelu_tanh != 0;
-  switch (dtype) {
-    case kBF16: {
-      auto k = tanh_form ? gelu_bwd_bias_kernel<bf16, true> : gelu_bwd_bias_kernel<bf16, false>;
-      k<<<blocks, threads, 0, stream>>>(static_cast<const bf16*>(dy), static_cast<const bf16*>(h), static_cast<bf16*>(dh),
-                                        partials, rows, N, rpw);
-      break;
-    }
-    case kF16: {
-      auto k = tanh_form ? gelu_bwd_bias_kernel<f16, true> : gelu_bwd_bias_kernel<f16, false>;
-      k<<<blocks, threads, 0, stream>>>(static_cast<const f16*>(dy), static_cast<const f16*>(h), static_cast<f16*>(dh),
-                                        partials, rows, N, rpw);
-      break;
-    }
-    default:
-      throw std::runtime_error("gelu_bwd_bias: bf16 / fp16 only");
-  }
+  dispatch_half(dtype, "gelu_bwd_bias: bf16 / fp16 only", [&](auto t, auto tanh_c) {
+    using T = typename decltype(t)::type;
+    gelu_bwd_bias_kernel<T, decltype(tanh_c)::value><<<blocks, threads, 0, stream>>>(
+        static_cast<const T*>(dy), static_cast<const T*>(h), static_cast<T*>(dh), partials, rows, N, rpw);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 

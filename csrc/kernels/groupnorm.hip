@@ -315,14 +315,15 @@ void fwd_dispatch(const void* x, const void* a, void* h, void* y, const float* w
   T* yp = static_cast<T*>(y);
   const size_t lds = gn_lds(s);
   const dim3 grid(static_cast<unsigned>(N));
-  const bool add = a != nullptr, saveh = h != nullptr;
-#define GN_FWD(A, R, H) \
-  gn_fwd_kernel<T, A, R, H><<<grid, block_of(s), lds, st>>>(xp, ap, hp, yp, w, b, mean, rstd, s, eps, ys)
-  if (add && relu) { if (saveh) GN_FWD(true, true, true); else GN_FWD(true, true, false); }
-  else if (add) { if (saveh) GN_FWD(true, false, true); else GN_FWD(true, false, false); }
-  else if (relu) { if (saveh) GN_FWD(false, true, true); else GN_FWD(false, true, false); }
-  else GN_FWD(false, false, false);
-#undef GN_FWD
+  dispatch_bool(a != nullptr, [&](auto add_c) {
+    dispatch_bool(relu, [&](auto relu_c) {
+      dispatch_bool(h != nullptr, [&](auto saveh_c) {
+        constexpr bool A = decltype(add_c)::value, R = decltype(relu_c)::value;
+        constexpr bool H = decltype(saveh_c)::value && (A || R);  // without add or ReLU, h would be x: not written
+        gn_fwd_kernel<T, A, R, H><<<grid, block_of(s), lds, st>>>(xp, ap, hp, yp, w, b, mean, rstd, s, eps, ys);
+      });
+    });
+  });
 }
 
 template <typename T>
@@ -330,12 +331,10 @@ void bwd_dispatch(const void* dy, const void* h, const float* mean, const float*
                   float* part, int64_t N, const GnShape& s, bool relu, hipStream_t st) {
   const size_t lds = gn_lds(s);
   const dim3 grid(static_cast<unsigned>(N));
-  if (relu)
-    gn_bwd_kernel<T, true><<<grid, block_of(s), lds, st>>>(static_cast<const T*>(dy), static_cast<const T*>(h), mean,
-                                                          rstd, w, static_cast<T*>(dh), part, s);
-  else
-    gn_bwd_kernel<T, false><<<grid, block_of(s), lds, st>>>(static_cast<const T*>(dy), static_cast<const T*>(h), mean,
-                                                           rstd, w, static_cast<T*>(dh), part, s);
+  dispatch_bool(relu, [&](auto relu_c) {
+    gn_bwd_kernel<T, decltype(relu_c)::value><<<grid, block_of(s), lds, st>>>(
+        static_cast<const T*>(dy), static_cast<const T*>(h), mean, rstd, w, static_cast<T*>(dh), part, s);
+  });
 }
 
 void check_ptrs(std::initializer_list<const void*> ps) {
@@ -354,12 +353,9 @@ void groupnorm_nhwc_fwd(const void* x, const void* add, void* h, void* y, const 
   if (N < 1 || N > 2147483647LL) throw std::runtime_error("fused groupnorm: bad N");
   if (y_stride == 0) y_stride = HW * C;
   if (y_stride < HW * C || y_stride % 8 != 0) throw std::runtime_error("fused groupnorm: bad output sample stride");
-  switch (dtype) {
-    case kBF16: fwd_dispatch<bf16>(x, add, h, y, w, b, mean, rstd, N, s, relu, eps, stream, y_stride); break;
-    case kF16: fwd_dispatch<f16>(x, add, h, y, w, b, mean, rstd, N, s, relu, eps, stream, y_stride); break;
-    case kF32: fwd_dispatch<float>(x, add, h, y, w, b, mean, rstd, N, s, relu, eps, stream, y_stride); break;
-    default: throw std::runtime_error("fused groupnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, "fused groupnorm: unsupported dtype", [&](auto t) {
+    fwd_dispatch<typename decltype(t)::type>(x, add, h, y, w, b, mean, rstd, N, s, relu, eps, stream, y_stride);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -369,12 +365,9 @@ void groupnorm_nhwc_bwd(const void* dy, const void* h, const float* mean, const 
   const GnShape s = gn_shape(HW, C, G);
   check_ptrs({dy, h, dh});
   if (N < 1 || N > 2147483647LL) throw std::runtime_error("fused groupnorm: bad N");
-  switch (dtype) {
-    case kBF16: bwd_dispatch<bf16>(dy, h, mean, rstd, w, dh, partials, N, s, relu, stream); break;
-    case kF16: bwd_dispatch<f16>(dy, h, mean, rstd, w, dh, partials, N, s, relu, stream); break;
-    case kF32: bwd_dispatch<float>(dy, h, mean, rstd, w, dh, partials, N, s, relu, stream); break;
-    default: throw std::runtime_error("fused groupnorm: unsupported dtype");
-  }
+  dispatch_float(dtype, "fused groupnorm: unsupported dtype", [&](auto t) {
+    bwd_dispatch<typename decltype(t)::type>(dy, h, mean, rstd, w, dh, partials, N, s, relu, stream);
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 

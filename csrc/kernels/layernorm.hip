@@ -326,18 +326,19 @@ int bwd_launch(const void* dy, const void* x, const void* dh, const float* mean,
   return static_cast<int>(blocks);
 }
 
-// compiled vectors-per-lane variants (D up to 8192)
-#define LN_VPL_SWITCH(VPL_VAR, CALL) \
-  switch (VPL_VAR) {                 \
-    case 1: CALL(1); break;          \
-    case 2: CALL(2); break;          \
-    case 3: CALL(3); break;          \
-    case 4: CALL(4); break;          \
-    case 6: CALL(6); break;          \
-    case 8: CALL(8); break;          \
-    case 12: CALL(12); break;        \
-    default: CALL(16); break;        \
-  }
+// T x affine type (fp32, or T when `wt`) x the compiled vectors-per-lane variants (D up to 8192;
+// vpl_for returns one of them, 16 for everything above 12): f(TypeTag<T>, TypeTag<A>, VPL)
+template <typename F>
+decltype(auto) dispatch_ln(int dtype, bool wt, int vpl, F&& f) {
+  return dispatch_float(dtype, "fused layernorm: unsupported dtype", [&](auto t) {
+    return dispatch_bool(wt, [&](auto wt_c) {
+      using T = typename decltype(t)::type;
+      using A = std::conditional_t<decltype(wt_c)::value, T, float>;
+      return dispatch_int<1, 2, 3, 4, 6, 8, 12, 16>(vpl, "fused layernorm: no kernel for this D",
+                                                    [&](auto v) { return f(t, TypeTag<A>{}, v); });
+    });
+  });
+}
 
 }  // namespace
 
@@ -355,39 +356,18 @@ void layernorm_fwd(const void* x, const void* residual, void* h, void* y, const 
     throw std::runtime_error("fused layernorm: w and b must be 16-byte aligned (ones / zeros when absent)");
   check_affine(dtype, wdtype, "fused layernorm");
   const bool wt = wdtype != static_cast<int>(kF32);
-#define CALL_ADD(V) fwd_launch<TT, true, V, AT>(x, residual, h, y, w, b, mean, rstd, rows, D, eps, stream)
-#define CALL_NOADD(V) fwd_launch<TT, false, V, AT>(x, residual, h, y, w, b, mean, rstd, rows, D, eps, stream)
-#define CALL_ALL                                                                \
-  if (add) { LN_VPL_SWITCH(vpl, CALL_ADD) } else { LN_VPL_SWITCH(vpl, CALL_NOADD) }
-  switch (dtype) {
-    case kBF16: {
-      using TT = bf16;
-      if (wt) { using AT = bf16; CALL_ALL } else { using AT = float; CALL_ALL }
-      break;
-    }
-    case kF16: {
-      using TT = f16;
-      if (wt) { using AT = f16; CALL_ALL } else { using AT = float; CALL_ALL }
-      break;
-    }
-    case kF32: {
-      using TT = float;
-      using AT = float;
-      CALL_ALL
-      break;
-    }
-    default:
-      throw std::runtime_error("fused layernorm: unsupported dtype");
-  }
-#undef CALL_ALL
-#undef CALL_ADD
-#undef CALL_NOADD
+  dispatch_ln(dtype, wt, vpl, [&](auto t, auto at, auto v) {
+    dispatch_bool(add, [&](auto add_c) {
+      fwd_launch<typename decltype(t)::type, decltype(add_c)::value, decltype(v)::value, typename decltype(at)::type>(
+          x, residual, h, y, w, b, mean, rstd, rows, D, eps, stream);
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
 int layernorm_bwd(const void* dy, const void* x, const void* dh_ext, const float* mean, const float* rstd,
                   const void* w, void* dx, float* partials, int max_blocks, int64_t rows, int64_t D, int dtype,
-                  int wdtype, bool colsum, hipStream_t stream) {
+                  int wdtype, hipStream_t stream, bool colsum) {
   const int vpl = vpl_for(D);
   const bool dh = dh_ext != nullptr;
   if (colsum && !dh) throw std::runtime_error("fused layernorm backward: colsum needs the residual-stream input");
@@ -395,37 +375,14 @@ int layernorm_bwd(const void* dy, const void* x, const void* dh_ext, const float
     throw std::runtime_error("fused layernorm backward: w must be 16-byte aligned (ones when absent)");
   check_affine(dtype, wdtype, "fused layernorm backward");
   const bool wt = wdtype != static_cast<int>(kF32);
-  int blocks = 0;
-#define CALL_DH(V) blocks = bwd_launch<TT, true, V, AT>(dy, x, dh_ext, mean, rstd, w, dx, partials, max_blocks, rows, D, stream)
-#define CALL_NODH(V) blocks = bwd_launch<TT, false, V, AT>(dy, x, dh_ext, mean, rstd, w, dx, partials, max_blocks, rows, D, stream)
-#define CALL_DHCS(V) blocks = bwd_launch<TT, true, V, AT, true>(dy, x, dh_ext, mean, rstd, w, dx, partials, max_blocks, rows, D, stream)
-#define CALL_ALL                                                                \
-  if (dh && colsum) { LN_VPL_SWITCH(vpl, CALL_DHCS) } else if (dh) { LN_VPL_SWITCH(vpl, CALL_DH) }      \
-  else { LN_VPL_SWITCH(vpl, CALL_NODH) }
-  switch (dtype) {
-    case kBF16: {
-      using TT = bf16;
-      if (wt) { using AT = bf16; CALL_ALL } else { using AT = float; CALL_ALL }
-      break;
-    }
-    case kF16: {
-      using TT = f16;
-      if (wt) { using AT = f16; CALL_ALL } else { using AT = float; CALL_ALL }
-      break;
-    }
-    case kF32: {
-      using TT = float;
-      using AT = float;
-      CALL_ALL
-      break;
-    }
-    default:
-      throw std::runtime_error("fused layernorm: unsupported dtype");
-  }
-#undef CALL_ALL
-#undef CALL_DH
-#undef CALL_DHCS
-#undef CALL_NODH
+  // 0: no residual-stream gradient; 1: dh added; 2: dh added and the column sums of dx written
+  const int blocks = dispatch_ln(dtype, wt, vpl, [&](auto t, auto at, auto v) {
+    return dispatch_int<0, 1, 2>(dh ? (colsum ? 2 : 1) : 0, "fused layernorm backward: bad mode", [&](auto m) {
+      constexpr int M = decltype(m)::value;
+      return bwd_launch<typename decltype(t)::type, M != 0, decltype(v)::value, typename decltype(at)::type, M == 2>(
+          dy, x, dh_ext, mean, rstd, w, dx, partials, max_blocks, rows, D, stream);
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
   return blocks;
 }

@@ -190,17 +190,6 @@ void for_each_group(const std::vector<uintptr_t>& src, const std::vector<uintptr
   flush();
 }
 
-template <typename Tin>
-void copy_from(int out_dtype, const CopyArgs& a, int blocks, float scale, hipStream_t s) {
-  switch (out_dtype) {
-    case kF32: mt_copy_kernel<Tin, float><<<blocks, kThreads, 0, s>>>(a, scale); break;
-    case kBF16: mt_copy_kernel<Tin, bf16><<<blocks, kThreads, 0, s>>>(a, scale); break;
-    case kF16: mt_copy_kernel<Tin, f16><<<blocks, kThreads, 0, s>>>(a, scale); break;
-    case kF64: mt_copy_kernel<Tin, double><<<blocks, kThreads, 0, s>>>(a, scale); break;
-    default: throw std::runtime_error("mt_copy: unsupported output dtype " + std::to_string(out_dtype));
-  }
-}
-
 }  // namespace
 
 void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& dst,
@@ -208,18 +197,20 @@ void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& ds
              hipStream_t stream) {
   if (src.size() != numel.size() || dst.size() != numel.size())
     throw std::runtime_error("mt_copy: list length mismatch");
+  const auto bad_in = [&] { return "mt_copy: unsupported input dtype " + std::to_string(in_dtype); };
+  const auto bad_out = [&] {
+    return in_dtype == kF64 ? std::string("mt_copy: fp64 -> low precision not supported")
+                            : "mt_copy: unsupported output dtype " + std::to_string(out_dtype);
+  };
   for_each_group(src, dst, numel, [&](const CopyArgs& a, int blocks) {
-    switch (in_dtype) {
-      case kF32: copy_from<float>(out_dtype, a, blocks, scale, stream); break;
-      case kBF16: copy_from<bf16>(out_dtype, a, blocks, scale, stream); break;
-      case kF16: copy_from<f16>(out_dtype, a, blocks, scale, stream); break;
-      case kF64:
-        if (out_dtype == kF64) mt_copy_kernel<double, double><<<blocks, kThreads, 0, stream>>>(a, scale);
-        else if (out_dtype == kF32) mt_copy_kernel<double, float><<<blocks, kThreads, 0, stream>>>(a, scale);
-        else throw std::runtime_error("mt_copy: fp64 -> low precision not supported");
-        break;
-      default: throw std::runtime_error("mt_copy: unsupported input dtype " + std::to_string(in_dtype));
-    }
+    dispatch_float64(in_dtype, bad_in, [&](auto in) {
+      dispatch_float64(out_dtype, bad_out, [&](auto out) {
+        using Tin = typename decltype(in)::type;
+        using Tout = typename decltype(out)::type;
+        if constexpr (std::is_same_v<Tin, double> && sizeof(Tout) == 2) dispatch_fail(bad_out);
+        else mt_copy_kernel<Tin, Tout><<<blocks, kThreads, 0, stream>>>(a, scale);
+      });
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }
@@ -227,13 +218,9 @@ void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& ds
 void mt_fill(const std::vector<uintptr_t>& dst, const std::vector<int64_t>& numel, int dtype,
              float value, hipStream_t stream) {
   for_each_group({}, dst, numel, [&](const CopyArgs& a, int blocks) {
-    switch (dtype) {
-      case kF32: mt_fill_kernel<float><<<blocks, kThreads, 0, stream>>>(a, value); break;
-      case kBF16: mt_fill_kernel<bf16><<<blocks, kThreads, 0, stream>>>(a, value); break;
-      case kF16: mt_fill_kernel<f16><<<blocks, kThreads, 0, stream>>>(a, value); break;
-      case kF64: mt_fill_kernel<double><<<blocks, kThreads, 0, stream>>>(a, value); break;
-      default: throw std::runtime_error("mt_fill: unsupported dtype");
-    }
+    dispatch_float64(dtype, "mt_fill: unsupported dtype", [&](auto t) {
+      mt_fill_kernel<typename decltype(t)::type><<<blocks, kThreads, 0, stream>>>(a, value);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }
@@ -241,12 +228,9 @@ void mt_fill(const std::vector<uintptr_t>& dst, const std::vector<int64_t>& nume
 void mt_sumsq(const std::vector<uintptr_t>& src, const std::vector<int64_t>& numel, int dtype,
               float* out, hipStream_t stream) {
   for_each_group(src, {}, numel, [&](const CopyArgs& a, int blocks) {
-    switch (dtype) {
-      case kF32: mt_sumsq_kernel<float><<<blocks, kThreads, 0, stream>>>(a, out); break;
-      case kBF16: mt_sumsq_kernel<bf16><<<blocks, kThreads, 0, stream>>>(a, out); break;
-      case kF16: mt_sumsq_kernel<f16><<<blocks, kThreads, 0, stream>>>(a, out); break;
-      default: throw std::runtime_error("mt_sumsq: unsupported dtype");
-    }
+    dispatch_float(dtype, "mt_sumsq: unsupported dtype", [&](auto t) {
+      mt_sumsq_kernel<typename decltype(t)::type><<<blocks, kThreads, 0, stream>>>(a, out);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }

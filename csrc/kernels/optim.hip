@@ -407,13 +407,10 @@ void leaf_sumsq_impl(const std::vector<uintptr_t>& grad, const std::vector<int64
 
 void mt_leaf_sumsq(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
                    void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream) {
-  switch (g_dtype) {
-    case kF32: leaf_sumsq_impl<float>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
-    case kBF16: leaf_sumsq_impl<bf16>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
-    case kF16: leaf_sumsq_impl<f16>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
-    case kF64: leaf_sumsq_impl<double>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream); break;
-    default: throw std::runtime_error("mt_leaf_sumsq: unsupported gradient dtype " + std::to_string(g_dtype));
-  }
+  dispatch_float64(
+      g_dtype, [&] { return "mt_leaf_sumsq: unsupported gradient dtype " + std::to_string(g_dtype); }, [&](auto t) {
+        leaf_sumsq_impl<typename decltype(t)::type>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream);
+      });
 }
 
 void clip_total(const void* sumsq, int64_t n, int acc_dtype, float* slot, int accumulate, float omega,

@@ -256,26 +256,16 @@ void bn_relu_maxpool_fwd(const void* x, const float* scale, const float* shift, 
   // 56 x 8 = 448 lanes; a 256-lane workgroup looping over it left a quarter of its lanes idle)
   const int64_t per_row = g.OW * (C / 8);
   const int thr = per_row <= 1024 ? static_cast<int>((per_row + 63) / 64 * 64) : kThreads;
-  switch (dtype) {
-    case kBF16:
-      if (g.K == 3 && !std::getenv("FLUXMPI_POOL_GENERIC"))
-        bn_relu_maxpool_fwd_kernel<bf16, 3><<<nb, thr, 0, s>>>(static_cast<const bf16*>(x), scale, shift,
-                                                                  static_cast<bf16*>(y), idx, g);
-      else
-        bn_relu_maxpool_fwd_kernel<bf16><<<nb, thr, 0, s>>>(static_cast<const bf16*>(x), scale, shift,
-                                                                 static_cast<bf16*>(y), idx, g);
-      break;
-    case kF16:
-      bn_relu_maxpool_fwd_kernel<f16><<<nb, thr, 0, s>>>(static_cast<const f16*>(x), scale, shift,
-                                                              static_cast<f16*>(y), idx, g);
-      break;
-    case kF32:
-      bn_relu_maxpool_fwd_kernel<float><<<nb, thr, 0, s>>>(static_cast<const float*>(x), scale, shift,
-                                                                static_cast<float*>(y), idx, g);
-      break;
-    default:
-      throw std::runtime_error("bn_relu_maxpool_fwd: unsupported dtype");
-  }
+  dispatch_float(dtype, "bn_relu_maxpool_fwd: unsupported dtype", [&](auto t) {
+    using T = typename decltype(t)::type;
+    // the unrolled 3x3 window is compiled for bf16 only
+    const bool k3 = std::is_same_v<T, bf16> && g.K == 3 && !std::getenv("FLUXMPI_POOL_GENERIC");
+    dispatch_bool(k3, [&](auto k3_c) {
+      constexpr int KK = decltype(k3_c)::value && std::is_same_v<T, bf16> ? 3 : 0;
+      bn_relu_maxpool_fwd_kernel<T, KK><<<nb, thr, 0, s>>>(static_cast<const T*>(x), scale, shift, static_cast<T*>(y),
+                                                           idx, g);
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -284,23 +274,13 @@ void maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int64_t N, int64_
   const PoolGeo g = make_geo(N, H, W, C, K, S, P);
   const int nb = static_cast<int>(N * H);  // one workgroup per input row
   const int nw = (K + S - 1) / S;
-#define POOL_BWD(T, NW)                                                                                         \
-  maxpool_bwd_gather_kernel<T, NW><<<nb, kThreads, 0, s>>>(static_cast<const T*>(dy), idx, static_cast<T*>(dx), g)
-#define POOL_BWD_NW(T)                              \
-  {                                                 \
-    if (nw == 1) POOL_BWD(T, 1);                    \
-    else if (nw == 2) POOL_BWD(T, 2);               \
-    else if (nw == 3) POOL_BWD(T, 3);               \
-    else throw std::runtime_error("maxpool_bwd: ceil(K/S) > 3 unsupported"); \
-  }
-  switch (dtype) {
-    case kBF16: POOL_BWD_NW(bf16) break;
-    case kF16: POOL_BWD_NW(f16) break;
-    case kF32: POOL_BWD_NW(float) break;
-    default: throw std::runtime_error("maxpool_bwd: unsupported dtype");
-  }
-#undef POOL_BWD_NW
-#undef POOL_BWD
+  dispatch_float(dtype, "maxpool_bwd: unsupported dtype", [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_int<1, 2, 3>(nw, "maxpool_bwd: ceil(K/S) > 3 unsupported", [&](auto nw_c) {
+      maxpool_bwd_gather_kernel<T, decltype(nw_c)::value><<<nb, kThreads, 0, s>>>(static_cast<const T*>(dy), idx,
+                                                                                  static_cast<T*>(dx), g);
+    });
+  });
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 

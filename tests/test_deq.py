@@ -300,6 +300,56 @@ def test_deq_train_step_gpu_param_grads():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 6, 7])
+def test_anderson_every_history_length_gpu(n):
+    """The history lengths the tests above leave out (the kernels are compiled per n = 1 .. 8): gram with every
+    row fresh (n = 4, 6, 7), with one fresh row read next to the stored G (n = 1, 3, 4, 6, 7), the solve
+    (n = 4, 6, 7) and the mix with and without the X term (n = 2, 4, 6, 7), at the smallest shapes of those
+    tests, against their references and tolerances."""
+    torch.manual_seed(40 + n)
+    bsz, m, d = 3, 8, 36
+    X = torch.randn(bsz, m, d, device="cuda")
+    Fv = torch.randn(bsz, m, d, device="cuda")
+    tol = dict(rtol=1e-4, atol=1e-3 * d ** 0.5)
+    last = n - 1
+    if n in (4, 6, 7):
+        H, fn = AO.gram(X, Fv, n, last)
+        Hr, fr = _ref_gram(X, Fv, n, last)
+        torch.testing.assert_close(H.double(), Hr, **tol)
+        torch.testing.assert_close(fn.double(), fr, rtol=1e-4, atol=1e-3)
+    if n != 2:
+        G = torch.zeros_like(X)
+        AO.gram(X, Fv, n, last, G, tuple(range(n)))  # fills G
+        s = n // 2
+        X[:, s].normal_()
+        Fv[:, s].normal_()
+        H, fn = AO.gram(X, Fv, n, s, G, (s,))
+        Hr, fr = _ref_gram(X, Fv, n, s)
+        torch.testing.assert_close(H.double(), Hr, **tol)
+        torch.testing.assert_close(fn.double(), fr, rtol=1e-4, atol=1e-3)
+        torch.testing.assert_close(G[:, s], Fv[:, s] - X[:, s])
+    if n in (4, 6, 7):
+        d2, lam = 4100, 1e-4
+        X2 = torch.randn(bsz, m, d2, device="cuda")
+        F2 = X2 + 0.1 * torch.randn(bsz, m, d2, device="cuda")
+        alpha, _ = AO.gram_solve(X2, F2, n, last, torch.zeros_like(X2), tuple(range(n)), lam, True)
+        Hr, _ = _ref_gram(X2, F2, n, last)
+        A = torch.zeros(bsz, n + 1, n + 1, dtype=torch.float64, device="cuda")
+        A[:, 0, 1:] = A[:, 1:, 0] = 1
+        A[:, 1:, 1:] = Hr + lam * torch.eye(n, dtype=torch.float64, device="cuda")
+        y = torch.zeros(bsz, n + 1, 1, dtype=torch.float64, device="cuda")
+        y[:, 0] = 1
+        torch.testing.assert_close(alpha.double(), torch.linalg.solve(A, y)[:, 1:, 0], rtol=2e-3, atol=2e-3)
+    if n in (2, 4, 6, 7):
+        alpha = torch.randn(bsz, n, device="cuda")
+        for beta in (1.0, 0.8):
+            want = _ref_mix(X, Fv, alpha, beta)
+            slot = (n + 2) % m
+            AO.mix(X, Fv, alpha, slot, beta, None)
+            torch.testing.assert_close(X[:, slot].double(), want, rtol=1e-5, atol=1e-4)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("hdt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("fdt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("n", [2, 5, 8])

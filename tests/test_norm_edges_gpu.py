@@ -993,7 +993,7 @@ GN_SHAPES = [(2, 8, 1, 1, 1), (2, 48, 3, 3, 8), (1, 64, 9, 9, 64), (2, 520, 3, 5
 
 # (add, relu, save h, extra elements between the samples of the out= slot)
 GN_COMBOS = [(False, False, False, 0), (True, False, True, 0), (False, True, True, 64), (True, True, True, 0),
-             (True, True, False, 64)]
+             (True, True, False, 64), (True, False, False, 0), (False, True, False, 0)]
 
 
 def _gn_case(ext, family, ratio, n, c, hh, ww, g, dtype, errs, combos=None, affine_on=True, eps=1e-5):

@@ -5,7 +5,8 @@ derived as in ``norm_edges``; nothing is fitted). A CPU test walks the same case
 
 Shapes: C in {8, 24, 64, 2048} (24: the coefficients staged in LDS), shards of one workgroup (rows 1, 5, 37: a
 ragged tail, rows not a multiple of rpi), and of 2 - 5 workgroups (1100+ rows at C = 64, 50 / 100 / 156 at 2048,
-8199 at 8, 2963 at 24), an empty shard in every 3-rank split.
+8199 at 8, 2963 at 24), an empty shard in every 3-rank split. The backward's ReLU decision comes from the mask
+bits (ReLU + residual), is recomputed from x (ReLU alone) or, in test_sync_relu_from_y, is read from y.
 """
 
 import pytest
@@ -49,10 +50,15 @@ def _vec(n, init=None):
 class RawPlayer:
     """The raw entry points on outputs pre-filled with NaN inside guard bands (checked after every call). The
     partial buffer is a fresh NaN-filled, guarded one of exactly ``bn_sync_workspace_floats`` per call: a partial
-    the reduction left unwritten would reach the fold as NaN."""
+    the reduction left unwritten would reach the fold as NaN. ``from_y``: the backward gets the stored output y
+    in place of the mask bits (ReLU mode 1: the decision is y > 0)."""
 
-    def __init__(self, ext, dtype, errs, tag):
-        self.ext, self.dtype, self.errs, self.tag = ext, dtype, errs, tag
+    def __init__(self, ext, dtype, errs, tag, from_y=False):
+        self.ext, self.dtype, self.errs, self.tag, self.from_y = ext, dtype, errs, tag, from_y
+
+    def _decision(self, fw, relu):
+        """(y, mask) as the backward entry points take them."""
+        return (fw["y"].contiguous(), None) if (self.from_y and relu) else (None, fw["mask"])
 
     def _part(self, rows, C):
         need = self.ext.bn_sync_workspace_floats(rows, C)
@@ -108,7 +114,8 @@ class RawPlayer:
         if rows == 0:
             return torch.zeros(2 * C, device="cuda"), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
         part, msg, dw, db = self._part(rows, C), _vec(2 * C), _vec(C), _vec(C)
-        self.ext.bn_sync_bwd_reduce(sh["dy"].data_ptr(), x.data_ptr(), 0, _p(fw["mask"]),
+        yk, mk = self._decision(fw, relu)
+        self.ext.bn_sync_bwd_reduce(sh["dy"].data_ptr(), x.data_ptr(), _p(yk), _p(mk),
                                     _p(sh["w"]) if affine_on else 0, _p(sh["b"]) if affine_on else 0,
                                     fw["mean"].data_ptr(), fw["inv"].data_ptr(), part[1].data_ptr(), msg[1].data_ptr(),
                                     dw[1].data_ptr(), db[1].data_ptr(), rows, C, int(relu), _code(self.dtype), _st())
@@ -125,7 +132,8 @@ class RawPlayer:
         dres = E.guarded(rows, C, C, self.dtype, "cuda") if want_dres else None
         coef = _vec(2 * C) if count is not None else None
         msg = msg.contiguous()
-        self.ext.bn_sync_bwd_dx(sh["dy"].data_ptr(), x.data_ptr(), 0, _p(fw["mask"]), _p(sh["w"]) if affine_on else 0,
+        yk, mk = self._decision(fw, relu)
+        self.ext.bn_sync_bwd_dx(sh["dy"].data_ptr(), x.data_ptr(), _p(yk), _p(mk), _p(sh["w"]) if affine_on else 0,
                                 _p(sh["b"]) if affine_on else 0, fw["mean"].data_ptr(), fw["inv"].data_ptr(),
                                 msg.data_ptr(), _p(count), coef[1].data_ptr() if coef else 0, dx[1].data_ptr(),
                                 dres[1].data_ptr() if dres else 0, rows, C, int(relu), _code(self.dtype), _st())
@@ -207,6 +215,23 @@ def test_sync_exact_shard_invariant(gpu_ext, C, dtype):
     half of the backward message is exact; and everything lies within the derived bounds (db equal)."""
     errs = []
     _exact_case(gpu_ext, C, dtype, errs)
+    assert not errs, "\n".join(errs)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DT, ids=DT_IDS)
+@pytest.mark.parametrize("C", [16, 24])
+def test_sync_relu_from_y(gpu_ext, C, dtype):
+    """ReLU mode 1 of the deterministic reduce and of the dx pass (the y pointer given, no mask bits), which the
+    cases above never select: 37 rows (one unrolled group plus a tail) at C = 16 (coefficients in registers) and
+    C = 24 (in LDS), ReLU + residual, against the same float64 reference and bounds. The stored mask stays the
+    reference's decision; y > 0 is checked to be the same decision."""
+    errs, tag = [], f"uniform [37] C {C} relu_res from y"
+    inp = _cuda(N.rows_inputs("uniform", 37, C, dtype))
+    fwd, bwd = SE.play(RawPlayer(gpu_ext, dtype, errs, tag, from_y=True), SE.split(inp, [37]), "relu_res", True, None,
+                       errs, tag, local_count=True)
+    assert torch.equal(fwd["y"] > 0, N.mask_bits(fwd["mask"], (37, C)).bool())
+    SE.check_play(tag, inp, fwd, bwd, SE.L_sync([37], C), "relu_res", True, dtype, errs)
     assert not errs, "\n".join(errs)
 
 
