@@ -61,24 +61,28 @@ void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& g
             const SgdHyper& h, hipStream_t stream);
 
 // The rest of the rule set (optim_rules.hip), one generic kernel with a per-element functor.
+// kLars / kLamb: the layer-wise rules (optim_layerwise.hip), two phases (norm partials, then the
+// update scaled by the leaf's trust ratio) behind the same entry.
 enum RuleKind : int { kRmsProp = 0, kAdaGrad = 1, kLion = 2, kAdaMax = 3, kAmsGrad = 4, kNAdam = 5,
-                      kAdaBelief = 6, kAdaDelta = 7 };
+                      kAdaBelief = 6, kAdaDelta = 7, kLars = 8, kLamb = 9 };
 struct RuleHyper {
   int kind;                  // RuleKind
   // doubles: fp64 leaves compute with the caller's values (1 - beta2 of a float 0.999 is off by
   // 1e-5); the fp32 kernels round them once, to what the caller's fp32 value was
-  double lr, beta1, beta2, eps;  // beta1 is rho for RMSProp / AdaDelta
+  double lr, beta1, beta2, eps;  // beta1 is rho for RMSProp / AdaDelta / LARS; beta2 is LARS' trust coefficient
   double bt1, bt2;           // beta1^t, beta2^t (host mode; AdaMax, NAdam, AdaBelief)
-  double weight_decay;       // WeightDecay after the rule: dx += wd * x
+  double weight_decay;       // WeightDecay after the rule: dx += wd * x (LARS / LAMB: the rule's own decay)
   float grad_scale;
   const float* dev;          // optional device block {lr, beta1^t, beta2^t}; {lr} for rules without beta^t
   const float* dev_gscale;   // as in AdamHyper
-  const void* tscale;
-  float clip_delta;
+  const void* tscale;        // LARS / LAMB: written, the trust ratio of each leaf of the call (no input scale)
+  float clip_delta;          // LARS / LAMB: must be 0
 };
 // s1 / s2 / s3: the rule's state tensors in its Optimisers.jl order (as many lists as the rule
 // keeps states: 1 RMSProp, AdaGrad, Lion; 2 AdaMax, NAdam, AdaBelief, AdaDelta; 3 AMSGrad; the
 // others empty). master as in mt_adam. adam_advance advances a device block with beta^t entries.
+// LARS (s1: velocity) and LAMB (s1, s2: m, v; device block as Adam's) take in s3 each leaf's address
+// in a workspace of 2 * sumsq_partials(numel) entries of fp32 (fp64 leaves: fp64), no zero fill.
 void mt_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
              const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
              const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,

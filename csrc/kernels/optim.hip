@@ -202,25 +202,6 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
 }
 
 // ---- deterministic multi-tensor sum of squares + clip scales -------------------------------
-// sum over the workgroup, valid in thread 0. Wave level: DPP (fp32) / xor shuffles (fp64), every
-// lane takes part (EXEC full); then the four wave totals through LDS, added in wave order.
-template <typename A>
-__device__ __forceinline__ A block_sum(A v) {
-  __shared__ A wave_tot[kThreads / 64];
-  if constexpr (sizeof(A) == 4) {
-    v = wave_sum_dpp(v);
-  } else {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  A s = wave_tot[0];
-#pragma unroll
-  for (int w = 1; w < kThreads / 64; ++w) s += wave_tot[w];
-  return s;
-}
-
 // launch 1: the job layout of the update kernels; workgroup b writes partials[pbase + b]
 template <typename G>
 __global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, typename Acc<G>::type* __restrict__ partials) {

@@ -1,11 +1,12 @@
 // Shared by the fused multi-tensor optimiser kernels (optim.hip: Adam, SGD, sums of squares;
-// optim_rules.hip: the rest of the rule set): the job layout — 4096-element chunks of up to 24
+// optim_rules.hip: the rest of the rule set; optim_layerwise.hip: LARS, LAMB): the job layout — 4096-element chunks of up to 24
 // leaves per launch, the chunk -> leaf map a prefix table in the kernel arguments — the compute
 // type, the gradient clamp and the dtype combinations every update kernel is built for.
 #pragma once
 #include <stdexcept>
 #include <vector>
 
+#include "../api.h"
 #include "common.h"
 
 namespace fluxmpi {
@@ -38,6 +39,26 @@ template <typename C>
 __device__ __forceinline__ C clip_grad(C g, C delta) {
   if (delta > C(0)) g = g < -delta ? -delta : (g > delta ? delta : g);
   return g;
+}
+
+// sum over the workgroup, valid in every thread. Wave level: DPP (fp32) / xor shuffles (fp64), every
+// lane takes part (EXEC full); then the four wave totals through LDS, added in wave order. A second
+// call in one kernel needs a __syncthreads() in front: it writes the same LDS slots.
+template <typename A>
+__device__ __forceinline__ A block_sum(A v) {
+  __shared__ A wave_tot[kThreads / 64];
+  if constexpr (sizeof(A) == 4) {
+    v = wave_sum_dpp(v);
+  } else {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  A s = wave_tot[0];
+#pragma unroll
+  for (int w = 1; w < kThreads / 64; ++w) s += wave_tot[w];
+  return s;
 }
 
 template <typename F>
@@ -103,5 +124,14 @@ template <> constexpr int code_of<float>() { return kF32; }
 template <> constexpr int code_of<bf16>() { return kBF16; }
 template <> constexpr int code_of<f16>() { return kF16; }
 template <> constexpr int code_of<double>() { return kF64; }
+
+// The layer-wise rules (optim_layerwise.hip: kLars, kLamb) behind mt_rule's entry. s3 carries each
+// leaf's address in the partials workspace (2 entries per 4096-element chunk, in compute precision)
+// and RuleHyper::tscale is written: the trust ratio each leaf used. LARS: beta1 = rho, beta2 = trust.
+void mt_layerwise(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
+                  const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
+                  const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,
+                  const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, const RuleHyper& h,
+                  hipStream_t stream);
 
 }  // namespace fluxmpi

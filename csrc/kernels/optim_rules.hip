@@ -296,6 +296,8 @@ void mt_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
     RULE(kNAdam, NAdamRule)
     RULE(kAdaBelief, AdaBeliefRule)
     RULE(kAdaDelta, AdaDeltaRule)
+    case kLars:
+    case kLamb: mt_layerwise(param, grad, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, stream); break;
     default: throw std::runtime_error("mt_rule: unknown rule " + std::to_string(h.kind));
   }
 #undef RULE

@@ -20,7 +20,9 @@ ap.add_argument("--model", default="resnet50")
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--image", type=int, default=224)
 ap.add_argument("--steps", type=int, default=20)
-ap.add_argument("--lr", type=float, default=1e-3)
+ap.add_argument("--lr", type=float, default=None, help="default: 1e-3 (adamw, lamb), 0.1 (lars)")
+ap.add_argument("--opt", default="adamw", choices=["adamw", "lars", "lamb"],
+                help="lars / lamb: the layer-wise rules for large global batches")
 args = ap.parse_args()
 
 FluxMPI.Init()
@@ -33,7 +35,10 @@ if dev.type == "cuda":
         if not isinstance(m, (torch.nn.modules.batchnorm._BatchNorm, torch.nn.LayerNorm)):
             for p in m.parameters(recurse=False):
                 p.data = p.data.bfloat16()
-ddp = DDP(model, O.AdamW(args.lr, decay=1e-4), average=True)
+lr = args.lr if args.lr is not None else (0.1 if args.opt == "lars" else 1e-3)
+rule = {"adamw": lambda: O.AdamW(lr, decay=1e-4), "lars": lambda: O.LARS(lr, 0.9, trust=0.001, decay=1e-4),
+        "lamb": lambda: O.LAMB(lr, decay=0.01)}[args.opt]()
+ddp = DDP(model, rule, average=True)
 if FluxMPI.local_rank() == 0:
     print("buckets:", ddp.bucket_summary())
 
@@ -53,6 +58,9 @@ for step in range(args.steps):
         ddp.step()
     if step % 10 == 0:
         FluxMPI.fluxmpi_println(f"step {step} loss {loss.item():.4f}")
+        if args.opt != "adamw" and FluxMPI.local_rank() == 0:
+            q = torch.stack(list(ddp.trust_ratios().values())).float()
+            print(f"  trust ratios: min {q.min().item():.3g} median {q.median().item():.3g} max {q.max().item():.3g}")
 if FluxMPI.local_rank() == 0:
     print({k: round(v, 3) for k, v in timer.summary().items()}, "ms;",
           f"{args.steps * args.batch * FluxMPI.total_workers() / (time.time() - t0):.1f} samples/s")

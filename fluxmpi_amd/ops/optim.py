@@ -1,5 +1,6 @@
 """Fused multi-tensor optimiser steps (wrappers of ``csrc/kernels/optim.hip`` — Adam, the SGD
-family, sums of squares — and ``csrc/kernels/optim_rules.hip`` — the rest of the rule set).
+family, sums of squares — ``csrc/kernels/optim_rules.hip`` — the rest of the rule set — and
+``csrc/kernels/optim_layerwise.hip`` — LARS and LAMB).
 
 Each function updates many (param, grad, state...) tuples in one launch per
 dtype group. CPU tensors use the PyTorch reference math, which mirrors the
@@ -340,6 +341,185 @@ def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta
         p.copy_(x)
 
 
+# ---- layer-wise adaptive rules (csrc/kernels/optim_layerwise.hip) ---------------------------------
+LAYERWISE = {"lars": 8, "lamb": 9}  # codes of the kernel's rule switch, behind rule_'s entry
+
+
+def layerwise_workspace(params) -> int:
+    """Entries of the ``workspace`` :func:`lars_` / :func:`lamb_` need for ``params``: two per
+    4096-element chunk (the chunk's sums of squares of the parameter and of the gradient / update)."""
+    return 2 * sumsq_partials(params)
+
+
+def _layerwise_(kind, params, grads, states, hyper, *, weight_decay, grad_scale, masters, dev_hyper, dev_gscale,
+                ratios, workspace):
+    """The GPU side of :func:`lars_` / :func:`lamb_`: one ``mt_rule`` call per dtype group, each leaf's
+    slice of the workspace in the ``s3`` slot and the ratio table in ``tscale``."""
+    C = _ext.get(required=True)
+    dev = params[0].device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ns, nh = len(states), 3 if kind == "lamb" else 1
+    if dev_hyper is not None and (dev_hyper.dtype != torch.float32 or dev_hyper.numel() < nh
+                                  or not dev_hyper.is_contiguous()):
+        raise TypeError(f"fused {kind}: dev_hyper is a contiguous fp32 tensor of {nh} entries")
+    groups: dict = {}
+    for i, p in enumerate(params):
+        sd = states[0][i].dtype
+        if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
+                or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
+            raise TypeError(f"fused {kind}: leaf {i}: gradient, states and master must match the parameter's "
+                            "size (states of one dtype, fp32 master)")
+        groups.setdefault((p.dtype, grads[i].dtype, sd, masters is not None), []).append(i)
+    for (pd, gd, sd, hm), idx in groups.items():
+        if not supported(pd, gd, sd, hm):
+            raise TypeError(f"fused {kind}: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
+        at = _acc_dtype(pd)
+        need = layerwise_workspace([params[i] for i in idx])
+        ws = workspace
+        if ws is None or len(groups) > 1:
+            # allocated and consumed on the current stream: the allocator reuses it in stream order
+            ws = torch.empty(max(need, 1), dtype=at, device=dev)
+        elif ws.dtype != at or ws.numel() < need or not ws.is_contiguous() or ws.device != dev:
+            raise TypeError(f"fused {kind}: workspace must be a contiguous {at} tensor with at least {need} entries "
+                            f"on {dev} (layerwise_workspace)")
+        table = ratios
+        if table is None or idx != list(range(len(params))):
+            table = torch.empty(len(idx), dtype=at, device=dev)
+        elif table.dtype != at or table.numel() < len(idx) or not table.is_contiguous() or table.device != dev:
+            raise TypeError(f"fused {kind}: ratios must be a contiguous {at} tensor with {len(idx)} entries on {dev}")
+        part, off, esz = [], 0, ws.element_size()
+        for k, i in enumerate(idx):
+            part.append(ws.data_ptr() + off * esz)
+            off += 2 * ((params[i].numel() + 4095) // 4096)
+            if params[i].numel() == 0:
+                table[k:k + 1].fill_(1)  # a leaf without elements reaches no kernel: ratio 1
+        st = [[s[i].data_ptr() for i in idx] for s in states] + [[]] * (2 - ns)
+        C.mt_rule(LAYERWISE[kind], [params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx],
+                  st[0], st[1], part, [masters[i].data_ptr() for i in idx] if hm else [],
+                  [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
+                  float(hyper["lr"]), float(hyper["beta1"]), float(hyper["beta2"]), float(hyper["eps"]),
+                  float(hyper.get("bt1", 0.0)), float(hyper.get("bt2", 0.0)), float(weight_decay), float(grad_scale),
+                  dev_hyper.data_ptr() if dev_hyper is not None else 0,
+                  dev_gscale.data_ptr() if dev_gscale is not None else 0, table.data_ptr(), 0.0, stream)
+        if ratios is not None and table is not ratios:
+            ratios[torch.tensor(idx, device=dev)] = table.to(ratios.dtype)
+
+
+def _check_layerwise(kind, params, grads, states, masters, ratios):
+    if any(len(s) != len(params) for s in states) or len(grads) != len(params):
+        raise ValueError(f"fused {kind}: needs a gradient and {len(states)} state tensor(s) per parameter")
+    if masters is not None and len(masters) != len(params):
+        raise ValueError(f"fused {kind}: needs a master per parameter")
+    if ratios is not None and ratios.numel() < len(params):
+        raise ValueError(f"fused {kind}: ratios has {ratios.numel()} entries for {len(params)} leaves")
+
+
+def lars_(params, grads, bufs, *, lr: float, momentum: float, trust: float, weight_decay: float = 0.0,
+          eps: float = 0.0, grad_scale: float = 1.0, masters=None, dev_hyper: torch.Tensor | None = None,
+          dev_gscale: torch.Tensor | None = None, ratios: torch.Tensor | None = None,
+          workspace: torch.Tensor | None = None) -> None:
+    """In-place fused LARS over lists of tensors, every leaf adapted (``optim_layerwise.hip``):
+    ``q = trust·‖x‖ / (‖g‖ + wd·‖x‖ + eps)`` (1 when either norm is 0), ``vel = momentum·vel +
+    lr·q·(g + wd·x)``, ``x -= vel`` with ``g = grads[i] * grad_scale * dev_gscale`` and ``x`` the
+    fp32 master where there is one. Two launches per 24 leaves (three with a leaf above 16.8M
+    elements), deterministic norms, no host read.
+
+    ``dev_hyper``: fp32 ``[lr]`` on the device. ``ratios``: optional table (fp32; fp64 for fp64
+    parameters) that receives ``q`` of each leaf of ``params``. ``workspace``: scratch of
+    :func:`layerwise_workspace` entries of the same dtype, allocated here when not given."""
+    states = [list(bufs)]
+    _check_layerwise("lars", params, grads, states, masters, ratios)
+    if not params:
+        return
+    if params[0].is_cuda:
+        _layerwise_("lars", params, grads, states, {"lr": lr, "beta1": momentum, "beta2": trust, "eps": eps},
+                    weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, dev_hyper=dev_hyper,
+                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace)
+        return
+    if dev_hyper is not None:
+        lr = float(dev_hyper.reshape(-1)[0])
+    if dev_gscale is not None:
+        grad_scale = grad_scale * float(dev_gscale)
+    lars_reference_(params, grads, bufs, lr=lr, momentum=momentum, trust=trust, weight_decay=weight_decay, eps=eps,
+                    grad_scale=grad_scale, masters=masters, ratios=ratios)
+
+
+def lamb_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
+          bt1: float, bt2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
+          dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
+          ratios: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> None:
+    """In-place fused LAMB over lists of tensors, every leaf adapted (``optim_layerwise.hip``):
+    Adam's ``m`` and ``v``, ``u = m/(1-bt1) / (sqrt(v/(1-bt2)) + eps) + wd·x``, ``q = ‖x‖/‖u‖`` (1
+    when either norm is 0), ``x -= lr·q·u``. ``bt1`` / ``bt2`` are ``beta^t``; ``dev_hyper`` (fp32
+    ``[lr, beta1^t, beta2^t]``) overrides them and ``lr``, advanced by :func:`adam_advance_`. The
+    other arguments are :func:`lars_`'s. ``u`` is never written to memory: the second phase forms it
+    again from the stored ``m`` and ``v``."""
+    states = [list(exp_avgs), list(exp_avg_sqs)]
+    _check_layerwise("lamb", params, grads, states, masters, ratios)
+    if not params:
+        return
+    if params[0].is_cuda:
+        _layerwise_("lamb", params, grads, states,
+                    {"lr": lr, "beta1": beta1, "beta2": beta2, "eps": eps, "bt1": bt1, "bt2": bt2},
+                    weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, dev_hyper=dev_hyper,
+                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace)
+        return
+    if dev_hyper is not None:
+        h = dev_hyper.tolist()
+        lr, bt1, bt2 = h[0], h[1], h[2]
+    if dev_gscale is not None:
+        grad_scale = grad_scale * float(dev_gscale)
+    lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
+                    weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, ratios=ratios)
+
+
+def _norm(t: torch.Tensor) -> torch.Tensor:
+    return torch.sqrt((t * t).sum())
+
+
+def lars_reference_(params, grads, bufs, *, lr, momentum, trust, weight_decay=0.0, eps=0.0, grad_scale=1.0,
+                    masters=None, ratios=None):
+    """PyTorch reference of :func:`lars_` (compute in fp32, or fp64 for fp64 params)."""
+    for i, p in enumerate(params):
+        ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        x = masters[i].to(ct) if masters is not None else p.to(ct)
+        g = grads[i].to(ct) * grad_scale
+        xn, gn = _norm(x), _norm(g)
+        q = torch.where((xn > 0) & (gn > 0), trust * xn / (gn + weight_decay * xn + eps), torch.ones_like(xn))
+        d = g + weight_decay * x if weight_decay else g
+        vel = momentum * bufs[i].to(ct) + lr * (q * d)
+        bufs[i].copy_(vel)
+        x = x - vel
+        if ratios is not None:
+            ratios[i] = q
+        if masters is not None:
+            masters[i].copy_(x)
+        p.copy_(x)
+
+
+def lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps, bt1, bt2, weight_decay=0.0,
+                    grad_scale=1.0, masters=None, ratios=None):
+    """PyTorch reference of :func:`lamb_` (compute in fp32, or fp64 for fp64 params): ``u`` is formed
+    from the moments as stored, in the state's dtype."""
+    for i, p in enumerate(params):
+        ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        x = masters[i].to(ct) if masters is not None else p.to(ct)
+        g = grads[i].to(ct) * grad_scale
+        exp_avgs[i].copy_(exp_avgs[i].to(ct) * beta1 + (1 - beta1) * g)
+        exp_avg_sqs[i].copy_(exp_avg_sqs[i].to(ct) * beta2 + (1 - beta2) * (g * g))
+        u = exp_avgs[i].to(ct) / (1 - bt1) / (torch.sqrt(exp_avg_sqs[i].to(ct) / (1 - bt2)) + eps)
+        if weight_decay:
+            u = u + weight_decay * x
+        xn, un = _norm(x), _norm(u)
+        q = torch.where((xn > 0) & (un > 0), xn / un, torch.ones_like(xn))
+        x = x - (lr * q) * u
+        if ratios is not None:
+            ratios[i] = q
+        if masters is not None:
+            masters[i].copy_(x)
+        p.copy_(x)
+
+
 def sumsq_partials(grads) -> int:
     """Entries of the ``partials`` workspace :func:`sumsq_` needs for ``grads`` (one per 4096-element chunk)."""
     return sum((g.numel() + 4095) // 4096 for g in grads)
@@ -422,4 +602,5 @@ def bias_corrections(beta1_t: float, beta2_t: float) -> tuple[float, float]:
 
 __all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_", "supported", "bias_corrections",
            "rule_", "rule_reference_", "RULES",
+           "lars_", "lamb_", "lars_reference_", "lamb_reference_", "layerwise_workspace", "LAYERWISE",
            "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_"]

@@ -21,6 +21,8 @@ NAdam(η,β,ϵ)   ``(m, v, βᵗ)``                                   ``(β1·m/
                                                                 ``/(sqrt(v·β2/(1-β2ᵗ))+ϵ)·η``
 AdaBelief(η,β,ϵ) ``(m, s, βᵗ)``, ``s = β2·s+(1-β2)·(dx-m)²+ϵ``  ``η·m/(1-β1ᵗ)/(sqrt(s/(1-β2ᵗ))+ϵ)``
 AdaDelta(ρ,ϵ)  ``(acc, Δ)``, ``Δ = ρ·Δ + (1-ρ)·dx'²``           ``dx·sqrt(Δ+ϵ)/sqrt(acc+ϵ)``
+LARS(η,ρ,trust,decay,ϵ) ``vel``; q = trust·‖x‖/(‖dx‖+decay·‖x‖+ϵ)   ``vel = ρ·vel + η·q·(dx + decay·x)``
+LAMB(η,β,ϵ,decay) Adam's; u = Adam's dx'/η + decay·x            ``η·‖x‖/‖u‖·u`` (1-D leaves: Momentum / Adam)
 WeightDecay(γ) ``None``                                         ``dx + γ·x``
 ClipGrad(δ)    ``None``                                         ``clamp(dx, -δ, δ)``
 ClipNorm(ω,p)  ``None``                                         ``dx · min(1, ω/‖dx‖ₚ)``
@@ -456,6 +458,138 @@ def _same_dense(*ts) -> bool:
     return all(t.shape == t0.shape and t.stride() == t0.stride() for t in ts[1:])
 
 
+def _leaf_norm(t: torch.Tensor) -> torch.Tensor:
+    """L2 norm over the leaf in compute precision (fp32 for bf16 / fp16 leaves)."""
+    t = t.float() if t.dtype in (torch.bfloat16, torch.float16) else t
+    return torch.sqrt((t * t).sum())
+
+
+class _LayerwiseRule(AbstractRule):
+    """Shared by LARS and LAMB: a leaf with ``x.ndim <= 1`` (biases, norm scales and shifts) is
+    neither decayed nor adapted unless ``adapt_1d`` — it takes the base rule (Momentum / Adam) — and
+    the adapted GPU leaves take the fused two-phase kernels of ``ops.optim``."""
+
+    adapt_1d = False
+
+    def _adapts(self, x) -> bool:
+        return self.adapt_1d or x.ndim > 1
+
+    def _fused_ok(self, leaf, x, dx) -> bool:
+        raise NotImplementedError
+
+    def _base_batch(self, items) -> list:
+        raise NotImplementedError
+
+    def _fused(self, x0, idx, items) -> None:
+        raise NotImplementedError
+
+    def apply_batch(self, items):
+        out: list = [None] * len(items)
+        base = [i for i, (_, x, _) in enumerate(items) if not self._adapts(x)]
+        for i, d in zip(base, self._base_batch([items[i] for i in base]) if base else []):
+            out[i] = d
+        fused: dict = {}
+        for i, (leaf, x, dx) in enumerate(items):
+            if not self._adapts(x):
+                continue
+            if x.is_cuda and dx is not None and self._fused_ok(leaf, x, dx):
+                fused.setdefault(self._key(leaf, x, dx), []).append(i)
+            else:
+                leaf.state, out[i] = self.apply(leaf.state, x, dx)
+        for idx in fused.values():
+            self._fused(items[idx[0]][1], idx, items)
+        return out
+
+
+class LARS(_LayerwiseRule):
+    """``LARS(η=0.1, ρ=0.9, trust=0.001, decay=0, ϵ=0)`` (You et al. 2017); state ``vel``, Momentum's.
+    ``q = trust·‖x‖ / (‖dx‖ + decay·‖x‖ + ϵ)`` (1 when either norm is 0), ``vel = ρ·vel +
+    η·q·(dx + decay·x)``, ``dx' = vel``."""
+
+    def __init__(self, eta: float = 0.1, rho: float = 0.9, trust: float = 0.001, decay: float = 0.0,
+                 epsilon: float = 0.0, adapt_1d: bool = False):
+        self.eta, self.rho, self.trust, self.decay, self.epsilon, self.adapt_1d = eta, rho, trust, decay, epsilon, adapt_1d
+
+    def init(self, x):
+        return torch.zeros_like(x)
+
+    def apply(self, vel, x, dx):
+        if not self._adapts(x):
+            return Momentum.apply(self, vel, x, dx)
+        eta, rho, trust = _T(x, self.eta), _T(x, self.rho), _T(x, self.trust)
+        decay, eps = _T(x, self.decay), _eps(x, self.epsilon)
+        xn, gn = _leaf_norm(x), _leaf_norm(dx)
+        q = torch.where((xn > 0) & (gn > 0), trust * xn / (gn + decay * xn + eps), torch.ones_like(xn)).to(x.dtype)
+        d = dx + decay * x if decay else dx
+        vel.mul_(rho).add_(q * d, alpha=eta)
+        return vel, vel
+
+    def _fused_ok(self, leaf, x, dx):
+        return (isinstance(leaf.state, torch.Tensor) and _same_dense(x, dx, leaf.state)
+                and _fused.supported(x.dtype, dx.dtype, leaf.state.dtype, False))
+
+    def _key(self, leaf, x, dx):
+        return (x.device, x.dtype, dx.dtype)
+
+    def _base_batch(self, items):
+        return _sgd_batch(self, items, self.rho, False)
+
+    def _fused(self, x0, idx, items):
+        _fused.lars_([items[i][1] for i in idx], [items[i][2] for i in idx], [items[i][0].state for i in idx],
+                     lr=_T(x0, self.eta), momentum=_T(x0, self.rho), trust=_T(x0, self.trust),
+                     weight_decay=_T(x0, self.decay), eps=_eps(x0, self.epsilon))
+
+
+class LAMB(_LayerwiseRule):
+    """``LAMB(η=0.001, β=(0.9, 0.999), ϵ=1e-6, decay=0.01)`` (You et al. 2020); state ``(mt, vt, βt)``,
+    Adam's. ``u = mt/(1-β1ᵗ)/(sqrt(vt/(1-β2ᵗ))+ϵ) + decay·x``, ``q = ‖x‖/‖u‖`` (1 when either norm is
+    0), ``dx' = η·q·u``."""
+
+    def __init__(self, eta: float = 0.001, beta: tuple = (0.9, 0.999), epsilon: float = 1e-6, decay: float = 0.01,
+                 adapt_1d: bool = False):
+        self.eta, self.beta, self.epsilon, self.decay, self.adapt_1d = eta, tuple(beta), epsilon, decay, adapt_1d
+
+    def init(self, x):
+        return (torch.zeros_like(x), torch.zeros_like(x), (_T(x, self.beta[0]), _T(x, self.beta[1])))
+
+    def apply(self, state, x, dx):
+        if not self._adapts(x):
+            return Adam.apply(self, state, x, dx)
+        eta, b1, b2, eps = _T(x, self.eta), _T(x, self.beta[0]), _T(x, self.beta[1]), _eps(x, self.epsilon)
+        decay = _T(x, self.decay)
+        mt, vt, bt = state
+        mt.mul_(b1).add_(dx, alpha=1 - b1)
+        vt.mul_(b2).addcmul_(dx, dx, value=1 - b2)
+        u = mt / (1 - bt[0]) / (torch.sqrt(vt / (1 - bt[1])) + eps)
+        if decay:
+            u = u + decay * x
+        xn, un = _leaf_norm(x), _leaf_norm(u)
+        q = torch.where((xn > 0) & (un > 0), xn / un, torch.ones_like(xn)).to(x.dtype)
+        return (mt, vt, (_T(x, bt[0] * b1), _T(x, bt[1] * b2))), (eta * q) * u
+
+    def _fused_ok(self, leaf, x, dx):
+        st = leaf.state
+        return (isinstance(st, tuple) and len(st) == 3 and _same_dense(x, dx, st[0], st[1])
+                and st[0].dtype == st[1].dtype and _fused.supported(x.dtype, dx.dtype, st[0].dtype, False))
+
+    def _key(self, leaf, x, dx):
+        return (x.device, x.dtype, dx.dtype, tuple(leaf.state[2]))  # same precision and beta^t -> one call
+
+    def _base_batch(self, items):
+        return _adam_batch(self, items, 0.0)
+
+    def _fused(self, x0, idx, items):
+        bt = items[idx[0]][0].state[2]
+        b1, b2 = _T(x0, self.beta[0]), _T(x0, self.beta[1])
+        _fused.lamb_([items[i][1] for i in idx], [items[i][2] for i in idx], [items[i][0].state[0] for i in idx],
+                     [items[i][0].state[1] for i in idx], lr=_T(x0, self.eta), beta1=b1, beta2=b2,
+                     eps=_eps(x0, self.epsilon), bt1=bt[0], bt2=bt[1], weight_decay=_T(x0, self.decay))
+        for i in idx:
+            leaf, x = items[i][0], items[i][1]
+            m, v, t = leaf.state
+            leaf.state = (m, v, (_T(x, t[0] * b1), _T(x, t[1] * b2)))
+
+
 def _adam_batch(rule: Adam, items, weight_decay: float, clip=None):
     """Fused multi-tensor Adam on GPU leaves (x updated in place, dx' = None). ``clip``: the
     chain's leading clip rule, fused into the update on the GPU leaves (per-leaf elsewhere)."""
@@ -883,7 +1017,7 @@ def _leaves_of(tree):
 
 __all__ = [
     "AbstractRule", "Leaf", "Descent", "Momentum", "Nesterov", "RMSProp", "AdaGrad", "Adam", "AdamW",
-    "Lion", "AdaMax", "AMSGrad", "NAdam", "AdaBelief", "AdaDelta",
+    "Lion", "AdaMax", "AMSGrad", "NAdam", "AdaBelief", "AdaDelta", "LARS", "LAMB",
     "WeightDecay", "ClipGrad", "ClipNorm", "OptimiserChain", "OptimizerChain", "setup", "update", "update_",
     "update_inplace", "freeze_", "thaw_", "adjust_",
 ]

@@ -101,6 +101,10 @@ class _Bucket:
     applied: bool = False  # overlap_opt: this step's update already enqueued (during backward)
     clip: torch.Tensor | None = None  # gradient clipping: [2, leaves] per-leaf sums of squares / scales
     partials: torch.Tensor | None = None  # ... and the sum-of-squares kernel's per-workgroup partials
+    adapted: list = field(default_factory=list)  # LARS / LAMB: positions of the leaves that take the trust ratio
+    plain: list = field(default_factory=list)    # ... and of the 1-D leaves that take Momentum / Adam
+    ratios: torch.Tensor | None = None     # ... the adapted leaves' trust ratios (a slice of the dtype's table)
+    lw_work: torch.Tensor | None = None    # ... and the layer-wise kernels' norm partials
 
 
 def _strided_view(flat: torch.Tensor, like: torch.Tensor, offset: int) -> torch.Tensor:
@@ -134,7 +138,9 @@ class DDP:
     module: the model (already on its device, in its compute dtype/memory format).
     rule:   an ``optimisers`` rule (Adam, Descent, Momentum, Nesterov, RMSProp, AdaGrad, Lion, AdaMax,
             AMSGrad, NAdam, AdaBelief, AdaDelta; all but the SGD family also in a chain with
-            WeightDecay, as AdamW is), optionally
+            WeightDecay, as AdamW is; or the layer-wise LARS / LAMB, on their own: their decay is
+            the rule's, their updates always run leaf by leaf and :meth:`trust_ratios` shows the
+            ratios), optionally
             behind a clip: ``OptimiserChain(ClipNorm(omega), rule)`` (per-leaf L2 norm) or
             ``OptimiserChain(ClipGrad(delta), rule)``; the engine runs it with fused flat-buffer
             kernels (the clip inside the update kernel, the norms from a deterministic
@@ -390,6 +396,10 @@ class DDP:
             self.kind, self.adam = "adam", r
         elif isinstance(r, O._KernelRule):
             self.kind = r._kind
+        elif isinstance(r, O.LARS):
+            self.kind = "lars"
+        elif isinstance(r, O.LAMB):
+            self.kind = "lamb"
         elif isinstance(r, O.Nesterov):
             self.kind = "nesterov"
         elif isinstance(r, O.Momentum):
@@ -399,7 +409,11 @@ class DDP:
         else:
             raise TypeError(f"DDP: no fused kernel for rule {r!r}; use the functional optimisers API")
         # the kernel rules of ops.optim.rule_: state buffers per bucket, and whether beta^t is kept
-        _, self._nstate, self._has_bt = fused.RULES.get(self.kind, (None, 0, self.kind == "adam"))
+        _, self._nstate, self._has_bt = fused.RULES.get(self.kind, (None, 0, self.kind in ("adam", "lamb")))
+        self._layerwise = self.kind in fused.LAYERWISE
+        if self.kind == "lars" and self.clip_global_norm is not None:
+            raise ValueError("DDP: LARS rescales every leaf's gradient by its own norm, which undoes a global "
+                             "clip: drop clip_global_norm (LAMB takes it)")
         dev = self.device
         for b in self.buckets:
             low = b.dtype in (torch.bfloat16, torch.float16)
@@ -407,10 +421,10 @@ class DDP:
             sdt = torch.float32 if use_master else b.dtype
             if use_master:
                 b.master = b.flat_param.float()
-            if self.kind == "adam":
+            if self.kind in ("adam", "lamb"):
                 b.exp_avg = torch.zeros(b.numel, dtype=sdt, device=dev)
                 b.exp_avg_sq = torch.zeros(b.numel, dtype=sdt, device=dev)
-            elif self.kind in ("momentum", "nesterov"):
+            elif self.kind in ("momentum", "nesterov", "lars"):
                 b.exp_avg = torch.zeros(b.numel, dtype=sdt, device=dev)
             elif self._nstate:
                 # AdaGrad's and AMSGrad's states start at epsilon (Optimisers.jl init), the rest at 0
@@ -436,6 +450,23 @@ class DDP:
                     b.clip, b.partials = buf[:, off:off + k], parts[poff:poff + kp]
                     off, poff = off + k, poff + kp
                 self._clip_groups.append((bs, buf, parts))
+        # layer-wise rules: each bucket's leaves split once into adapted and 1-D ones, and per bucket
+        # dtype one table of trust ratios and one workspace of norm partials, a slice per bucket
+        if self._layerwise:
+            by_dtype = {}
+            for b in self.buckets:
+                b.adapted = [i for i, p in enumerate(b.params) if r._adapts(p)]
+                b.plain = [i for i, p in enumerate(b.params) if not r._adapts(p)]
+                by_dtype.setdefault(b.dtype, []).append(b)
+            for dt, bs in by_dtype.items():
+                at = torch.float64 if dt == torch.float64 else torch.float32
+                need = [fused.layerwise_workspace([b.params[i] for i in b.adapted]) for b in bs]
+                table = torch.ones(sum(len(b.adapted) for b in bs), dtype=at, device=dev)
+                work = torch.zeros(sum(need), dtype=at, device=dev)
+                off = woff = 0
+                for b, kw in zip(bs, need):
+                    b.ratios, b.lw_work = table[off:off + len(b.adapted)], work[woff:woff + kw]
+                    off, woff = off + len(b.adapted), woff + kw
         # [sum of squares, norm, global clip scale] of the step's whole gradient (device, fp32)
         self._clip_slot = torch.zeros(3, dtype=torch.float32, device=dev) if self._norms else None
         if self._has_bt:
@@ -893,7 +924,9 @@ class DDP:
             kw["tscale"] = b.clip[1]
         if self.clip_global_norm is not None:
             kw["dev_gscale"] = self._clip_slot[2:3]
-        if self.kind == "adam":
+        if self._layerwise:
+            self._run_layerwise(st, gs, gscale, b, kw)
+        elif self.kind == "adam":
             a = self.adam
             fused.adam_(ps, gs, ms, vs, lr=a.eta, beta1=a.beta[0], beta2=a.beta[1], eps=a.epsilon, bc1=0.0,
                         bc2=0.0, weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_hyper=self.hyper, **kw)
@@ -904,6 +937,32 @@ class DDP:
             mom = {"descent": 0.0}.get(self.kind, getattr(self._upd, "rho", 0.0))
             fused.sgd_(ps, gs, ms, lr=self._upd.eta, momentum=mom, nesterov=self.kind == "nesterov",
                        weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_lr=self.hyper, **kw)
+
+    def _run_layerwise(self, st: tuple, gs: list, gscale: float, b: _Bucket, kw: dict):
+        """LARS / LAMB over the bucket's per-leaf lists: the two-phase kernels on the adapted leaves,
+        Momentum's / Adam's kernel (no decay, the same device hyper block) on the 1-D ones."""
+        ps, ms, vs, ws, _ = st
+        r = self._inner
+        for idx, adapt in ((b.adapted, True), (b.plain, False)):
+            if not idx:
+                continue
+            pick = lambda l: [l[i] for i in idx] if l is not None else None  # noqa: E731
+            p, g, m, v, w = pick(ps), pick(gs), pick(ms), pick(vs), pick(ws)
+            if self.kind == "lars":
+                if adapt:
+                    fused.lars_(p, g, m, lr=r.eta, momentum=r.rho, trust=r.trust, weight_decay=r.decay,
+                                eps=r.epsilon, grad_scale=gscale, masters=w, dev_hyper=self.hyper,
+                                ratios=b.ratios, workspace=b.lw_work, **kw)
+                else:
+                    fused.sgd_(p, g, m, lr=r.eta, momentum=r.rho, grad_scale=gscale, masters=w, dev_lr=self.hyper,
+                               **kw)
+            elif adapt:
+                fused.lamb_(p, g, m, v, lr=r.eta, beta1=r.beta[0], beta2=r.beta[1], eps=r.epsilon, bt1=0.0, bt2=0.0,
+                            weight_decay=r.decay, grad_scale=gscale, masters=w, dev_hyper=self.hyper,
+                            ratios=b.ratios, workspace=b.lw_work, **kw)
+            else:
+                fused.adam_(p, g, m, v, lr=r.eta, beta1=r.beta[0], beta2=r.beta[1], eps=r.epsilon, bc1=0.0, bc2=0.0,
+                            grad_scale=gscale, masters=w, dev_hyper=self.hyper, **kw)
 
     def _enqueue_norms(self, gs: list, buf: torch.Tensor, parts: torch.Tensor, gscale: float):
         """Per-leaf sums of squares of ``gs`` into ``buf[0]`` (two deterministic launches per 24
@@ -929,7 +988,7 @@ class DDP:
         self._run_update(st, gs, gscale, b)
 
     def _apply(self, b: _Bucket, gscale: float):
-        if self._norms:
+        if self._norms or self._layerwise:
             # per-leaf norms: the update reads the flat bucket leaf by leaf (as _apply_direct does)
             self._update(b, self._slices(b), [v.as_strided((v.numel(),), (1,)) for _, v, _ in self._grad_views(b)],
                          gscale)
@@ -964,6 +1023,15 @@ class DDP:
             raise RuntimeError("DDP.grad_norm: the engine computes gradient norms only when it clips by one: "
                                "use an OptimiserChain(ClipNorm(omega), rule) or clip_global_norm=...")
         return self._clip_slot[1]
+
+    def trust_ratios(self) -> dict:
+        """``{name: ratio}`` of the last step's trust ratios under LARS / LAMB: 0-dim device tensors
+        (fp32; fp64 for fp64 parameters), views of the engine's tables, so they follow later steps.
+        The 1-D leaves, which are not adapted, are absent. Never synchronises (read it after
+        ``step()``, on the stream ``step()`` ran on)."""
+        if not self._layerwise:
+            raise RuntimeError("DDP.trust_ratios: only the layer-wise rules (LARS, LAMB) have trust ratios")
+        return {b.names[i]: b.ratios[k] for b in self.buckets for k, i in enumerate(b.adapted)}
 
     def set_lr(self, lr: float):
         """Change the learning rate (device-side, so captured graphs see it)."""
