@@ -60,11 +60,8 @@ struct AdamElem {
 template <typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper h) {
   using C = typename Comp<P>::type;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t;
 
   AdamElem<P, G, S, MASTER> op;
   C lr = h.lr, bc1 = h.bc1, bc2 = h.bc2;
@@ -86,14 +83,14 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
   float* __restrict__ w = reinterpret_cast<float*>(a.w[t]);
   const int tid = threadIdx.x;
   const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!MASTER || aligned16(w));
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (vec) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
-        const int64_t off = base + vi * kVec;
+        const int64_t off = ch.base + vi * kVec;
         P pv[kVec]; G gv[kVec]; S mv[kVec]; S vv[kVec]; float wv[kVec];
         load8(g + off, gv);
         load8(m + off, mv);
@@ -107,9 +104,9 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
         store8(p + off, pv);
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     P pv = p[i];
     S mv = m[i], vv = v[i];
     float wv = MASTER ? w[i] : 0.f;
@@ -150,11 +147,8 @@ struct SgdElem {
 template <typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h) {
   using C = typename Comp<P>::type;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t;
   SgdElem<P, G, S, MASTER> op;
   op.lr = h.dev_lr ? *h.dev_lr : h.lr;
   op.rho = h.momentum; op.wd = h.weight_decay;
@@ -169,14 +163,14 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
   const bool has_buf = op.mode != 0;
   const int tid = threadIdx.x;
   const bool vec = aligned16(p) && aligned16(g) && (!has_buf || aligned16(buf)) && (!MASTER || aligned16(w));
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (vec) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
-        const int64_t off = base + vi * kVec;
+        const int64_t off = ch.base + vi * kVec;
         P pv[kVec]; G gv[kVec]; S bv[kVec]; float wv[kVec];
         load8(g + off, gv);
         if (has_buf) load8(buf + off, bv);
@@ -188,9 +182,9 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
         store8(p + off, pv);
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     P pv = p[i];
     S bv = has_buf ? buf[i] : S(0);
     float wv = MASTER ? w[i] : 0.f;
@@ -206,23 +200,20 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
 template <typename G>
 __global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, typename Acc<G>::type* __restrict__ partials) {
   using A = typename Acc<G>::type;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t;
   const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
   const int tid = threadIdx.x;
   A acc = A(0);
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (aligned16(g)) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
         G gv[kVec];
-        load8(g + base + vi * kVec, gv);
+        load8(g + ch.base + vi * kVec, gv);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
           const A x = static_cast<A>(gv[j]);
@@ -230,14 +221,14 @@ __global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, t
         }
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     const A x = static_cast<A>(g[i]);
     acc += x * x;
   }
   const A s = block_sum(acc);
-  if (tid == 0) partials[a.pbase + b] = s;
+  if (tid == 0) partials[a.pbase + static_cast<int>(blockIdx.x)] = s;
 }
 
 // torch.clamp(omega / nrm, max=1): nrm 0 -> 1, nrm NaN -> NaN, nrm inf -> 0
@@ -299,19 +290,10 @@ void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
   const bool has_master = !master.empty();
   if (m.size() != numel.size() || v.size() != numel.size()) throw std::runtime_error("mt_adam: need m and v");
   for_each_group(param, grad, m, v, {}, master, numel, [&](const OptArgs& a, int blocks) {
-    bool done = false;
-#define X(P, G, S, M)                                                                            \
-  if (!done && p_dtype == code_of<P>() && g_dtype == code_of<G>() && s_dtype == code_of<S>() && \
-      has_master == M) {                                                                         \
-    mt_adam_kernel<P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);                           \
-    done = true;                                                                                 \
-  }
-    OPT_DTYPE_COMBOS(X)
-#undef X
-    if (!done)
-      throw std::runtime_error("mt_adam: unsupported dtype combination p=" + std::to_string(p_dtype) +
-                               " g=" + std::to_string(g_dtype) + " s=" + std::to_string(s_dtype) +
-                               " master=" + std::to_string(has_master));
+    dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_adam", [&](auto p, auto g, auto s, auto master) {
+      mt_adam_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                     decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }
@@ -329,16 +311,10 @@ void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& g
   if (h.momentum != 0.f && buf.size() != numel.size())
     throw std::runtime_error("mt_sgd: momentum needs buffers");
   for_each_group(param, grad, buf, {}, {}, master, numel, [&](const OptArgs& a, int blocks) {
-    bool done = false;
-#define X(P, G, S, M)                                                                            \
-  if (!done && p_dtype == code_of<P>() && g_dtype == code_of<G>() && s_dtype == code_of<S>() && \
-      has_master == M) {                                                                         \
-    mt_sgd_kernel<P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);                            \
-    done = true;                                                                                 \
-  }
-    OPT_DTYPE_COMBOS(X)
-#undef X
-    if (!done) throw std::runtime_error("mt_sgd: unsupported dtype combination");
+    dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_sgd", [&](auto p, auto g, auto s, auto master) {
+      mt_sgd_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                    decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }

@@ -1,9 +1,12 @@
 // Shared by the fused multi-tensor optimiser kernels (optim.hip: Adam, SGD, sums of squares;
 // optim_rules.hip: the rest of the rule set; optim_layerwise.hip: LARS, LAMB): the job layout — 4096-element chunks of up to 24
-// leaves per launch, the chunk -> leaf map a prefix table in the kernel arguments — the compute
-// type, the gradient clamp and the dtype combinations every update kernel is built for.
+// leaves per launch, the chunk -> leaf map a prefix table in the kernel arguments — and the one
+// copy of what the kernels have in common: chunk_of (which chunk a workgroup owns), block_sum /
+// block_sum2, the compute type, the gradient clamp and dispatch_opt_combo (the dtype combinations
+// every update kernel is built for).
 #pragma once
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../api.h"
@@ -41,6 +44,21 @@ __device__ __forceinline__ C clip_grad(C g, C delta) {
   return g;
 }
 
+// This workgroup's job: chunk c of the nb chunks of leaf t, elements [base, end) of the leaf.
+struct Chunk {
+  int t, c, nb;
+  int64_t base, end;
+};
+
+__device__ __forceinline__ Chunk chunk_of(const OptArgs& a) {
+  const int b = blockIdx.x;
+  const int t = find_tensor(a.start, a.n, b);
+  const int c = b - a.start[t];
+  const int64_t base = static_cast<int64_t>(c) * kChunk;
+  const int64_t n = a.numel[t];
+  return {t, c, a.start[t + 1] - a.start[t], base, base + kChunk < n ? base + kChunk : n};
+}
+
 // sum over the workgroup, valid in every thread. Wave level: DPP (fp32) / xor shuffles (fp64), every
 // lane takes part (EXEC full); then the four wave totals through LDS, added in wave order. A second
 // call in one kernel needs a __syncthreads() in front: it writes the same LDS slots.
@@ -59,6 +77,14 @@ __device__ __forceinline__ A block_sum(A v) {
 #pragma unroll
   for (int w = 1; w < kThreads / 64; ++w) s += wave_tot[w];
   return s;
+}
+
+// two sums over the workgroup, each valid in every thread
+template <typename A>
+__device__ __forceinline__ void block_sum2(A ax, A ay, A& sx, A& sy) {
+  sx = block_sum(ax);
+  __syncthreads();  // block_sum's LDS slots are about to be written again
+  sy = block_sum(ay);
 }
 
 template <typename F>
@@ -105,25 +131,40 @@ void for_each_group(const std::vector<uintptr_t>& p, const std::vector<uintptr_t
   flush();
 }
 
-// (parameter, gradient, state, fp32 master) combinations of the update kernels
-#define OPT_DTYPE_COMBOS(X)            \
-  X(float, float, float, false)          \
-  X(float, bf16, float, false)           \
-  X(bf16, bf16, bf16, false)             \
-  X(bf16, bf16, float, false)            \
-  X(bf16, bf16, float, true)             \
-  X(bf16, float, float, true)            \
-  X(f16, f16, f16, false)                \
-  X(f16, f16, float, false)              \
-  X(f16, f16, float, true)               \
-  X(f16, float, float, true)             \
-  X(double, double, double, false)
-
 template <typename T> constexpr int code_of();
 template <> constexpr int code_of<float>() { return kF32; }
 template <> constexpr int code_of<bf16>() { return kBF16; }
 template <> constexpr int code_of<f16>() { return kF16; }
 template <> constexpr int code_of<double>() { return kF64; }
+
+// (parameter, gradient, state, fp32 master) combinations of the update kernels
+#define OPT_DTYPE_COMBOS(COMBO)            \
+  COMBO(float, float, float, false)        \
+  COMBO(float, bf16, float, false)         \
+  COMBO(bf16, bf16, bf16, false)           \
+  COMBO(bf16, bf16, float, false)          \
+  COMBO(bf16, bf16, float, true)           \
+  COMBO(bf16, float, float, true)          \
+  COMBO(f16, f16, f16, false)              \
+  COMBO(f16, f16, float, false)            \
+  COMBO(f16, f16, float, true)             \
+  COMBO(f16, float, float, true)           \
+  COMBO(double, double, double, false)
+
+// Runtime dtype codes -> one of the combinations above, in the style of common.h's dispatchers:
+// f(TypeTag<P>, TypeTag<G>, TypeTag<S>, std::bool_constant<MASTER>) names the launch once. Any
+// other combination throws "<what>: unsupported dtype combination p= g= s= master=".
+template <typename F>
+void dispatch_opt_combo(int p_dtype, int g_dtype, int s_dtype, bool has_master, const char* what, F&& f) {
+#define X(P, G, S, M)                                                                                     \
+  if (p_dtype == code_of<P>() && g_dtype == code_of<G>() && s_dtype == code_of<S>() && has_master == M) \
+    return f(TypeTag<P>{}, TypeTag<G>{}, TypeTag<S>{}, std::bool_constant<M>{});
+  OPT_DTYPE_COMBOS(X)
+#undef X
+  throw std::runtime_error(std::string(what) + ": unsupported dtype combination p=" + std::to_string(p_dtype) +
+                           " g=" + std::to_string(g_dtype) + " s=" + std::to_string(s_dtype) +
+                           " master=" + std::to_string(has_master));
+}
 
 // The layer-wise rules (optim_layerwise.hip: kLars, kLamb) behind mt_rule's entry. s3 carries each
 // leaf's address in the partials workspace (2 entries per 4096-element chunk, in compute precision)

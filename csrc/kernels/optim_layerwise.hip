@@ -91,21 +91,14 @@ __device__ __forceinline__ void lw_fold(const A* __restrict__ part, int nb, A& s
     ax += part[j];
     ay += part[nb + j];
   }
-  sx = block_sum(ax);
-  __syncthreads();  // block_sum's LDS slots are about to be written again
-  sy = block_sum(ay);
+  block_sum2(ax, ay, sx, sy);
 }
 
 template <bool LAMB, typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper h) {
   using C = typename Comp<P>::type;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int c = b - a.start[t];
-  const int nb = a.start[t + 1] - a.start[t];
-  const int64_t base = static_cast<int64_t>(c) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t, c = ch.c, nb = ch.nb;
   const LwScalars<C> s = lw_scalars<C>(h, LAMB);
 
   const P* __restrict__ p = reinterpret_cast<const P*>(a.p[t]);
@@ -132,14 +125,14 @@ __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper
   };
 
   const bool vec = aligned16(g) && (MASTER ? aligned16(w) : aligned16(p)) && (!LAMB || (aligned16(m) && aligned16(v)));
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (vec) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
-        const int64_t off = base + vi * kVec;
+        const int64_t off = ch.base + vi * kVec;
         P pv[kVec]; G gv[kVec]; S mv[kVec]; S vv[kVec]; float wv[kVec];
         load8(g + off, gv);
         if (LAMB) { load8(m + off, mv); load8(v + off, vv); }
@@ -150,16 +143,15 @@ __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper
         if (LAMB) { store8(m + off, mv); store8(v + off, vv); }
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     S mv = LAMB ? m[i] : S(0), vv = LAMB ? v[i] : S(0);
     elem(MASTER ? static_cast<C>(w[i]) : static_cast<C>(p[i]), g[i], mv, vv);
     if (LAMB) { m[i] = mv; v[i] = vv; }
   }
-  const C sx = block_sum(ax);
-  __syncthreads();  // block_sum's LDS slots are about to be written again
-  const C sy = block_sum(ay);
+  C sx, sy;
+  block_sum2(ax, ay, sx, sy);
   if (tid == 0) {
     part[c] = sx;
     part[nb + c] = sy;
@@ -180,12 +172,8 @@ __global__ __launch_bounds__(kThreads) void lw_fold_kernel(OptArgs a, RuleHyper 
 template <bool LAMB, bool FOLD, typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper h) {
   using C = typename Comp<P>::type;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int c = b - a.start[t];
-  const int64_t base = static_cast<int64_t>(c) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t, c = ch.c;
   const LwScalars<C> s = lw_scalars<C>(h, LAMB);
   const int tid = threadIdx.x;
 
@@ -193,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper
   C q;
   if (FOLD) {
     C sx, sy;
-    lw_fold(reinterpret_cast<const C*>(a.s3[t]), a.start[t + 1] - a.start[t], sx, sy);
+    lw_fold(reinterpret_cast<const C*>(a.s3[t]), ch.nb, sx, sy);
     q = lw_ratio<LAMB>(s, sx, sy);
     if (c == 0 && tid == 0) ratio[a.tidx[t]] = q;
   } else {
@@ -224,14 +212,14 @@ __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper
   };
 
   const bool vec = aligned16(p) && aligned16(s1) && (LAMB ? aligned16(s2) : aligned16(g)) && (!MASTER || aligned16(w));
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (vec) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
-        const int64_t off = base + vi * kVec;
+        const int64_t off = ch.base + vi * kVec;
         P pv[kVec]; G gv[kVec]; S av[kVec]; S bv[kVec]; float wv[kVec];
         load8(s1 + off, av);
         if (LAMB) load8(s2 + off, bv); else load8(g + off, gv);
@@ -243,9 +231,9 @@ __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper
         store8(p + off, pv);
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     P pv = p[i];
     S av = s1[i];
     const S bv = LAMB ? s2[i] : S(0);
@@ -290,27 +278,21 @@ void launch_layerwise(const std::vector<uintptr_t>& param, const std::vector<uin
     int most = 0;
     for (int t = 0; t < a.n; ++t) most = std::max(most, a.start[t + 1] - a.start[t]);
     const bool own_launch = pin >= 0 ? pin == 1 : most > kFoldLaunchChunks;
-    bool done = false;
-#define X(P, G, S, M)                                                                            \
-  if (!done && p_dtype == code_of<P>() && g_dtype == code_of<G>() && s_dtype == code_of<S>() && \
-      has_master == M) {                                                                         \
-    lw_stats_kernel<LAMB, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);                    \
-    FLUXMPI_HIP_CHECK(hipGetLastError());                                                        \
-    if (own_launch) {                                                                            \
-      lw_fold_kernel<LAMB, typename Comp<P>::type><<<a.n, kThreads, 0, stream>>>(a, h);          \
-      FLUXMPI_HIP_CHECK(hipGetLastError());                                                      \
-      lw_apply_kernel<LAMB, false, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);           \
-    } else {                                                                                     \
-      lw_apply_kernel<LAMB, true, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);            \
-    }                                                                                            \
-    done = true;                                                                                 \
-  }
-    OPT_DTYPE_COMBOS(X)
-#undef X
-    if (!done)
-      throw std::runtime_error(std::string(name) + ": unsupported dtype combination p=" + std::to_string(p_dtype) +
-                               " g=" + std::to_string(g_dtype) + " s=" + std::to_string(s_dtype) +
-                               " master=" + std::to_string(has_master));
+    dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, name, [&](auto p, auto g, auto s, auto master) {
+      using P = typename decltype(p)::type;
+      using G = typename decltype(g)::type;
+      using S = typename decltype(s)::type;
+      constexpr bool M = decltype(master)::value;
+      lw_stats_kernel<LAMB, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
+      FLUXMPI_HIP_CHECK(hipGetLastError());
+      if (own_launch) {
+        lw_fold_kernel<LAMB, typename Comp<P>::type><<<a.n, kThreads, 0, stream>>>(a, h);
+        FLUXMPI_HIP_CHECK(hipGetLastError());
+        lw_apply_kernel<LAMB, false, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
+      } else {
+        lw_apply_kernel<LAMB, true, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
+      }
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }

@@ -175,11 +175,8 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
   using C = typename Comp<P>::type;
   using R = RuleT<C>;
   constexpr int NS = R::kStates;
-  const int b = blockIdx.x;
-  const int t = find_tensor(a.start, a.n, b);
-  const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
-  const int64_t n = a.numel[t];
-  const int64_t end = base + kChunk < n ? base + kChunk : n;
+  const Chunk ch = chunk_of(a);
+  const int t = ch.t;
 
   RuleElem<R, P, G, S, MASTER> op;
   C lr = static_cast<C>(h.lr), bt1 = static_cast<C>(h.bt1), bt2 = static_cast<C>(h.bt2);
@@ -207,14 +204,14 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
   const int tid = threadIdx.x;
   const bool vec = aligned16(p) && aligned16(g) && aligned16(s1) && (NS < 2 || aligned16(s2)) &&
                    (NS < 3 || aligned16(s3)) && (!MASTER || aligned16(w));
-  int64_t scalar_from = base;
+  int64_t scalar_from = ch.base;
   if (vec) {
-    const int64_t nvec = (end - base) / kVec;
+    const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
     for (int k = 0; k < kIters; ++k) {
       const int64_t vi = tid + k * kThreads;
       if (vi < nvec) {
-        const int64_t off = base + vi * kVec;
+        const int64_t off = ch.base + vi * kVec;
         P pv[kVec]; G gv[kVec]; S av[kVec]; S bv[kVec]; S cv[kVec]; float wv[kVec];
         load8(g + off, gv);
         load8(s1 + off, av);
@@ -230,9 +227,9 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
         store8(p + off, pv);
       }
     }
-    scalar_from = base + nvec * kVec;
+    scalar_from = ch.base + nvec * kVec;
   }
-  for (int64_t i = scalar_from + tid; i < end; i += kThreads) {
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     P pv = p[i];
     S av = s1[i];
     S bv = NS > 1 ? s2[i] : S(0);
@@ -261,19 +258,10 @@ void launch_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_
                              " state list(s) as long as the parameter list");
   const bool has_master = !master.empty();
   for_each_group(param, grad, s1, s2, s3, master, numel, [&](const OptArgs& a, int blocks) {
-    bool done = false;
-#define X(P, G, S, M)                                                                            \
-  if (!done && p_dtype == code_of<P>() && g_dtype == code_of<G>() && s_dtype == code_of<S>() && \
-      has_master == M) {                                                                         \
-    mt_rule_kernel<RuleT, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);                    \
-    done = true;                                                                                 \
-  }
-    OPT_DTYPE_COMBOS(X)
-#undef X
-    if (!done)
-      throw std::runtime_error("mt_rule: unsupported dtype combination p=" + std::to_string(p_dtype) +
-                               " g=" + std::to_string(g_dtype) + " s=" + std::to_string(s_dtype) +
-                               " master=" + std::to_string(has_master));
+    dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_rule", [&](auto p, auto g, auto s, auto master) {
+      mt_rule_kernel<RuleT, typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                     decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }

@@ -54,6 +54,39 @@ def _tscale_ptr(tscale, idx, ct, n) -> int:
     return tscale[torch.tensor(idx, device=tscale.device)].data_ptr()
 
 
+def _ptr(t: torch.Tensor | None) -> int:
+    """Device address of an optional tensor; 0 when it is not given."""
+    return t.data_ptr() if t is not None else 0
+
+
+def _dtype_groups(name: str, params, grads, states, masters, slots: int) -> list:
+    """The call's leaves by (param, grad, state, master) dtype, one ``(idx, pd, head)`` per group, checked
+    before anything is launched. ``idx``: the group's positions in the call's lists; ``pd``: its
+    parameter dtype; ``head``: the leading arguments of the kernel entry — the address lists of the
+    parameters, the gradients, ``slots`` state lists (those beyond ``states`` empty) and the masters
+    (empty without), the element counts and the three dtype codes.
+
+    ``TypeError`` unless every leaf's gradient, states (of one dtype; a call without states counts as
+    the parameter's) and fp32 master have the parameter's element count — the kernels index all of
+    them by it — and the kernels are built for the group's dtypes."""
+    groups: dict = {}
+    for i, p in enumerate(params):
+        sd = states[0][i].dtype if states else p.dtype
+        if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
+                or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
+            raise TypeError(f"fused {name}: leaf {i}: gradient, states and master must match the parameter's "
+                            "size (states of one dtype, fp32 master)")
+        groups.setdefault((p.dtype, grads[i].dtype, sd, masters is not None), []).append(i)
+    out = []
+    for (pd, gd, sd, hm), idx in groups.items():
+        if not supported(pd, gd, sd, hm):
+            raise TypeError(f"fused {name}: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
+        lists = [params, grads, *states, *[None] * (slots - len(states)), masters]
+        out.append((idx, pd, [*([t[i].data_ptr() for i in idx] if t is not None else [] for t in lists),
+                              [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd]]))
+    return out
+
+
 def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
           bc1: float, bc2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
@@ -74,22 +107,9 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     if params[0].is_cuda:
         C = _ext.get(required=True)
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
-        m_list = masters if masters is not None else None
-        groups: dict = {}
-        for i, p in enumerate(params):
-            key = (p.dtype, grads[i].dtype, exp_avgs[i].dtype, m_list is not None)
-            groups.setdefault(key, []).append(i)
-        for (pd, gd, sd, hm), idx in groups.items():
-            if not supported(pd, gd, sd, hm):
-                raise TypeError(f"fused Adam: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
-            C.mt_adam([params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx],
-                      [exp_avgs[i].data_ptr() for i in idx], [exp_avg_sqs[i].data_ptr() for i in idx],
-                      [m_list[i].data_ptr() for i in idx] if hm else [],
-                      [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
-                      float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
-                      float(weight_decay), float(grad_scale),
-                      dev_hyper.data_ptr() if dev_hyper is not None else 0,
-                      dev_gscale.data_ptr() if dev_gscale is not None else 0, stream,
+        for idx, pd, head in _dtype_groups("Adam", params, grads, [exp_avgs, exp_avg_sqs], masters, 2):
+            C.mt_adam(*head, float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
+                      float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), stream,
                       tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
         return
     if dev_hyper is not None:
@@ -153,21 +173,10 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
     if params[0].is_cuda:
         C = _ext.get(required=True)
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
-        groups: dict = {}
-        for i, p in enumerate(params):
-            sd = bufs[i].dtype if (bufs is not None and momentum != 0.0) else p.dtype
-            key = (p.dtype, grads[i].dtype, sd, masters is not None)
-            groups.setdefault(key, []).append(i)
-        for (pd, gd, sd, hm), idx in groups.items():
-            if not supported(pd, gd, sd, hm):
-                raise TypeError(f"fused SGD: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
-            C.mt_sgd([params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx],
-                     [bufs[i].data_ptr() for i in idx] if momentum != 0.0 else [],
-                     [masters[i].data_ptr() for i in idx] if hm else [],
-                     [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
-                     float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(nesterov)),
-                     dev_lr.data_ptr() if dev_lr is not None else 0, stream,
-                     dev_gscale=dev_gscale.data_ptr() if dev_gscale is not None else 0,
+        # without momentum the buffers are not read: Optimisers.Descent has none
+        for idx, pd, head in _dtype_groups("SGD", params, grads, [bufs] if momentum != 0.0 else [], masters, 1):
+            C.mt_sgd(*head, float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(nesterov)),
+                     _ptr(dev_lr), stream, dev_gscale=_ptr(dev_gscale),
                      tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
         return
     if dev_lr is not None:
@@ -254,25 +263,9 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
     if params[0].is_cuda:
         C = _ext.get(required=True)
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
-        groups: dict = {}
-        for i, p in enumerate(params):
-            sd = states[0][i].dtype
-            if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
-                    or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
-                raise TypeError(f"fused {kind}: leaf {i}: gradient, states and master must match the parameter's "
-                                "size (states of one dtype, fp32 master)")
-            groups.setdefault((p.dtype, grads[i].dtype, sd, masters is not None), []).append(i)
-        for (pd, gd, sd, hm), idx in groups.items():
-            if not supported(pd, gd, sd, hm):
-                raise TypeError(f"fused {kind}: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
-            st = [[s[i].data_ptr() for i in idx] for s in states] + [[]] * (3 - ns)
-            C.mt_rule(code, [params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx], st[0], st[1], st[2],
-                      [masters[i].data_ptr() for i in idx] if hm else [],
-                      [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
-                      float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
-                      float(weight_decay), float(grad_scale),
-                      dev_hyper.data_ptr() if dev_hyper is not None else 0,
-                      dev_gscale.data_ptr() if dev_gscale is not None else 0,
+        for idx, pd, head in _dtype_groups(kind, params, grads, states, masters, 3):
+            C.mt_rule(code, *head, float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
+                      float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale),
                       _tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), float(clip_delta), stream)
         return
     if dev_hyper is not None:
@@ -358,21 +351,12 @@ def _layerwise_(kind, params, grads, states, hyper, *, weight_decay, grad_scale,
     C = _ext.get(required=True)
     dev = params[0].device
     stream = torch.cuda.current_stream(dev).cuda_stream
-    ns, nh = len(states), 3 if kind == "lamb" else 1
+    nh = 3 if kind == "lamb" else 1
     if dev_hyper is not None and (dev_hyper.dtype != torch.float32 or dev_hyper.numel() < nh
                                   or not dev_hyper.is_contiguous()):
         raise TypeError(f"fused {kind}: dev_hyper is a contiguous fp32 tensor of {nh} entries")
-    groups: dict = {}
-    for i, p in enumerate(params):
-        sd = states[0][i].dtype
-        if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
-                or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
-            raise TypeError(f"fused {kind}: leaf {i}: gradient, states and master must match the parameter's "
-                            "size (states of one dtype, fp32 master)")
-        groups.setdefault((p.dtype, grads[i].dtype, sd, masters is not None), []).append(i)
-    for (pd, gd, sd, hm), idx in groups.items():
-        if not supported(pd, gd, sd, hm):
-            raise TypeError(f"fused {kind}: unsupported dtypes param={pd} grad={gd} state={sd} master={hm}")
+    groups = _dtype_groups(kind, params, grads, states, masters, 3)
+    for idx, pd, head in groups:
         at = _acc_dtype(pd)
         need = layerwise_workspace([params[i] for i in idx])
         ws = workspace
@@ -393,14 +377,10 @@ def _layerwise_(kind, params, grads, states, hyper, *, weight_decay, grad_scale,
             off += 2 * ((params[i].numel() + 4095) // 4096)
             if params[i].numel() == 0:
                 table[k:k + 1].fill_(1)  # a leaf without elements reaches no kernel: ratio 1
-        st = [[s[i].data_ptr() for i in idx] for s in states] + [[]] * (2 - ns)
-        C.mt_rule(LAYERWISE[kind], [params[i].data_ptr() for i in idx], [grads[i].data_ptr() for i in idx],
-                  st[0], st[1], part, [masters[i].data_ptr() for i in idx] if hm else [],
-                  [params[i].numel() for i in idx], DTYPE_CODE[pd], DTYPE_CODE[gd], DTYPE_CODE[sd],
-                  float(hyper["lr"]), float(hyper["beta1"]), float(hyper["beta2"]), float(hyper["eps"]),
-                  float(hyper.get("bt1", 0.0)), float(hyper.get("bt2", 0.0)), float(weight_decay), float(grad_scale),
-                  dev_hyper.data_ptr() if dev_hyper is not None else 0,
-                  dev_gscale.data_ptr() if dev_gscale is not None else 0, table.data_ptr(), 0.0, stream)
+        head[4] = part  # the s3 slot
+        C.mt_rule(LAYERWISE[kind], *head, float(hyper["lr"]), float(hyper["beta1"]), float(hyper["beta2"]),
+                  float(hyper["eps"]), float(hyper.get("bt1", 0.0)), float(hyper.get("bt2", 0.0)), float(weight_decay),
+                  float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), table.data_ptr(), 0.0, stream)
         if ratios is not None and table is not ratios:
             ratios[torch.tensor(idx, device=dev)] = table.to(ratios.dtype)
 
@@ -555,7 +535,7 @@ def sumsq_(grads, out: torch.Tensor, *, scales: torch.Tensor | None = None, omeg
         elif partials.dtype != at or partials.numel() < need or not partials.is_contiguous():
             raise TypeError(f"sumsq_: partials must be a contiguous {at} tensor with at least {need} entries")
         C.mt_leaf_sumsq([g.data_ptr() for g in grads], [g.numel() for g in grads], DTYPE_CODE[gd],
-                        partials.data_ptr(), out.data_ptr(), scales.data_ptr() if scales is not None else 0,
+                        partials.data_ptr(), out.data_ptr(), _ptr(scales),
                         float(omega), float(grad_scale), torch.cuda.current_stream(grads[0].device).cuda_stream)
         return
     ss = torch.stack([(g.to(at) * g.to(at)).sum() for g in grads])

@@ -148,6 +148,28 @@ def test_fused_sgd(gpu_ext, mom, nest):
         torch.testing.assert_close(a.cpu(), b, rtol=1e-6, atol=1e-6)
 
 
+@pytest.mark.parametrize("rule", ["adam", "sgd"])
+def test_adam_sgd_reject_short_state(gpu_ext, rule):
+    """A state tensor shorter than its parameter is a TypeError before any launch (the kernels index
+    the states by the parameter's element count): nothing is written, the canary behind the
+    parameter included. Every tensor is a view of a buffer long enough for the kernel's reads, so
+    the addresses would be valid even if a launch happened."""
+    from fluxmpi_amd.ops import optim
+    dev = torch.device("cuda")
+    buf = torch.randn(16, device=dev)
+    p, before = buf[:9], buf.clone()
+    g = torch.randn(9, device=dev)
+    full, short = torch.zeros(9, device=dev), torch.zeros(16, device=dev)[:8]
+    with pytest.raises(TypeError, match="leaf 0"):
+        if rule == "adam":
+            optim.adam_([p], [g], [full], [short], lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, bc1=0.1, bc2=0.001)
+        else:
+            optim.sgd_([p], [g], [short], lr=0.1, momentum=0.9)
+    torch.cuda.synchronize()
+    assert torch.equal(buf, before)
+    assert not full.any() and not short.any()
+
+
 def test_rccl_world1(gpu_ext):
     """The native RCCL communicator initialises and runs collectives on one GPU."""
     from fluxmpi_amd.parallel.comm import RcclComm
