@@ -115,6 +115,9 @@ void bn_fwd_train(const void* x, void* y, const void* residual, const float* wei
 // (when residual was fused) d_residual = masked dy.
 // y == nullptr with relu: the ReLU mask is recomputed from x (bit-identical to forward).
 // relu_mask (optional): the 1-bit-per-element mask written by bn_fwd_train.
+// dx == nullptr: reduce and finalize only. dweight / dbias (the finished sums of dy_eff * xhat and of
+// dy_eff) are written and no pass forms dx; the consumer forms it itself from them (gemm_bf16 mode 4).
+// dres must then be null too (it is written by the dx pass): the combination is an error.
 void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
             const float* bias,
             const float* save_mean, const float* save_invstd, void* dx, void* dres,
@@ -287,6 +290,17 @@ struct GemmProblem {
   int conv_s = 1;
 };
 void gemm_bf16(const GemmProblem& g, hipStream_t stream);
+// mode 4 (conv3bn3_bwd.hip): the one-pass backward of conv3 (1x1, 64 -> 256) -> bn3 (+ residual,
+// ReLU) of a stage-1 identity block. dx3, bn3's input gradient, is formed in registers (the dx
+// pass's arithmetic, bit for bit) and never stored; c = d_a2 [M][64] = dx3 . W and the filter
+// gradient's fp32 partials stats[s][256][64], s < splits, of dx3^T . a2 (sum them with
+// gemm_splitk_reduce). Fields: M = pixels, N = 64, K = 256; a = dy [M][256] (K-major, lda = 256);
+// bnb_x = x3 [M][256]; bnb_mask = the 1-bit ReLU mask (bnb_rm = 3); bnb_w / bnb_mean / bnb_inv =
+// bn3's weight (nullable) / saved mean / saved invstd; a_scale = sum dy_eff, a_shift = sum dy_eff
+// xhat ([256] fp32, bn_bwd's dbias / dweight); b = W [256][64] as stored (N-major, ldb = 64);
+// res = a2 [M][64] (ldr = 64); ldc = 64. splits = the slab count = the workgroups launched, the
+// caller's choice: min(ceil(M / 64), 2 x compute units) fills the device with one round.
+void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream);
 // the LDS-DMA pipelined kernel: K-major A (or implicit conv) and B, modes 0/1, optional residual,
 // no prologue affine / split-K / BN-backward epilogue
 bool gemm_glds_supported(const GemmProblem& g);

@@ -24,6 +24,7 @@
 #include <string>
 
 #include "../api.h"
+#include "bn_dx.h"
 #include "common.h"
 
 namespace fluxmpi {
@@ -606,43 +607,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
   block_reduce<DET>(s, q, g.cv, g.rpi, C, acc, smem);
 }
 
-// dx = w*invstd * (dy_eff - sum_dy/R - xhat * sum_dy_xhat/R); dres = dy_eff
-// (sum_dy = db, sum_dy_xhat = dw, produced by bn_finalize_bwd_kernel), evaluated as
-// dx = A*dy_eff + B*x + D with per-channel A = w*invstd, B = -A*invstd*mean(dy_eff*xhat),
-// D = A*(mean*invstd*mean(dy_eff*xhat) - mean(dy_eff)). Coefficients in registers
-// (FIXED) or LDS as in bn_norm_kernel; two vectors per lane per iteration.
-struct DxCoef {
-  float a, b, d, sh;  // sh: forward shift (RM == 2 mask recompute, with a == forward scale)
-};
-
-__device__ __forceinline__ DxCoef dx_coef(int c, const float* __restrict__ w, const float* __restrict__ bias,
-                                          const float* __restrict__ smean, const float* __restrict__ sinv,
-                                          const float* __restrict__ dw, const float* __restrict__ db, float inv_n) {
-  const float iv = sinv[c], m = smean[c];
-  const float sc = (w ? w[c] : 1.f) * iv;
-  const float k2 = db[c] * inv_n, k3 = dw[c] * inv_n;
-  DxCoef k;
-  k.a = sc;
-  k.b = -sc * iv * k3;
-  k.d = sc * (m * iv * k3 - k2);
-  k.sh = fmaf(-m, sc, bias ? bias[c] : 0.f);
-  return k;
-}
-
-template <typename T, int RM, bool DRES>
-__device__ __forceinline__ void dx_vec(float (&d)[8], float (&xv)[8], const float (&yv)[8], unsigned mbs,
-                                       const DxCoef* k) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float dd = d[j];
-    if (RM == 1) dd = yv[j] > 0.f ? dd : 0.f;
-    if (RM == 3) dd = (mbs >> j) & 1u ? dd : 0.f;
-    if (RM == 2) dd = fmaf(xv[j], k[j].a, k[j].sh) > 0.f ? dd : 0.f;
-    d[j] = dd;
-    xv[j] = fmaf(k[j].a, dd, fmaf(k[j].b, xv[j], k[j].d));
-  }
-}
-
+// The dx pass: dx = A*dy_eff + B*x + D per channel (DxCoef, dx_coef, dx_vec: bn_dx.h, shared with
+// conv3bn3_bwd.hip). Coefficients in registers (FIXED) or LDS as in bn_norm_kernel; two vectors
+// per lane per iteration.
 template <typename T, int RM, bool DRES, bool FIXED, int U = 2>
 __global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                              const T* __restrict__ y,
@@ -668,14 +635,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict
     ld8ch(w ? w : smean, c0, ww);  // unconditional: see bn_norm_kernel
     ld8ch(bias ? bias : smean, c0, bb);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {  // == dx_coef, from vector loads
-      const float sc = (w ? ww[j] : 1.f) * iv[j];
-      const float k2 = kdb[j] * inv_n, k3 = kdw[j] * inv_n;
-      rk[j].a = sc;
-      rk[j].b = -sc * iv[j] * k3;
-      rk[j].d = sc * (m[j] * iv[j] * k3 - k2);
-      rk[j].sh = fmaf(-m[j], sc, bias ? bb[j] : 0.f);
-    }
+    for (int j = 0; j < 8; ++j)  // == dx_coef, from vector loads
+      rk[j] = dx_coef_of(w != nullptr, ww[j], bias != nullptr, bb[j], m[j], iv[j], kdw[j], kdb[j], inv_n);
   } else {
     for (int c = threadIdx.x; c < C; c += kThreads) ksm[c] = dx_coef(c, w, bias, smean, sinv, dw, db, inv_n);
     __syncthreads();
@@ -1139,6 +1100,8 @@ void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_ma
             int64_t rows, int64_t C, int relu, int dtype, hipStream_t stream, int stats_ready) {
   check(C);
   check_aligned({weight, bias, save_mean, save_invstd, dweight, dbias});
+  if (dx == nullptr && dres != nullptr)
+    throw std::runtime_error("fused batchnorm: bn_bwd without a dx (reduce and finalize only) writes no dres either");
   const int rm = relu_mode(relu, y, relu_mask);
   dispatch_float(dtype, kBadDtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -1147,6 +1110,8 @@ void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_ma
     if (!stats_ready)
       bwd_reduce_t<T, false>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, workspace, rows, C, rm, stream);
     bn_finalize_bwd(workspace, C, dweight, dbias, stream);
+    // dx == nullptr: reduce and finalize only (the consumer forms dx itself from dweight / dbias)
+    if (dx == nullptr) return;
     dx_t<T>(dy, x, y, relu_mask, weight, bias, save_mean, save_invstd, dweight, dbias, dx, dres, rows, rows, C, rm,
             stream);
   });

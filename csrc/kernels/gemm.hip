@@ -639,6 +639,10 @@ void launch(const GemmArgs& a0, int splits, hipStream_t s) {
 }  // namespace
 
 void gemm_bf16(const GemmProblem& g, hipStream_t stream) {
+  if (g.mode == 4) {  // conv3 -> bn3 one-pass backward (operand mapping: api.h)
+    conv3bn3_bwd(g, stream);
+    return;
+  }
   // engine 0 (auto): the LDS-DMA pipelined kernel for every problem it covers
   // (not for a prologue affine: its per-fragment transform costs the LDS-DMA kernel 1.3-2.3x —
   // measured — while register staging applies it on the way to LDS; engine 2 forces it)

@@ -15,6 +15,7 @@ from __future__ import annotations
 import concurrent.futures as cf
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -71,7 +72,20 @@ def _obj_for(src: str) -> str:
 # clean: profiles/rd5c_gemm_nt_store_hazard.md). The memory-bound elementwise kernels keep it.
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {f: _NO_SLP for f in ("gemm_nt.hip", "attention.hip", "gemm_glds.hip", "gemm.hip", "conv3x3n.hip",
-                                        "wgrad3x3n.hip", "linbwd.hip")}
+                                        "wgrad3x3n.hip", "linbwd.hip", "conv3bn3_bwd.hip")}
+
+
+# kernels tuned to sit just under the 256-VGPR limit: a compiler that starts to spill them must show
+# at build time, not as a slow step (the resource remarks of their compile are checked for scratch)
+NO_SCRATCH = ("conv3bn3_bwd.hip",)
+
+
+def _check_no_scratch(src: str, remarks: str) -> None:
+    sizes = [int(m) for m in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks)]
+    if not sizes:
+        raise RuntimeError(f"{src}: the compiler printed no kernel resource usage to check for scratch")
+    if any(sizes):
+        raise RuntimeError(f"{src}: a kernel spills to scratch ({max(sizes)} bytes/lane); it must not\n{remarks}")
 
 
 def _compile_cmd(src: str, obj: str) -> list[str]:
@@ -81,7 +95,8 @@ def _compile_cmd(src: str, obj: str) -> list[str]:
               "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
     if src.endswith(".hip"):
         return [_tool("hipcc"), f"--offload-arch={ARCH}", "-c", src, "-o", obj, *common,
-                "-munsafe-fp-atomics", *EXTRA_FLAGS.get(os.path.basename(src), [])]
+                "-munsafe-fp-atomics", *EXTRA_FLAGS.get(os.path.basename(src), []),
+                *(["-Rpass-analysis=kernel-resource-usage"] if os.path.basename(src) in NO_SCRATCH else [])]
     inc = [f"-I{pybind11.get_include()}", f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include"]
     return [_tool("amdclang++"), "-D__HIP_PLATFORM_AMD__=1", "-c", src, "-o", obj, *common, *inc,
             "-fvisibility=hidden"]
@@ -115,7 +130,16 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
         return r
 
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        list(ex.map(lambda so: run(_compile_cmd(*so)), todo))
+        def compile_one(so):
+            r = run(_compile_cmd(*so))
+            if os.path.basename(so[0]) in NO_SCRATCH:
+                try:
+                    _check_no_scratch(so[0], r.stderr)
+                except RuntimeError:
+                    os.remove(so[1])  # not a usable object: the next build checks again
+                    raise
+
+        list(ex.map(compile_one, todo))
 
     objs = [_obj_for(s) for s in srcs]
     if force or todo or _stale(out, objs):

@@ -193,6 +193,10 @@ class Bottleneck(nn.Module):
                     else:
                         a2 = self.bn2(self.conv2(a1), relu=True)
                     o3 = fb.conv1x1_forward_is_ours(a2, self.conv3.weight)
+                    if self.downsample is None and fb.conv3bn3_ok(a2, self.conv3, self.bn3, identity, link):
+                        # stage-1 identity block: conv3 -> bn3 as one node, whose backward forms bn3's
+                        # input gradient in registers (one pass instead of dx + dgrad + wgrad)
+                        return fb.conv3_bn3_relu(a2, self.conv3, self.bn3, identity, link, ours_fwd=o3)
                     c3 = fb.conv1x1_hybrid(a2, self.conv3.weight, None, ours_stats=o3)
                 else:
                     c2 = fb.conv3x3(a1, self.conv2.weight) if fb.conv3x3_supported(a1, self.conv2) else self.conv2(a1)

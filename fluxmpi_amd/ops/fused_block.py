@@ -26,6 +26,8 @@ recomputed in the backward match the forward bit for bit.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _ext
@@ -391,6 +393,114 @@ class _BNFromStats(torch.autograd.Function):
         if ctx.link is not None:
             ctx.link.grad, dres = ((dy, mask) if hand_masked else dres), None
         return dx, dw.to(ctx.wdtype), db.to(ctx.wdtype), dres, None, None, None, None, None, None, None, None, None
+
+
+class _Conv3BN3(torch.autograd.Function):
+    """out = relu(bn3(conv3(a2)) + residual) of a stage-1 identity block (1x1, 64 -> 256), whose
+    backward never materialises bn3's input gradient dx3. Forward: exactly the launches of
+    ``conv1x1_hybrid(ours_stats=True)`` + ``bn_from_stats``. Backward: bn3's reduce + finalize
+    (``bn_bwd`` without a dx), then one kernel (``gemm_bf16`` mode 4, csrc/kernels/conv3bn3_bwd.hip)
+    that streams (dy, c3, mask, a2) once, forms dx3 in registers and produces d_a2 = dx3 . W and
+    the per-workgroup partials of dW = dx3^T . a2, then the split-K reduce into the filter's
+    gradient. Unfused, dx3 (the network's largest activation size) is written once and read twice.
+
+    The filter gradient always comes from the one-pass kernel: there is no per-shape choice as
+    ``wgrad_best`` makes for the unfused path. That is measured at ResNet-50's 56 x 56, batch 256 only
+    (``profiles/c3b3_conv3bn3.md``); :func:`conv3bn3_ok` admits any N, H, W, and at few pixels the kernel
+    runs few workgroups, each loading the 32 KiB filter first, which nobody has timed against the
+    unfused kernels."""
+
+    @staticmethod
+    def forward(ctx, a2, weight, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, nbt, link,
+                ours_fwd):
+        C = _ext.get(required=True)
+        cl = torch.channels_last
+        a2 = a2 if a2.is_contiguous(memory_format=cl) else a2.contiguous(memory_format=cl)
+        res = residual if residual.is_contiguous(memory_format=cl) else residual.contiguous(memory_format=cl)
+        note_filter(weight)
+        ws = _workspace(a2)
+        # the per-shape forward choice of conv1x1_hybrid: our GEMM with bn3's sums in its epilogue, or
+        # MIOpen and the statistics pass
+        c3 = _fwd1x1_stats(a2, weight, ws) if ours_fwd else torch.nn.functional.conv2d(a2, weight)
+        ch = c3.shape[1]
+        rows = c3.numel() // ch
+        w32, b32 = bn_weight.float(), bn_bias.float()
+        mean = torch.empty(ch, device=c3.device, dtype=torch.float32)
+        inv = torch.empty_like(mean)
+        C.bn_stats_finalize(c3.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(running_mean), _p(running_var),
+                            mean.data_ptr(), inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(momentum),
+                            float(eps), int(ours_fwd), DTYPE_CODE[c3.dtype], _stream(c3), _p(nbt))
+        y = torch.empty_like(c3)
+        mask = torch.empty(c3.numel() // 8, device=c3.device, dtype=torch.uint8)
+        C.bn_apply(c3.data_ptr(), y.data_ptr(), res.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
+                   inv.data_ptr(), rows, ch, 1, mask.data_ptr(), DTYPE_CODE[c3.dtype], _stream(c3))
+        ctx.link, ctx.wdtype, ctx.params = link, bn_weight.dtype, (bn_weight, bn_bias)
+        ctx.save_for_backward(a2, weight, c3, mask, w32, b32, mean, inv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ext.get(required=True)
+        a2, weight, c3, mask, w32, b32, mean, inv = ctx.saved_tensors
+        if not dy.is_contiguous(memory_format=torch.channels_last):
+            dy = dy.contiguous(memory_format=torch.channels_last)
+        n, ci, h, w = a2.shape
+        co, rows = weight.shape[0], n * h * w
+        dev, st = dy.device, _stream(dy)
+        dbw, dbb = _grad_out(ctx.params[0], co, c3), _grad_out(ctx.params[1], co, c3)
+        # reduce + finalize only (dx = dres = null): the two finished sums land in dbw / dbb
+        C.bn_bwd(dy.data_ptr(), c3.data_ptr(), 0, mask.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
+                 inv.data_ptr(), 0, 0, dbw.data_ptr(), dbb.data_ptr(), _workspace(c3).data_ptr(), rows, co, 1,
+                 DTYPE_CODE[c3.dtype], st, 0)
+        slabs = conv3bn3_slabs(rows, dev)
+        part = torch.empty(slabs, co, ci, device=dev, dtype=torch.float32)
+        d_a2 = _empty_nhwc(n, ci, h, w, a2)
+        gemm(dy, weight, d_a2, M=rows, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False, mode=4,
+             splits=slabs, a_affine=(dbb, dbw), stats=part, residual=_nhwc2d(a2),
+             bn_bwd=(c3, w32, None, mean, inv, mask, 3))
+        dw = None
+        if ctx.needs_input_grad[1]:
+            with graddst.into(weight):
+                dw = graddst.empty((co, ci), weight.dtype, dev)
+            C.gemm_splitk_reduce(part.data_ptr(), slabs, co * ci, dw.data_ptr(), DTYPE_CODE[dw.dtype], st)
+            dw = dw.view(co, ci, 1, 1)
+        if ctx.link is not None:
+            ctx.link.grad = (dy, mask)  # the residual's gradient: conv1's dgrad epilogue applies the mask
+        return (d_a2, dw, dbw.to(ctx.wdtype), dbb.to(ctx.wdtype), None, None, None, None, None, None, None, None)
+
+
+# the one-pass conv3 -> bn3 backward of the stage-1 identity blocks (FLUXMPI_CONV3BN3=0: the
+# separate dx pass + input-gradient GEMM + weight-gradient kernel)
+CONV3BN3 = os.environ.get("FLUXMPI_CONV3BN3", "1") != "0"
+
+
+def conv3bn3_slabs(rows: int, device) -> int:
+    """Workgroups (= fp32 partial slabs) of the mode-4 kernel: one resident round, two
+    workgroups per compute unit, never more than the 32-pixel tiles there are."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return max(1, min(-(-rows // 32), 2 * cus))
+
+
+def conv3bn3_ok(a2, conv, bn, residual, link) -> bool:
+    """:func:`conv3_bn3_relu` applies: bf16 NHWC, the 64 -> 256 1x1 convolution, a training-mode
+    affine fused BatchNorm, and a residual whose gradient travels as (dy, mask) through a masked
+    :class:`GradLink` (or is not needed)."""
+    from .batchnorm import FusedBatchNorm2d
+    wt = conv.weight
+    return (CONV3BN3 and G.ENGINE != 1 and a2.is_cuda and a2.dim() == 4 and a2.dtype == torch.bfloat16
+            and wt.dtype == torch.bfloat16 and tuple(wt.shape) == (256, 64, 1, 1) and wt.is_contiguous()
+            and a2.shape[1] == 64 and a2.numel() // 64 < 2 ** 31 and residual is not None
+            and residual.shape == (a2.shape[0], 256, a2.shape[2], a2.shape[3]) and residual.dtype == a2.dtype
+            and (link.masked if link is not None else not (residual.requires_grad and torch.is_grad_enabled()))
+            and isinstance(bn, FusedBatchNorm2d) and bn.training and bn.affine and bn.track_running_stats)
+
+
+def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True):
+    """relu(bn(conv(a2)) + residual) with the one-pass backward (check :func:`conv3bn3_ok`);
+    ``ours_fwd``: :func:`conv1x1_forward_is_ours` for this shape."""
+    mom, nbt = bn_counter(bn)
+    return _Conv3BN3.apply(a2, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, mom,
+                           bn.eps, nbt, link, bool(ours_fwd))
 
 
 class _DualBN(torch.autograd.Function):
