@@ -188,7 +188,10 @@ void pad_c3_to_c4(const void* x, void* y, int64_t npix, int dtype, hipStream_t s
 
 // ---- ResNet stem on MFMA (stem.hip): 7x7/2 conv of NHWC4 224x224 images + BN statistics;
 // the fused backward (pool gather + BN backward + filter gradient)
-void stem_fwd(const void* x, const void* wp, void* y, float* stats, int64_t n, hipStream_t stream);
+// (stem_fwd's max_blocks caps the persistent grid, 0 = the resident workgroups: fewer workgroups walk more
+// row groups each, which is how the tests run the double-buffered halo loop at small batches)
+void stem_fwd(const void* x, const void* wp, void* y, float* stats, int64_t n, hipStream_t stream,
+              int max_blocks = 0);
 int stem_bwd_blocks(int64_t n);
 int64_t stem_part_floats();
 void stem_bwd(const void* x, const void* c, const void* dp, const uint8_t* idx, const float* w, const float* mean,

@@ -127,7 +127,8 @@ PYBIND11_MODULE(_C, m) {
     return py::make_tuple(std::string(d.fwd), std::string(d.bwd), d.fwd_parts, d.bwd_parts);
   });
   m.def("pad_c3_to_c4", raw(&pad_c3_to_c4));
-  m.def("stem_fwd", raw(&stem_fwd));
+  m.def("stem_fwd", raw(&stem_fwd), py::arg("x"), py::arg("wp"), py::arg("y"), py::arg("stats"), py::arg("n"),
+        py::arg("stream"), py::arg("max_blocks") = 0);
   m.def("stem_bwd_blocks", &stem_bwd_blocks);
   m.def("stem_part_floats", &stem_part_floats);
   m.def("stem_bwd", raw(&stem_bwd));

@@ -629,16 +629,18 @@ int stem_bwd_blocks(int64_t n) {
 
 int64_t stem_part_floats() { return kPart; }
 
-void stem_fwd(const void* x, const void* wp, void* y, float* stats, int64_t n, hipStream_t s) {
+void stem_fwd(const void* x, const void* wp, void* y, float* stats, int64_t n, hipStream_t s, int max_blocks) {
   check_ptr(x, "x");
   check_ptr(wp, "packed filter");
   check_ptr(y, "y");
   check_ptr(stats, "stats");
   if (n < 1 || n * kOH * kOW * kCo >= (int64_t(1) << 40)) throw std::runtime_error("stem_fwd: bad batch");
+  if (max_blocks < 0) throw std::runtime_error("stem_fwd: max_blocks must be >= 0 (0: the resident workgroups)");
   set_lds_attrs();
   const int groups = static_cast<int>(n * (kOH / kFRows));
   static int resident = [] { return resident_blocks(reinterpret_cast<const void*>(&stem_fwd_kernel), kFT, kFSmem); }();
-  const int blocks = groups < resident ? groups : resident;
+  const int cap = max_blocks > 0 && max_blocks < resident ? max_blocks : resident;  // a test's grid: longer walks
+  const int blocks = groups < cap ? groups : cap;
   const int per = (groups + blocks - 1) / blocks;
   StemFwdArgs a{static_cast<const bf16*>(x), static_cast<const bf16*>(wp), static_cast<bf16*>(y), stats, groups, per};
   stem_fwd_kernel<<<static_cast<unsigned>((groups + per - 1) / per), kFT, kFSmem, s>>>(a);
