@@ -34,6 +34,9 @@ struct AdamHyper {
   const float* dev_gscale;  // optional device gradient scale (e.g. 1/loss_scale, the global-norm clip)
   const void* tscale = nullptr;  // optional device scale per leaf of the call (ClipNorm), fp32 (fp64 params: fp64)
   float clip_delta = 0.f;        // ClipGrad: clamp the scaled gradient to [-delta, delta]; 0: off
+  // optional device int32 (loss scaling's non-finite flag): when *dev_skip != 0 every workgroup
+  // returns before its first load of tensor data and nothing is stored; null: no predicate
+  const int32_t* dev_skip = nullptr;
 };
 
 // master: optional fp32 master weights (mixed precision); when given, param is
@@ -43,8 +46,9 @@ void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
              const std::vector<uintptr_t>& master, const std::vector<int64_t>& numel,
              int p_dtype, int g_dtype, int s_dtype, const AdamHyper& h, hipStream_t stream);
 
-// dev[1] *= beta1, dev[2] *= beta2 (advance the bias-correction powers on device).
-void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream);
+// dev[1] *= beta1, dev[2] *= beta2 (advance the bias-correction powers on device); not when
+// dev_skip is given and *dev_skip != 0 (a skipped step does not count).
+void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream, const int32_t* dev_skip = nullptr);
 
 struct SgdHyper {
   float lr, momentum, weight_decay, grad_scale;
@@ -53,6 +57,7 @@ struct SgdHyper {
   const float* dev_gscale = nullptr;  // as in AdamHyper
   const void* tscale = nullptr;
   float clip_delta = 0.f;
+  const int32_t* dev_skip = nullptr;  // as in AdamHyper
 };
 // buf: momentum buffers (ignored when momentum == 0 -> Optimisers.Descent).
 void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
@@ -77,6 +82,9 @@ struct RuleHyper {
   const float* dev_gscale;   // as in AdamHyper
   const void* tscale;        // LARS / LAMB: written, the trust ratio of each leaf of the call (no input scale)
   float clip_delta;          // LARS / LAMB: must be 0
+  // as in AdamHyper; a skipped LARS / LAMB step also leaves the moments, the partials and the ratio
+  // table as the previous step wrote them
+  const int32_t* dev_skip = nullptr;
 };
 // s1 / s2 / s3: the rule's state tensors in its Optimisers.jl order (as many lists as the rule
 // keeps states: 1 RMSProp, AdaGrad, Lion; 2 AdaMax, NAdam, AdaBelief, AdaDelta; 3 AMSGrad; the
@@ -95,13 +103,34 @@ void mt_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
 // scale[i] = min(1, omega / (grad_scale * sqrt(sumsq[i]))) with torch.clamp's edge values
 // (norm 0 -> 1, NaN -> NaN, inf -> 0). sumsq / scale / partials hold fp32 (fp64 gradients:
 // fp64); partials needs sumsq_partials(numel) entries. A leaf without elements gets 0 / 1.
+// nonfinite_flag: the same pass also runs mt_check_finite's test on every element it reads (the
+// sums are the bits of the call without it). dev_pre: a device scalar multiplied into the norm
+// (loss scaling's inverse scale: the scales then refer to the unscaled gradient); sumsq stays raw.
 int64_t sumsq_partials(const std::vector<int64_t>& numel);
 void mt_leaf_sumsq(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
-                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream);
+                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream,
+                   int32_t* nonfinite_flag = nullptr, const float* dev_pre = nullptr);
 // slot[0] = (accumulate ? slot[0] : 0) + sum_i sumsq[i] (fixed order); slot[1] = grad_scale *
-// sqrt(slot[0]) (the global gradient norm); slot[2] = omega > 0 ? min(1, omega / slot[1]) : 1.
+// [*dev_pre *] sqrt(slot[0]) (the global gradient norm); slot[2] = [*dev_pre *] (omega > 0 ?
+// min(1, omega / slot[1]) : 1): the one dev_gscale of an update behind a loss scale and a global clip.
 void clip_total(const void* sumsq, int64_t n, int acc_dtype, float* slot, int accumulate, float omega,
-                float grad_scale, hipStream_t stream);
+                float grad_scale, hipStream_t stream, const float* dev_pre = nullptr);
+
+// ---- loss scaling: exact non-finite check, scaler update -------------------------------
+// flag[0] = 1 if any element of any gradient is inf or NaN (exponent field all ones: per element,
+// so a finite value whose square overflows does not count); left alone otherwise. One int32,
+// sticky: the checks of a step's buckets and dtypes accumulate into it and loss_scale_update
+// clears it. The update kernels' job layout (one workgroup per 4096-element chunk); a workgroup
+// that found one stores the 1 from one lane after a block-wide OR: no atomics, no zero fill.
+void mt_check_finite(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
+                     int32_t* flag, hipStream_t stream);
+// The scaler's device block, 8 words: {float scale, float 1/scale, int32 growth tracker, int32 steps
+// skipped so far, int32 last step skipped, int32 non-finite flag, 2 unused}. One thread applies
+// GradScaler's rule: flag set -> scale *= backoff, tracker = 0, skipped += 1; clear -> tracker += 1
+// and at tracker == interval scale *= growth, tracker = 0. Then scale is clamped to [min_scale,
+// max_scale], its inverse stored, the flag copied to "last step skipped" and cleared.
+void loss_scale_update(void* block, float growth, float backoff, int interval, float min_scale, float max_scale,
+                       hipStream_t stream);
 
 // ---- BatchNorm (NHWC, channels innermost) + ReLU / residual-add fusions ----------
 // Training forward: per-channel batch statistics over rows = N*H*W, then

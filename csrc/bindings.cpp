@@ -36,6 +36,94 @@ template <typename R, typename... A> auto raw(R (*fn)(A...)) {
 using Ptrs = const std::vector<uintptr_t>&;
 using Ptrs3 = std::array<uintptr_t, 3>;
 
+// ---- the fused optimisers' entries, bound twice --------------------------------------------------
+// `_C` keeps the surface tests/golden/c_api_surface.json records. The loss-scaling arguments (the
+// skip predicate of the update kernels, the non-finite flag and the inverse scale of the norm pass)
+// and entries live in `_C_scale`, a second module of this shared object, with `dev_skip` as a
+// trailing keyword argument. One body serves both: it takes dev_skip FIRST, no_skip binds it to
+// null and skip_last moves it behind the other parameters.
+template <typename R, typename... A> auto no_skip(R (*fn)(uintptr_t, A...)) {
+  return [fn](A... a) -> R { return fn(0, a...); };
+}
+template <typename R, typename... A> auto skip_last(R (*fn)(uintptr_t, A...)) {
+  return [fn](A... a, uintptr_t dev_skip) -> R { return fn(dev_skip, a...); };
+}
+
+static void py_mt_adam(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
+                       const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, float lr, float beta1,
+                       float beta2, float eps, float bc1, float bc2, float weight_decay, float grad_scale,
+                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale, float clip_delta) {
+  AdamHyper h{lr, beta1, beta2, eps, bc1, bc2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
+              ptr<const float*>(dev_gscale)};
+  h.tscale = ptr<const void*>(tscale);
+  h.clip_delta = clip_delta;
+  h.dev_skip = ptr<const int32_t*>(dev_skip);
+  mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+}
+
+static void py_mt_sgd(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel,
+                      int p_dtype, int g_dtype, int s_dtype, float lr, float momentum, float weight_decay,
+                      float grad_scale, int nesterov, uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale,
+                      uintptr_t tscale, float clip_delta) {
+  SgdHyper h{lr, momentum, weight_decay, grad_scale, nesterov, ptr<const float*>(dev_lr)};
+  h.dev_gscale = ptr<const float*>(dev_gscale);
+  h.tscale = ptr<const void*>(tscale);
+  h.clip_delta = clip_delta;
+  h.dev_skip = ptr<const int32_t*>(dev_skip);
+  mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+}
+
+static void py_mt_rule(uintptr_t dev_skip, int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master,
+                       const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
+                       double beta2, double eps, double bt1, double bt2, double weight_decay, float grad_scale,
+                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta, uintptr_t stream) {
+  RuleHyper h{kind, lr, beta1, beta2, eps, bt1, bt2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
+              ptr<const float*>(dev_gscale), ptr<const void*>(tscale), clip_delta, ptr<const int32_t*>(dev_skip)};
+  mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+}
+
+#define ADAM_ARGS                                                                                                  \
+  py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("master"), py::arg("numel"),             \
+      py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("beta1"),                \
+      py::arg("beta2"), py::arg("eps"), py::arg("bc1"), py::arg("bc2"), py::arg("weight_decay"),                  \
+      py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"),                      \
+      py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f
+#define SGD_ARGS                                                                                                   \
+  py::arg("param"), py::arg("grad"), py::arg("buf"), py::arg("master"), py::arg("numel"), py::arg("p_dtype"),     \
+      py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),        \
+      py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"), py::arg("stream"),                           \
+      py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f
+#define RULE_ARGS                                                                                                  \
+  py::arg("kind"), py::arg("param"), py::arg("grad"), py::arg("s1"), py::arg("s2"), py::arg("s3"),                \
+      py::arg("master"), py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"),            \
+      py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("bt1"), py::arg("bt2"),          \
+      py::arg("weight_decay"), py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"),                \
+      py::arg("tscale"), py::arg("clip_delta"), py::arg("stream")
+#define SUMSQ_ARGS                                                                                                 \
+  py::arg("grad"), py::arg("numel"), py::arg("g_dtype"), py::arg("partials"), py::arg("sumsq"), py::arg("scale"), \
+      py::arg("omega"), py::arg("grad_scale"), py::arg("stream")
+#define TOTAL_ARGS                                                                                                 \
+  py::arg("sumsq"), py::arg("n"), py::arg("acc_dtype"), py::arg("slot"), py::arg("accumulate"), py::arg("omega"), \
+      py::arg("grad_scale"), py::arg("stream")
+#define NO_SKIP py::arg("dev_skip") = uintptr_t(0)
+
+// The loss-scaling surface (DDP(loss_scale=...)): fluxmpi_amd.ops._ext.scale() loads it from _C's file.
+PYBIND11_MODULE(_C_scale, m) {
+  m.doc() = "fluxmpi_amd native library: the fused optimisers' entries with the loss-scaling arguments";
+  m.def("mt_adam", skip_last(&py_mt_adam), ADAM_ARGS, NO_SKIP);
+  m.def("mt_sgd", skip_last(&py_mt_sgd), SGD_ARGS, NO_SKIP);
+  m.def("mt_rule", skip_last(&py_mt_rule), RULE_ARGS, NO_SKIP);
+  m.def("adam_advance", raw(&adam_advance), py::arg("dev"), py::arg("beta1"), py::arg("beta2"), py::arg("stream"),
+        NO_SKIP);
+  m.def("mt_leaf_sumsq", raw(&mt_leaf_sumsq), SUMSQ_ARGS, py::arg("nonfinite_flag") = uintptr_t(0),
+        py::arg("dev_pre") = uintptr_t(0));
+  m.def("clip_total", raw(&clip_total), TOTAL_ARGS, py::arg("dev_pre") = uintptr_t(0));
+  m.def("mt_check_finite", raw(&mt_check_finite), py::arg("grad"), py::arg("numel"), py::arg("g_dtype"),
+        py::arg("flag"), py::arg("stream"));
+  m.def("loss_scale_update", raw(&loss_scale_update), py::arg("block"), py::arg("growth"), py::arg("backoff"),
+        py::arg("interval"), py::arg("min_scale"), py::arg("max_scale"), py::arg("stream"));
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
 
@@ -44,58 +132,23 @@ PYBIND11_MODULE(_C, m) {
   m.def("mt_fill", raw(&mt_fill));
   m.def("mt_sumsq", raw(&mt_sumsq));
 
-  m.def("mt_adam",
-        [](Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master, const std::vector<int64_t>& numel, int p_dtype, int g_dtype,
-           int s_dtype, float lr, float beta1, float beta2, float eps, float bc1, float bc2, float weight_decay,
-           float grad_scale, uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale,
-           float clip_delta) {
-          AdamHyper h{lr, beta1, beta2, eps, bc1, bc2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
-                      ptr<const float*>(dev_gscale)};
-          h.tscale = ptr<const void*>(tscale);
-          h.clip_delta = clip_delta;
-          mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
-        },
-        py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("master"), py::arg("numel"),
-        py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("beta1"),
-        py::arg("beta2"), py::arg("eps"), py::arg("bc1"), py::arg("bc2"), py::arg("weight_decay"),
-        py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"),
-        py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f);
-  m.def("adam_advance", raw(&adam_advance));
-  m.def("mt_sgd",
-        [](Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel, int p_dtype, int g_dtype,
-           int s_dtype, float lr, float momentum, float weight_decay, float grad_scale, int nesterov,
-           uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta) {
-          SgdHyper h{lr, momentum, weight_decay, grad_scale, nesterov, ptr<const float*>(dev_lr)};
-          h.dev_gscale = ptr<const float*>(dev_gscale);
-          h.tscale = ptr<const void*>(tscale);
-          h.clip_delta = clip_delta;
-          mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
-        },
-        py::arg("param"), py::arg("grad"), py::arg("buf"), py::arg("master"), py::arg("numel"),
-        py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("momentum"),
-        py::arg("weight_decay"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"),
-        py::arg("stream"), py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0),
-        py::arg("clip_delta") = 0.f);
-  m.def("mt_rule",
-        [](int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master, const std::vector<int64_t>& numel,
-           int p_dtype, int g_dtype, int s_dtype, double lr, double beta1, double beta2, double eps, double bt1,
-           double bt2, double weight_decay, float grad_scale, uintptr_t dev_hyper, uintptr_t dev_gscale,
-           uintptr_t tscale, float clip_delta, uintptr_t stream) {
-          RuleHyper h{kind, lr, beta1, beta2, eps, bt1, bt2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
-                      ptr<const float*>(dev_gscale), ptr<const void*>(tscale), clip_delta};
-          mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
-        },
-        py::arg("kind"), py::arg("param"), py::arg("grad"), py::arg("s1"), py::arg("s2"), py::arg("s3"),
-        py::arg("master"), py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"),
-        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("bt1"), py::arg("bt2"),
-        py::arg("weight_decay"), py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"),
-        py::arg("tscale"), py::arg("clip_delta"), py::arg("stream"));
+  m.def("mt_adam", no_skip(&py_mt_adam), ADAM_ARGS);
+  m.def("adam_advance", [](uintptr_t dev, float beta1, float beta2, uintptr_t stream) {
+    adam_advance(ptr<float*>(dev), beta1, beta2, ptr<hipStream_t>(stream));
+  });
+  m.def("mt_sgd", no_skip(&py_mt_sgd), SGD_ARGS);
+  m.def("mt_rule", no_skip(&py_mt_rule), RULE_ARGS);
   m.def("sumsq_partials", &sumsq_partials, py::arg("numel"));
-  m.def("mt_leaf_sumsq", raw(&mt_leaf_sumsq), py::arg("grad"), py::arg("numel"), py::arg("g_dtype"),
-        py::arg("partials"), py::arg("sumsq"), py::arg("scale"), py::arg("omega"), py::arg("grad_scale"),
-        py::arg("stream"));
-  m.def("clip_total", raw(&clip_total), py::arg("sumsq"), py::arg("n"), py::arg("acc_dtype"), py::arg("slot"),
-        py::arg("accumulate"), py::arg("omega"), py::arg("grad_scale"), py::arg("stream"));
+  m.def("mt_leaf_sumsq",
+        [](Ptrs grad, const std::vector<int64_t>& numel, int g_dtype, uintptr_t partials, uintptr_t sumsq,
+           uintptr_t scale, float omega, float grad_scale, uintptr_t stream) {
+          raw(&mt_leaf_sumsq)(grad, numel, g_dtype, partials, sumsq, scale, omega, grad_scale, stream, 0, 0);
+        },
+        SUMSQ_ARGS);
+  m.def("clip_total",
+        [](uintptr_t sumsq, int64_t n, int acc_dtype, uintptr_t slot, int accumulate, float omega, float grad_scale,
+           uintptr_t stream) { raw(&clip_total)(sumsq, n, acc_dtype, slot, accumulate, omega, grad_scale, stream, 0); },
+        TOTAL_ARGS);
 
   // ---- fused NHWC BatchNorm ------------------------------------------------
   m.def("bn_fwd_train", raw(&bn_fwd_train));

@@ -25,6 +25,13 @@
 // folds the per-leaf sums into one device slot {sum, norm, scale} for global-norm clipping.
 // Nothing is read back to the host: the whole sequence is HIP-graph capturable.
 //
+// Loss scaling (DDP(loss_scale=...)) lives here too: mt_check_finite, the exact per-element inf / NaN
+// test into one sticky int32 flag (also the CHECK instantiation of the sum-of-squares pass, so an
+// engine that takes norms reads its gradients once); AdamHyper / SgdHyper::dev_skip, on which a
+// workgroup returns before it touches a tensor (a template flag: without it the kernels are the
+// code they were); dev_pre, the inverse scale multiplied into the norms; and loss_scale_update,
+// GradScaler's rule on the scaler's device block, one thread.
+//
 // Optional fp32 master weights give the mixed-precision layout (bf16 param +
 // fp32 master/m/v); without them the state dtype equals the parameter dtype,
 // which is Optimisers.jl's `zero(x)` layout (bit-compatible state trees).
@@ -57,9 +64,10 @@ struct AdamElem {
   }
 };
 
-template <typename P, typename G, typename S, bool MASTER>
+template <typename P, typename G, typename S, bool MASTER, bool SKIP>
 __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper h) {
   using C = typename Comp<P>::type;
+  if (step_skipped<SKIP>(h.dev_skip)) return;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
 
@@ -144,9 +152,10 @@ struct SgdElem {
   }
 };
 
-template <typename P, typename G, typename S, bool MASTER>
+template <typename P, typename G, typename S, bool MASTER, bool SKIP>
 __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h) {
   using C = typename Comp<P>::type;
+  if (step_skipped<SKIP>(h.dev_skip)) return;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
   SgdElem<P, G, S, MASTER> op;
@@ -196,15 +205,19 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
 }
 
 // ---- deterministic multi-tensor sum of squares + clip scales -------------------------------
-// launch 1: the job layout of the update kernels; workgroup b writes partials[pbase + b]
-template <typename G>
-__global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, typename Acc<G>::type* __restrict__ partials) {
+// launch 1: the job layout of the update kernels; workgroup b writes partials[pbase + b].
+// CHECK: the pass also tests every element it reads for inf / NaN and raises flag[0] (loss scaling:
+// no second read of the gradients); the sums are the bits of CHECK == false.
+template <typename G, bool CHECK>
+__global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, typename Acc<G>::type* __restrict__ partials,
+                                                                     int32_t* __restrict__ flag) {
   using A = typename Acc<G>::type;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
   const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
   const int tid = threadIdx.x;
   A acc = A(0);
+  bool bad = false;
   int64_t scalar_from = ch.base;
   if (aligned16(g)) {
     const int64_t nvec = (ch.end - ch.base) / kVec;
@@ -218,17 +231,51 @@ __global__ __launch_bounds__(kThreads) void mt_sumsq_partial_kernel(OptArgs a, t
         for (int j = 0; j < kVec; ++j) {
           const A x = static_cast<A>(gv[j]);
           acc += x * x;
+          if (CHECK) bad |= nonfinite(gv[j]);
         }
       }
     }
     scalar_from = ch.base + nvec * kVec;
   }
   for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
-    const A x = static_cast<A>(g[i]);
+    const G gi = g[i];
+    const A x = static_cast<A>(gi);
     acc += x * x;
+    if (CHECK) bad |= nonfinite(gi);
   }
-  const A s = block_sum(acc);
+  if (CHECK) note_found(bad);
+  const A s = block_sum(acc);  // (its barrier is the block-wide OR's too)
   if (tid == 0) partials[a.pbase + static_cast<int>(blockIdx.x)] = s;
+  if (CHECK) raise_noted(flag);
+}
+
+// the non-finite test alone, in the same job layout (an engine that takes no norms): one read of the
+// gradients, nothing written but the flag
+template <typename G>
+__global__ __launch_bounds__(kThreads) void mt_check_finite_kernel(OptArgs a, int32_t* __restrict__ flag) {
+  const Chunk ch = chunk_of(a);
+  const G* __restrict__ g = reinterpret_cast<const G*>(a.g[ch.t]);
+  const int tid = threadIdx.x;
+  bool bad = false;
+  int64_t scalar_from = ch.base;
+  if (aligned16(g)) {
+    const int64_t nvec = (ch.end - ch.base) / kVec;
+#pragma unroll
+    for (int k = 0; k < kIters; ++k) {
+      const int64_t vi = tid + k * kThreads;
+      if (vi < nvec) {
+        G gv[kVec];
+        load8(g + ch.base + vi * kVec, gv);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) bad |= nonfinite(gv[j]);
+      }
+    }
+    scalar_from = ch.base + nvec * kVec;
+  }
+  for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) bad |= nonfinite(g[i]);
+  note_found(bad);
+  __syncthreads();
+  raise_noted(flag);
 }
 
 // torch.clamp(omega / nrm, max=1): nrm 0 -> 1, nrm NaN -> NaN, nrm inf -> 0
@@ -243,7 +290,8 @@ __device__ __forceinline__ A clip_scale(A omega, A nrm) {
 template <typename A>
 __global__ __launch_bounds__(kThreads) void mt_sumsq_finish_kernel(OptArgs a, const A* __restrict__ partials,
                                                                     A* __restrict__ sumsq, A* __restrict__ scale,
-                                                                    float omega, float gs) {
+                                                                    float omega, float gs,
+                                                                    const float* __restrict__ dev_pre) {
   const int t = blockIdx.x;
   const A* __restrict__ p = partials + a.pbase;
   A acc = A(0);
@@ -252,33 +300,67 @@ __global__ __launch_bounds__(kThreads) void mt_sumsq_finish_kernel(OptArgs a, co
   if (threadIdx.x == 0) {
     const int leaf = a.tidx[t];
     sumsq[leaf] = s;
-    if (scale != nullptr) scale[leaf] = clip_scale(static_cast<A>(omega), static_cast<A>(gs) * sqrt(s));
+    if (scale != nullptr) {
+      A nrm = static_cast<A>(gs) * sqrt(s);
+      if (dev_pre != nullptr) nrm *= static_cast<A>(*dev_pre);  // the norm of the unscaled gradient
+      scale[leaf] = clip_scale(static_cast<A>(omega), nrm);
+    }
   }
 }
 
 // one workgroup: slot[0] = (accumulate ? slot[0] : 0) + sum_t sumsq[t] (fixed order),
-// slot[1] = gs * sqrt(slot[0]) (the gradient norm), slot[2] = omega > 0 ? clip scale : 1
+// slot[1] = gs * sqrt(slot[0]) (the gradient norm), slot[2] = omega > 0 ? clip scale : 1; with
+// dev_pre (the inverse loss scale) slot[1] and slot[2] are multiplied by it: the norm of the
+// unscaled gradient, and the one device scalar that unscales and clips in the update kernels
 template <typename A>
 __global__ __launch_bounds__(kThreads) void clip_total_kernel(const A* __restrict__ sumsq, int64_t n,
                                                                float* __restrict__ slot, int accumulate,
-                                                               float omega, float gs) {
+                                                               float omega, float gs,
+                                                               const float* __restrict__ dev_pre) {
   A acc = A(0);
   for (int64_t j = threadIdx.x; j < n; j += kThreads) acc += sumsq[j];
   const A s = block_sum(acc);
   if (threadIdx.x == 0) {
     const float total = (accumulate ? slot[0] : 0.f) + static_cast<float>(s);
-    const float nrm = gs * sqrtf(total);
+    float nrm = gs * sqrtf(total);
+    if (dev_pre != nullptr) nrm *= *dev_pre;
+    const float cs = omega > 0.f ? clip_scale(omega, nrm) : 1.f;
     slot[0] = total;
     slot[1] = nrm;
-    slot[2] = omega > 0.f ? clip_scale(omega, nrm) : 1.f;
+    slot[2] = dev_pre != nullptr ? *dev_pre * cs : cs;
   }
 }
 
-__global__ void adam_advance_kernel(float* dev, float b1, float b2) {
+__global__ void adam_advance_kernel(float* dev, float b1, float b2, const int32_t* dev_skip) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (dev_skip != nullptr && *dev_skip != 0) return;  // a skipped step does not count
     dev[1] *= b1;
     dev[2] *= b2;
   }
+}
+
+// GradScaler's rule on the scaler's device block (api.h: loss_scale_update), one thread
+__global__ void loss_scale_update_kernel(int32_t* __restrict__ blk, float growth, float backoff, int interval,
+                                         float min_scale, float max_scale) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float* f = reinterpret_cast<float*>(blk);
+  float scale = f[0];
+  int tracker = blk[2];
+  const int flag = blk[5];
+  if (flag != 0) {
+    scale *= backoff;
+    tracker = 0;
+    blk[3] += 1;
+  } else if (++tracker == interval) {
+    scale *= growth;
+    tracker = 0;
+  }
+  scale = fminf(fmaxf(scale, min_scale), max_scale);
+  f[0] = scale;
+  f[1] = 1.f / scale;
+  blk[2] = tracker;
+  blk[4] = flag != 0 ? 1 : 0;
+  blk[5] = 0;
 }
 
 }  // namespace
@@ -291,15 +373,17 @@ void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
   if (m.size() != numel.size() || v.size() != numel.size()) throw std::runtime_error("mt_adam: need m and v");
   for_each_group(param, grad, m, v, {}, master, numel, [&](const OptArgs& a, int blocks) {
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_adam", [&](auto p, auto g, auto s, auto master) {
-      mt_adam_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
-                     decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+        mt_adam_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                       decltype(master)::value, decltype(skip)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      });
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }
 
-void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream) {
-  adam_advance_kernel<<<1, 64, 0, stream>>>(dev, beta1, beta2);
+void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream, const int32_t* dev_skip) {
+  adam_advance_kernel<<<1, 64, 0, stream>>>(dev, beta1, beta2, dev_skip);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 
@@ -312,8 +396,10 @@ void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& g
     throw std::runtime_error("mt_sgd: momentum needs buffers");
   for_each_group(param, grad, buf, {}, {}, master, numel, [&](const OptArgs& a, int blocks) {
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_sgd", [&](auto p, auto g, auto s, auto master) {
-      mt_sgd_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
-                    decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+        mt_sgd_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                      decltype(master)::value, decltype(skip)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      });
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
@@ -329,7 +415,8 @@ int64_t sumsq_partials(const std::vector<int64_t>& numel) {
 namespace {
 template <typename G>
 void leaf_sumsq_impl(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, void* partials,
-                     void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream) {
+                     void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream,
+                     int32_t* flag, const float* dev_pre) {
   using A = typename Acc<G>::type;
   bool empty = false;
   for (int64_t n : numel) empty = empty || n <= 0;
@@ -353,29 +440,55 @@ void leaf_sumsq_impl(const std::vector<uintptr_t>& grad, const std::vector<int64
     }
   }
   for_each_group(grad, grad, {}, {}, {}, {}, numel, [&](const OptArgs& a, int blocks) {
-    mt_sumsq_partial_kernel<G><<<blocks, kThreads, 0, stream>>>(a, static_cast<A*>(partials));
+    dispatch_bool(flag != nullptr, [&](auto check) {
+      mt_sumsq_partial_kernel<G, decltype(check)::value><<<blocks, kThreads, 0, stream>>>(a, static_cast<A*>(partials), flag);
+    });
     FLUXMPI_HIP_CHECK(hipGetLastError());
     mt_sumsq_finish_kernel<A><<<a.n, kThreads, 0, stream>>>(a, static_cast<const A*>(partials), static_cast<A*>(sumsq),
-                                                            static_cast<A*>(scale), omega, grad_scale);
+                                                            static_cast<A*>(scale), omega, grad_scale, dev_pre);
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });
 }
 }  // namespace
 
 void mt_leaf_sumsq(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
-                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream) {
+                   void* partials, void* sumsq, void* scale, float omega, float grad_scale, hipStream_t stream,
+                   int32_t* nonfinite_flag, const float* dev_pre) {
   dispatch_float64(
       g_dtype, [&] { return "mt_leaf_sumsq: unsupported gradient dtype " + std::to_string(g_dtype); }, [&](auto t) {
-        leaf_sumsq_impl<typename decltype(t)::type>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream);
+        leaf_sumsq_impl<typename decltype(t)::type>(grad, numel, partials, sumsq, scale, omega, grad_scale, stream,
+                                                    nonfinite_flag, dev_pre);
       });
 }
 
+void mt_check_finite(const std::vector<uintptr_t>& grad, const std::vector<int64_t>& numel, int g_dtype,
+                     int32_t* flag, hipStream_t stream) {
+  if (flag == nullptr) throw std::runtime_error("mt_check_finite: needs the flag");
+  dispatch_float64(
+      g_dtype, [&] { return "mt_check_finite: unsupported gradient dtype " + std::to_string(g_dtype); }, [&](auto t) {
+        for_each_group(grad, grad, {}, {}, {}, {}, numel, [&](const OptArgs& a, int blocks) {
+          mt_check_finite_kernel<typename decltype(t)::type><<<blocks, kThreads, 0, stream>>>(a, flag);
+          FLUXMPI_HIP_CHECK(hipGetLastError());
+        });
+      });
+}
+
+void loss_scale_update(void* block, float growth, float backoff, int interval, float min_scale, float max_scale,
+                       hipStream_t stream) {
+  if (block == nullptr) throw std::runtime_error("loss_scale_update: needs the scaler block");
+  loss_scale_update_kernel<<<1, 64, 0, stream>>>(static_cast<int32_t*>(block), growth, backoff, interval, min_scale,
+                                                 max_scale);
+  FLUXMPI_HIP_CHECK(hipGetLastError());
+}
+
 void clip_total(const void* sumsq, int64_t n, int acc_dtype, float* slot, int accumulate, float omega,
-                float grad_scale, hipStream_t stream) {
+                float grad_scale, hipStream_t stream, const float* dev_pre) {
   if (acc_dtype == kF32)
-    clip_total_kernel<float><<<1, kThreads, 0, stream>>>(static_cast<const float*>(sumsq), n, slot, accumulate, omega, grad_scale);
+    clip_total_kernel<float><<<1, kThreads, 0, stream>>>(static_cast<const float*>(sumsq), n, slot, accumulate, omega,
+                                                         grad_scale, dev_pre);
   else if (acc_dtype == kF64)
-    clip_total_kernel<double><<<1, kThreads, 0, stream>>>(static_cast<const double*>(sumsq), n, slot, accumulate, omega, grad_scale);
+    clip_total_kernel<double><<<1, kThreads, 0, stream>>>(static_cast<const double*>(sumsq), n, slot, accumulate, omega,
+                                                          grad_scale, dev_pre);
   else
     throw std::runtime_error("clip_total: sums are fp32 or fp64");
   FLUXMPI_HIP_CHECK(hipGetLastError());

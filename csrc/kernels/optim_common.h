@@ -59,6 +59,47 @@ __device__ __forceinline__ Chunk chunk_of(const OptArgs& a) {
   return {t, c, a.start[t + 1] - a.start[t], base, base + kChunk < n ? base + kChunk : n};
 }
 
+// The step's skip predicate (loss scaling: a non-finite gradient calls the whole step off): one
+// wave-uniform load of *dev_skip; a kernel leaves on `true` before its first load of tensor data.
+// SKIP == false (dev_skip == nullptr, the launchers' choice) compiles to nothing.
+template <bool SKIP>
+__device__ __forceinline__ bool step_skipped(const int32_t* dev_skip) {
+  if constexpr (SKIP) return *dev_skip != 0;
+  else return false;
+}
+
+// inf or NaN: the exponent field all ones, read off the bits (exact, no arithmetic)
+__device__ __forceinline__ bool nonfinite(f16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7c00u) == 0x7c00u; }
+__device__ __forceinline__ bool nonfinite(bf16 x) { return (__builtin_bit_cast(uint16_t, x) & 0x7f80u) == 0x7f80u; }
+__device__ __forceinline__ bool nonfinite(float x) {
+  return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u;
+}
+__device__ __forceinline__ bool nonfinite(double x) {
+  return (__builtin_bit_cast(uint64_t, x) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+}
+
+// Block-wide OR of `found` in two halves around ONE barrier: note_found leaves each wave's OR (a
+// ballot: no LDS traffic inside the wave) in LDS, raise_noted — after a __syncthreads() — has one
+// lane of a workgroup that found something store the sticky flag. A kernel that reduces anyway
+// (block_sum has a barrier inside) puts its reduction between the two and pays no second barrier.
+__device__ __forceinline__ int* found_slots() {
+  __shared__ int wave_found[kThreads / 64];
+  return wave_found;
+}
+__device__ __forceinline__ void note_found(bool found) {
+  const bool any = __ballot(found) != 0;  // wave-uniform
+  if ((threadIdx.x & 63) == 0) found_slots()[threadIdx.x >> 6] = any;
+}
+__device__ __forceinline__ void raise_noted(int32_t* __restrict__ flag) {
+  if (threadIdx.x == 0) {
+    const int* w = found_slots();
+    int any = 0;
+#pragma unroll
+    for (int i = 0; i < kThreads / 64; ++i) any |= w[i];
+    if (any) flag[0] = 1;
+  }
+}
+
 // sum over the workgroup, valid in every thread. Wave level: DPP (fp32) / xor shuffles (fp64), every
 // lane takes part (EXEC full); then the four wave totals through LDS, added in wave order. A second
 // call in one kernel needs a __syncthreads() in front: it writes the same LDS slots.

@@ -23,7 +23,9 @@
 // launch of its own with one workgroup per leaf that leaves q in the ratio table for the apply
 // kernel to read. The ratio each leaf used is written to ratio[tidx] (RuleHyper::tscale) either
 // way. lr and beta^t come from the host arguments or the device block {lr[, b1^t, b2^t]}, as for
-// Adam; nothing is read back, so a step is HIP-graph capturable.
+// Adam; nothing is read back, so a step is HIP-graph capturable. With RuleHyper::dev_skip (loss
+// scaling) every workgroup of all three kernels first reads that one device word and, when it is set,
+// returns: moments, velocity, parameters and the ratio table keep the previous step's values.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -94,9 +96,10 @@ __device__ __forceinline__ void lw_fold(const A* __restrict__ part, int nb, A& s
   block_sum2(ax, ay, sx, sy);
 }
 
-template <bool LAMB, typename P, typename G, typename S, bool MASTER>
+template <bool LAMB, bool SKIP, typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper h) {
   using C = typename Comp<P>::type;
+  if (step_skipped<SKIP>(h.dev_skip)) return;  // LAMB: m and v stay; the partials too (nobody reads them)
   const Chunk ch = chunk_of(a);
   const int t = ch.t, c = ch.c, nb = ch.nb;
   const LwScalars<C> s = lw_scalars<C>(h, LAMB);
@@ -159,8 +162,9 @@ __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper
 }
 
 // the fold as a launch of its own: workgroup t leaves leaf t's ratio in the table
-template <bool LAMB, typename C>
+template <bool LAMB, bool SKIP, typename C>
 __global__ __launch_bounds__(kThreads) void lw_fold_kernel(OptArgs a, RuleHyper h) {
+  if (step_skipped<SKIP>(h.dev_skip)) return;  // the ratio table stays as the previous step wrote it
   const int t = blockIdx.x;
   const LwScalars<C> s = lw_scalars<C>(h, LAMB);
   C sx, sy;
@@ -169,9 +173,10 @@ __global__ __launch_bounds__(kThreads) void lw_fold_kernel(OptArgs a, RuleHyper 
 }
 
 // FOLD: the fold is this kernel's prologue; else q is read from the ratio table
-template <bool LAMB, bool FOLD, typename P, typename G, typename S, bool MASTER>
+template <bool LAMB, bool FOLD, bool SKIP, typename P, typename G, typename S, bool MASTER>
 __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper h) {
   using C = typename Comp<P>::type;
+  if (step_skipped<SKIP>(h.dev_skip)) return;  // before the fold: the ratio table stays too
   const Chunk ch = chunk_of(a);
   const int t = ch.t, c = ch.c;
   const LwScalars<C> s = lw_scalars<C>(h, LAMB);
@@ -283,15 +288,18 @@ void launch_layerwise(const std::vector<uintptr_t>& param, const std::vector<uin
       using G = typename decltype(g)::type;
       using S = typename decltype(s)::type;
       constexpr bool M = decltype(master)::value;
-      lw_stats_kernel<LAMB, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
-      FLUXMPI_HIP_CHECK(hipGetLastError());
-      if (own_launch) {
-        lw_fold_kernel<LAMB, typename Comp<P>::type><<<a.n, kThreads, 0, stream>>>(a, h);
+      dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+        constexpr bool K = decltype(skip)::value;
+        lw_stats_kernel<LAMB, K, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
         FLUXMPI_HIP_CHECK(hipGetLastError());
-        lw_apply_kernel<LAMB, false, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
-      } else {
-        lw_apply_kernel<LAMB, true, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
-      }
+        if (own_launch) {
+          lw_fold_kernel<LAMB, K, typename Comp<P>::type><<<a.n, kThreads, 0, stream>>>(a, h);
+          FLUXMPI_HIP_CHECK(hipGetLastError());
+          lw_apply_kernel<LAMB, false, K, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
+        } else {
+          lw_apply_kernel<LAMB, true, K, P, G, S, M><<<blocks, kThreads, 0, stream>>>(a, h);
+        }
+      });
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });

@@ -22,7 +22,9 @@
 //
 // lr, b1^t and b2^t come from the host arguments or, when given, from the device block
 // {lr, b1^t, b2^t} ({lr} for the rules without bias correction): Adam's scheme, advanced by
-// adam_advance, so a captured graph replays correct steps. No atomics, no LDS.
+// adam_advance, so a captured graph replays correct steps. No atomics, no LDS. With
+// RuleHyper::dev_skip (loss scaling) a workgroup first reads that one device word and, when it is
+// set, returns before it touches any tensor.
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -170,9 +172,10 @@ struct RuleElem {
   }
 };
 
-template <template <typename> class RuleT, typename P, typename G, typename S, bool MASTER>
+template <template <typename> class RuleT, typename P, typename G, typename S, bool MASTER, bool SKIP>
 __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper h) {
   using C = typename Comp<P>::type;
+  if (step_skipped<SKIP>(h.dev_skip)) return;
   using R = RuleT<C>;
   constexpr int NS = R::kStates;
   const Chunk ch = chunk_of(a);
@@ -259,8 +262,10 @@ void launch_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_
   const bool has_master = !master.empty();
   for_each_group(param, grad, s1, s2, s3, master, numel, [&](const OptArgs& a, int blocks) {
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_rule", [&](auto p, auto g, auto s, auto master) {
-      mt_rule_kernel<RuleT, typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
-                     decltype(master)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+        mt_rule_kernel<RuleT, typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
+                       decltype(master)::value, decltype(skip)::value><<<blocks, kThreads, 0, stream>>>(a, h);
+      });
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });

@@ -21,6 +21,7 @@ and as the numerics oracle in tests.
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import os
 
 import torch
@@ -71,6 +72,33 @@ def get(required: bool = True):
             f"{_ERR!r}. Run `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`."
         )
     return mod
+
+
+_SCALE = None
+
+
+def scale():
+    """The ``_C_scale`` module: the fused optimisers' entries with the loss-scaling arguments
+    (``dev_skip``, ``nonfinite_flag``, ``dev_pre``), ``mt_check_finite`` and ``loss_scale_update``.
+
+    It is a second module of the shared object ``_C`` was loaded from (its ``PyInit__C_scale``), so
+    ``_C`` itself keeps the surface ``tests/golden/c_api_surface.json`` records. Missing: an error,
+    as for ``_C``."""
+    global _SCALE
+    if _SCALE is None:
+        C = get(required=True)
+        if C is None:
+            raise NativeExtensionError("fluxmpi_amd._C_scale needs the native extension fluxmpi_amd._C")
+        spec = importlib.util.spec_from_file_location("fluxmpi_amd._C_scale", C.__file__)
+        try:
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        except Exception as e:
+            raise NativeExtensionError(
+                f"fluxmpi_amd._C_scale (the loss-scaling entries of {C.__file__}) failed to load: {e!r}. "
+                "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
+        _SCALE = mod
+    return _SCALE
 
 
 def require_for(t: torch.Tensor):

@@ -59,6 +59,31 @@ def _ptr(t: torch.Tensor | None) -> int:
     return t.data_ptr() if t is not None else 0
 
 
+def _call(C, name: str, *args, _scaling: dict, **kw):
+    """Call the native entry ``name``: ``_C``'s, or, when one of the loss-scaling arguments
+    ``_scaling`` (device addresses; 0: not given) is there, ``_C_scale``'s with those arguments.
+    ``_C`` keeps its recorded surface; the loss-scaling surface is a second module of the same
+    library (``ops._ext.scale``)."""
+    given = {k: v for k, v in _scaling.items() if v}
+    if given:
+        return getattr(_ext.scale(), name)(*args, **kw, **given)
+    return getattr(C, name)(*args, **kw)
+
+
+def _skip_ptr(dev_skip) -> int:
+    """Device address of the optional skip predicate: one int32, non-zero calls the launch off."""
+    if dev_skip is None:
+        return 0
+    if dev_skip.dtype != torch.int32 or dev_skip.numel() < 1:
+        raise TypeError(f"fused optimiser: dev_skip is an int32 tensor of one entry, got {dev_skip.dtype}")
+    return dev_skip.data_ptr()
+
+
+def _skipped(dev_skip) -> bool:
+    """The reference path's reading of the skip predicate (a host read: CPU tensors)."""
+    return bool(_skip_ptr(dev_skip)) and int(dev_skip.reshape(-1)[0]) != 0
+
+
 def _dtype_groups(name: str, params, grads, states, masters, slots: int) -> list:
     """The call's leaves by (param, grad, state, master) dtype, one ``(idx, pd, head)`` per group, checked
     before anything is launched. ``idx``: the group's positions in the call's lists; ``pd``: its
@@ -90,7 +115,8 @@ def _dtype_groups(name: str, params, grads, states, masters, slots: int) -> list
 def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
           bc1: float, bc2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
-          tscale: torch.Tensor | None = None, clip_delta: float = 0.0) -> None:
+          tscale: torch.Tensor | None = None, clip_delta: float = 0.0,
+          dev_skip: torch.Tensor | None = None) -> None:
     """In-place fused Adam over lists of tensors.
 
     ``bc1``/``bc2`` are ``1 - beta^t`` (Optimisers.jl keeps ``beta^t`` in the
@@ -101,6 +127,9 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     ``g = clamp(g * grad_scale * dev_gscale * tscale[i], -clip_delta, clip_delta)`` with
     ``tscale`` one device scalar per leaf of ``params`` (fp32; fp64 for fp64 parameters; see
     :func:`sumsq_`) and ``clip_delta == 0`` meaning no clamp.
+
+    ``dev_skip``: one int32 on the device (loss scaling's non-finite flag, :func:`check_finite_`).
+    When it is non-zero the launch reads and writes no tensor: the step is called off.
     """
     if not params:
         return
@@ -108,9 +137,10 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
         C = _ext.get(required=True)
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
         for idx, pd, head in _dtype_groups("Adam", params, grads, [exp_avgs, exp_avg_sqs], masters, 2):
-            C.mt_adam(*head, float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
-                      float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), stream,
-                      tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
+            _call(C, "mt_adam", *head, float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
+                  float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), stream,
+                  tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta),
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -119,7 +149,7 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
         grad_scale = grad_scale * float(dev_gscale)
     adam_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bc1=bc1,
                     bc2=bc2, weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, tscale=tscale,
-                    clip_delta=clip_delta)
+                    clip_delta=clip_delta, dev_skip=dev_skip)
 
 
 def _clip_reference(g, i, tscale, clip_delta):
@@ -131,8 +161,10 @@ def _clip_reference(g, i, tscale, clip_delta):
 
 
 def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps, bc1, bc2,
-                    weight_decay=0.0, grad_scale=1.0, masters=None, tscale=None, clip_delta=0.0):
+                    weight_decay=0.0, grad_scale=1.0, masters=None, tscale=None, clip_delta=0.0, dev_skip=None):
     """PyTorch reference of the fused kernel (compute in fp32, or fp64 for fp64 params)."""
+    if _skipped(dev_skip):
+        return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         g = grads[i].to(ct) * grad_scale if grad_scale != 1.0 else grads[i].to(ct)
@@ -151,13 +183,15 @@ def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, e
         p.copy_(x)
 
 
-def adam_advance_(dev_hyper: torch.Tensor, beta1: float, beta2: float) -> None:
-    """``beta^t *= beta`` on the device hyper block (after the step's Adam launches)."""
+def adam_advance_(dev_hyper: torch.Tensor, beta1: float, beta2: float, *,
+                  dev_skip: torch.Tensor | None = None) -> None:
+    """``beta^t *= beta`` on the device hyper block (after the step's Adam launches); not when
+    ``dev_skip`` is non-zero: a skipped step does not count."""
     if dev_hyper.is_cuda:
         C = _ext.get(required=True)
-        C.adam_advance(dev_hyper.data_ptr(), float(beta1), float(beta2),
-                       torch.cuda.current_stream(dev_hyper.device).cuda_stream)
-    else:
+        _call(C, "adam_advance", dev_hyper.data_ptr(), float(beta1), float(beta2),
+              torch.cuda.current_stream(dev_hyper.device).cuda_stream, _scaling={"dev_skip": _skip_ptr(dev_skip)})
+    elif not _skipped(dev_skip):
         dev_hyper[1] *= beta1
         dev_hyper[2] *= beta2
 
@@ -165,9 +199,11 @@ def adam_advance_(dev_hyper: torch.Tensor, beta1: float, beta2: float) -> None:
 def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: bool = False,
          weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
          dev_lr: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
-         tscale: torch.Tensor | None = None, clip_delta: float = 0.0) -> None:
-    """Fused Descent / Momentum / Nesterov (Optimisers.jl semantics); ``dev_gscale``, ``tscale``
-    and ``clip_delta`` as in :func:`adam_` (the clipped gradient is formed before weight decay)."""
+         tscale: torch.Tensor | None = None, clip_delta: float = 0.0,
+         dev_skip: torch.Tensor | None = None) -> None:
+    """Fused Descent / Momentum / Nesterov (Optimisers.jl semantics); ``dev_gscale``, ``tscale``,
+    ``clip_delta`` and ``dev_skip`` as in :func:`adam_` (the clipped gradient is formed before
+    weight decay)."""
     if not params:
         return
     if params[0].is_cuda:
@@ -175,20 +211,24 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
         # without momentum the buffers are not read: Optimisers.Descent has none
         for idx, pd, head in _dtype_groups("SGD", params, grads, [bufs] if momentum != 0.0 else [], masters, 1):
-            C.mt_sgd(*head, float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(nesterov)),
-                     _ptr(dev_lr), stream, dev_gscale=_ptr(dev_gscale),
-                     tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta))
+            _call(C, "mt_sgd", *head, float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                  int(bool(nesterov)),
+                  _ptr(dev_lr), stream, dev_gscale=_ptr(dev_gscale),
+                  tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta),
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
         return
     if dev_lr is not None:
         lr = float(dev_lr.reshape(-1)[0])
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     sgd_reference_(params, grads, bufs, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay,
-                   grad_scale=grad_scale, masters=masters, tscale=tscale, clip_delta=clip_delta)
+                   grad_scale=grad_scale, masters=masters, tscale=tscale, clip_delta=clip_delta, dev_skip=dev_skip)
 
 
 def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, weight_decay=0.0, grad_scale=1.0,
-                   masters=None, tscale=None, clip_delta=0.0):
+                   masters=None, tscale=None, clip_delta=0.0, dev_skip=None):
+    if _skipped(dev_skip):
+        return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         x = masters[i].to(ct) if masters is not None else p.to(ct)
@@ -235,7 +275,7 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
           rho: float | None = None, eps: float = 0.0, bt1: float = 0.0, bt2: float = 0.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
           tscale: torch.Tensor | None = None, clip_delta: float = 0.0, weight_decay: float = 0.0,
-          grad_scale: float = 1.0) -> None:
+          grad_scale: float = 1.0, dev_skip: torch.Tensor | None = None) -> None:
     """In-place fused step of one of :data:`RULES` over lists of tensors (``optim_rules.hip``).
 
     ``states``: one list of tensors per state slot of the rule, in the order of its Optimisers.jl
@@ -245,8 +285,8 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
     Optimisers.jl keeps them in the state and starts them at ``beta``); ``dev_hyper`` (fp32
     ``[lr, beta1^t, beta2^t]``, or ``[lr]`` for the rules without ``beta^t``) overrides them for
     HIP-graph replay, advanced by :func:`adam_advance_`. ``weight_decay`` adds ``wd * x`` to the
-    rule's ``dx'`` (an ``OptimiserChain(rule, WeightDecay)``); the clip arguments are
-    :func:`adam_`'s."""
+    rule's ``dx'`` (an ``OptimiserChain(rule, WeightDecay)``); the clip arguments and ``dev_skip``
+    are :func:`adam_`'s."""
     code, ns, has_bt = _rule_info(kind)
     if rho is not None:
         beta1 = rho
@@ -264,9 +304,10 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
         C = _ext.get(required=True)
         stream = torch.cuda.current_stream(params[0].device).cuda_stream
         for idx, pd, head in _dtype_groups(kind, params, grads, states, masters, 3):
-            C.mt_rule(code, *head, float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
-                      float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale),
-                      _tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), float(clip_delta), stream)
+            _call(C, "mt_rule", code, *head, float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
+                  float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale),
+                  _tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), float(clip_delta), stream,
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -277,14 +318,17 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
         grad_scale = grad_scale * float(dev_gscale)
     rule_reference_(kind, params, grads, states, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
                     masters=masters, tscale=tscale, clip_delta=clip_delta, weight_decay=weight_decay,
-                    grad_scale=grad_scale)
+                    grad_scale=grad_scale, dev_skip=dev_skip)
 
 
 def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta2=0.0, rho=None, eps=0.0, bt1=0.0,
-                    bt2=0.0, masters=None, tscale=None, clip_delta=0.0, weight_decay=0.0, grad_scale=1.0):
+                    bt2=0.0, masters=None, tscale=None, clip_delta=0.0, weight_decay=0.0, grad_scale=1.0,
+                    dev_skip=None):
     """PyTorch reference of :func:`rule_`, term by term as the rules of ``optimisers`` write them
     (compute in fp32, or fp64 for fp64 params): the CPU path and the kernels' oracle."""
     _, ns, _ = _rule_info(kind)
+    if _skipped(dev_skip):
+        return
     if rho is not None:
         beta1 = rho
     b1, b2 = beta1, beta2
@@ -345,7 +389,7 @@ def layerwise_workspace(params) -> int:
 
 
 def _layerwise_(kind, params, grads, states, hyper, *, weight_decay, grad_scale, masters, dev_hyper, dev_gscale,
-                ratios, workspace):
+                ratios, workspace, dev_skip=None):
     """The GPU side of :func:`lars_` / :func:`lamb_`: one ``mt_rule`` call per dtype group, each leaf's
     slice of the workspace in the ``s3`` slot and the ratio table in ``tscale``."""
     C = _ext.get(required=True)
@@ -378,10 +422,14 @@ def _layerwise_(kind, params, grads, states, hyper, *, weight_decay, grad_scale,
             if params[i].numel() == 0:
                 table[k:k + 1].fill_(1)  # a leaf without elements reaches no kernel: ratio 1
         head[4] = part  # the s3 slot
-        C.mt_rule(LAYERWISE[kind], *head, float(hyper["lr"]), float(hyper["beta1"]), float(hyper["beta2"]),
-                  float(hyper["eps"]), float(hyper.get("bt1", 0.0)), float(hyper.get("bt2", 0.0)), float(weight_decay),
-                  float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), table.data_ptr(), 0.0, stream)
+        _call(C, "mt_rule", LAYERWISE[kind], *head, float(hyper["lr"]), float(hyper["beta1"]), float(hyper["beta2"]),
+              float(hyper["eps"]), float(hyper.get("bt1", 0.0)), float(hyper.get("bt2", 0.0)), float(weight_decay),
+              float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), table.data_ptr(), 0.0, stream,
+              _scaling={"dev_skip": _skip_ptr(dev_skip)})
         if ratios is not None and table is not ratios:
+            if dev_skip is not None:
+                raise ValueError(f"fused {kind}: with dev_skip the ratios of a call of several dtype groups cannot "
+                                 "be kept through a skipped step; call once per dtype group")
             ratios[torch.tensor(idx, device=dev)] = table.to(ratios.dtype)
 
 
@@ -397,7 +445,7 @@ def _check_layerwise(kind, params, grads, states, masters, ratios):
 def lars_(params, grads, bufs, *, lr: float, momentum: float, trust: float, weight_decay: float = 0.0,
           eps: float = 0.0, grad_scale: float = 1.0, masters=None, dev_hyper: torch.Tensor | None = None,
           dev_gscale: torch.Tensor | None = None, ratios: torch.Tensor | None = None,
-          workspace: torch.Tensor | None = None) -> None:
+          workspace: torch.Tensor | None = None, dev_skip: torch.Tensor | None = None) -> None:
     """In-place fused LARS over lists of tensors, every leaf adapted (``optim_layerwise.hip``):
     ``q = trust·‖x‖ / (‖g‖ + wd·‖x‖ + eps)`` (1 when either norm is 0), ``vel = momentum·vel +
     lr·q·(g + wd·x)``, ``x -= vel`` with ``g = grads[i] * grad_scale * dev_gscale`` and ``x`` the
@@ -406,7 +454,8 @@ def lars_(params, grads, bufs, *, lr: float, momentum: float, trust: float, weig
 
     ``dev_hyper``: fp32 ``[lr]`` on the device. ``ratios``: optional table (fp32; fp64 for fp64
     parameters) that receives ``q`` of each leaf of ``params``. ``workspace``: scratch of
-    :func:`layerwise_workspace` entries of the same dtype, allocated here when not given."""
+    :func:`layerwise_workspace` entries of the same dtype, allocated here when not given.
+    ``dev_skip``: as in :func:`adam_`; a skipped step also leaves ``ratios`` as they were."""
     states = [list(bufs)]
     _check_layerwise("lars", params, grads, states, masters, ratios)
     if not params:
@@ -414,20 +463,21 @@ def lars_(params, grads, bufs, *, lr: float, momentum: float, trust: float, weig
     if params[0].is_cuda:
         _layerwise_("lars", params, grads, states, {"lr": lr, "beta1": momentum, "beta2": trust, "eps": eps},
                     weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, dev_hyper=dev_hyper,
-                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace)
+                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace, dev_skip=dev_skip)
         return
     if dev_hyper is not None:
         lr = float(dev_hyper.reshape(-1)[0])
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     lars_reference_(params, grads, bufs, lr=lr, momentum=momentum, trust=trust, weight_decay=weight_decay, eps=eps,
-                    grad_scale=grad_scale, masters=masters, ratios=ratios)
+                    grad_scale=grad_scale, masters=masters, ratios=ratios, dev_skip=dev_skip)
 
 
 def lamb_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta2: float, eps: float,
           bt1: float, bt2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
-          ratios: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> None:
+          ratios: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+          dev_skip: torch.Tensor | None = None) -> None:
     """In-place fused LAMB over lists of tensors, every leaf adapted (``optim_layerwise.hip``):
     Adam's ``m`` and ``v``, ``u = m/(1-bt1) / (sqrt(v/(1-bt2)) + eps) + wd·x``, ``q = ‖x‖/‖u‖`` (1
     when either norm is 0), ``x -= lr·q·u``. ``bt1`` / ``bt2`` are ``beta^t``; ``dev_hyper`` (fp32
@@ -442,7 +492,7 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
         _layerwise_("lamb", params, grads, states,
                     {"lr": lr, "beta1": beta1, "beta2": beta2, "eps": eps, "bt1": bt1, "bt2": bt2},
                     weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, dev_hyper=dev_hyper,
-                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace)
+                    dev_gscale=dev_gscale, ratios=ratios, workspace=workspace, dev_skip=dev_skip)
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -450,7 +500,8 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
-                    weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, ratios=ratios)
+                    weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, ratios=ratios,
+                    dev_skip=dev_skip)
 
 
 def _norm(t: torch.Tensor) -> torch.Tensor:
@@ -458,8 +509,10 @@ def _norm(t: torch.Tensor) -> torch.Tensor:
 
 
 def lars_reference_(params, grads, bufs, *, lr, momentum, trust, weight_decay=0.0, eps=0.0, grad_scale=1.0,
-                    masters=None, ratios=None):
+                    masters=None, ratios=None, dev_skip=None):
     """PyTorch reference of :func:`lars_` (compute in fp32, or fp64 for fp64 params)."""
+    if _skipped(dev_skip):
+        return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         x = masters[i].to(ct) if masters is not None else p.to(ct)
@@ -478,9 +531,11 @@ def lars_reference_(params, grads, bufs, *, lr, momentum, trust, weight_decay=0.
 
 
 def lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps, bt1, bt2, weight_decay=0.0,
-                    grad_scale=1.0, masters=None, ratios=None):
+                    grad_scale=1.0, masters=None, ratios=None, dev_skip=None):
     """PyTorch reference of :func:`lamb_` (compute in fp32, or fp64 for fp64 params): ``u`` is formed
     from the moments as stored, in the state's dtype."""
+    if _skipped(dev_skip):
+        return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
         x = masters[i].to(ct) if masters is not None else p.to(ct)
@@ -506,7 +561,8 @@ def sumsq_partials(grads) -> int:
 
 
 def sumsq_(grads, out: torch.Tensor, *, scales: torch.Tensor | None = None, omega: float = 0.0,
-           grad_scale: float = 1.0, partials: torch.Tensor | None = None) -> None:
+           grad_scale: float = 1.0, partials: torch.Tensor | None = None, flag: torch.Tensor | None = None,
+           dev_pre: torch.Tensor | None = None) -> None:
     """``out[i] = sum(grads[i] ** 2)`` for a list of dense gradients of one dtype, deterministically
     (two launches per 24 leaves, no float atomics: bit-identical from run to run), and, with
     ``scales``, the ClipNorm factors ``scales[i] = min(1, omega / (grad_scale * sqrt(out[i])))``
@@ -515,6 +571,12 @@ def sumsq_(grads, out: torch.Tensor, *, scales: torch.Tensor | None = None, omeg
     ``out`` / ``scales`` / ``partials`` are fp32 (fp64 for fp64 gradients) tensors on the
     gradients' device with ``len(grads)`` (``partials``: :func:`sumsq_partials`) entries;
     ``partials`` is scratch, allocated here when not given. No host read: graph-capturable.
+
+    ``flag`` (one int32): the same pass runs :func:`check_finite_`'s test on every element it reads,
+    so an engine that takes norms reads its gradients once; ``out`` and ``scales`` are the bits of
+    the call without it. ``dev_pre`` (one fp32 on the device, the inverse loss scale) is multiplied
+    into the norm — ``scales[i] = min(1, omega / (grad_scale * dev_pre * sqrt(out[i])))``, the
+    factors of the unscaled gradient; ``out`` stays the raw sum.
     """
     if not grads:
         return
@@ -534,14 +596,120 @@ def sumsq_(grads, out: torch.Tensor, *, scales: torch.Tensor | None = None, omeg
             partials = torch.empty(max(need, 1), dtype=at, device=grads[0].device)
         elif partials.dtype != at or partials.numel() < need or not partials.is_contiguous():
             raise TypeError(f"sumsq_: partials must be a contiguous {at} tensor with at least {need} entries")
-        C.mt_leaf_sumsq([g.data_ptr() for g in grads], [g.numel() for g in grads], DTYPE_CODE[gd],
-                        partials.data_ptr(), out.data_ptr(), _ptr(scales),
-                        float(omega), float(grad_scale), torch.cuda.current_stream(grads[0].device).cuda_stream)
+        _call(C, "mt_leaf_sumsq", [g.data_ptr() for g in grads], [g.numel() for g in grads], DTYPE_CODE[gd],
+              partials.data_ptr(), out.data_ptr(), _ptr(scales),
+              float(omega), float(grad_scale), torch.cuda.current_stream(grads[0].device).cuda_stream,
+              _scaling={"nonfinite_flag": _flag_ptr(flag), "dev_pre": _pre_ptr(dev_pre)})
         return
     ss = torch.stack([(g.to(at) * g.to(at)).sum() for g in grads])
     out[:n].copy_(ss)
     if scales is not None:
-        scales[:n].copy_(clip_scales_reference(ss, omega, grad_scale).to(at))
+        nrm = grad_scale * torch.sqrt(ss)
+        if dev_pre is not None:
+            nrm = nrm * dev_pre.reshape(-1)[0].to(at)
+        scales[:n].copy_(torch.clamp(omega / nrm, max=1.0).to(at))
+    if flag is not None:
+        check_finite_reference_(grads, flag)
+
+
+def _flag_ptr(flag) -> int:
+    if flag is None:
+        return 0
+    if flag.dtype != torch.int32 or flag.numel() < 1:
+        raise TypeError(f"non-finite check: flag is an int32 tensor of one entry, got {flag.dtype}")
+    return flag.data_ptr()
+
+
+def _pre_ptr(dev_pre) -> int:
+    if dev_pre is None:
+        return 0
+    if dev_pre.dtype != torch.float32 or dev_pre.numel() < 1:
+        raise TypeError(f"dev_pre is an fp32 tensor of one entry, got {dev_pre.dtype}")
+    return dev_pre.data_ptr()
+
+
+def check_finite_(grads, flag: torch.Tensor) -> None:
+    """``flag[0] = 1`` if any element of any of ``grads`` is inf or NaN; untouched otherwise.
+
+    The test is exact and per element (exponent field all ones), not "the sum of squares came out
+    non-finite": a bf16 or fp32 gradient of 1e20 is finite while its square is not. ``flag`` (one
+    int32 on the gradients' device) is sticky: the checks of all buckets and dtypes of a step
+    accumulate into it and only :func:`loss_scale_update_` clears it. One launch per 24 leaves of a
+    dtype in the update kernels' job layout, no atomics, no host read: graph-capturable."""
+    if not grads:
+        return
+    if flag.dtype != torch.int32 or flag.numel() < 1 or flag.device != grads[0].device:
+        raise TypeError(f"check_finite_: flag is an int32 tensor of one entry on {grads[0].device}")
+    if not grads[0].is_cuda:
+        check_finite_reference_(grads, flag)
+        return
+    S = _ext.scale()
+    stream = torch.cuda.current_stream(grads[0].device).cuda_stream
+    by_dtype: dict = {}
+    for g in grads:
+        if g.dtype not in DTYPE_CODE or not g.dtype.is_floating_point or g.device != grads[0].device:
+            raise TypeError(f"check_finite_: unsupported gradient {g.dtype} on {g.device}")
+        by_dtype.setdefault(g.dtype, []).append(g)
+    for gd, gs in by_dtype.items():
+        S.mt_check_finite([g.data_ptr() for g in gs], [g.numel() for g in gs], DTYPE_CODE[gd], flag.data_ptr(), stream)
+
+
+def check_finite_reference_(grads, flag: torch.Tensor) -> None:
+    """PyTorch reference of :func:`check_finite_` (``torch.isfinite`` per element)."""
+    if any(g.numel() and not bool(torch.isfinite(g).all()) for g in grads):
+        flag.reshape(-1)[0] = 1
+
+
+# the scaler's device block (csrc/api.h: loss_scale_update): 8 int32 words, the first two fp32 bits
+LS_WORDS = 8
+LS_SCALE, LS_INV, LS_TRACKER, LS_SKIPPED, LS_LAST, LS_FLAG = range(6)
+
+
+def loss_scale_block(scale: float, device, *, tracker: int = 0, skipped: int = 0) -> torch.Tensor:
+    """A fresh scaler block on ``device``: ``scale``, its inverse, the counters; last-skipped and flag clear."""
+    blk = torch.zeros(LS_WORDS, dtype=torch.int32)
+    f = blk.view(torch.float32)
+    f[LS_SCALE] = scale
+    f[LS_INV] = 1.0 / f[LS_SCALE]
+    blk[LS_TRACKER], blk[LS_SKIPPED] = int(tracker), int(skipped)
+    return blk.to(device)
+
+
+def loss_scale_update_(block: torch.Tensor, *, growth: float, backoff: float, interval: int, min_scale: float,
+                       max_scale: float) -> None:
+    """``GradScaler``'s rule on the scaler block (:func:`loss_scale_block`), one thread on the device:
+    flag set → ``scale *= backoff``, tracker = 0, skipped += 1; flag clear → tracker += 1 and at
+    ``tracker == interval`` ``scale *= growth``, tracker = 0. Then the scale is clamped to
+    ``[min_scale, max_scale]``, its inverse stored, the flag copied to "last step skipped" and
+    cleared. A static scale is ``growth = backoff = 1``. No host read: graph-capturable."""
+    if block.dtype != torch.int32 or block.numel() < LS_WORDS or not block.is_contiguous():
+        raise TypeError(f"loss_scale_update_: block is a contiguous int32 tensor of {LS_WORDS} entries")
+    if block.is_cuda:
+        _ext.scale().loss_scale_update(block.data_ptr(), float(growth), float(backoff), int(interval), float(min_scale),
+                            float(max_scale), torch.cuda.current_stream(block.device).cuda_stream)
+        return
+    loss_scale_update_reference_(block, growth=growth, backoff=backoff, interval=interval, min_scale=min_scale,
+                                 max_scale=max_scale)
+
+
+def loss_scale_update_reference_(block: torch.Tensor, *, growth, backoff, interval, min_scale, max_scale) -> None:
+    """PyTorch reference of :func:`loss_scale_update_` on a CPU block, in fp32 as the kernel computes."""
+    f = block.view(torch.float32)
+    scale, flag = f[LS_SCALE].clone(), int(block[LS_FLAG])
+    if flag != 0:
+        scale = scale * torch.tensor(backoff, dtype=torch.float32)
+        block[LS_TRACKER] = 0
+        block[LS_SKIPPED] += 1
+    else:
+        block[LS_TRACKER] += 1
+        if int(block[LS_TRACKER]) == int(interval):
+            scale = scale * torch.tensor(growth, dtype=torch.float32)
+            block[LS_TRACKER] = 0
+    scale = torch.clamp(scale, torch.tensor(min_scale, dtype=torch.float32), torch.tensor(max_scale, dtype=torch.float32))
+    f[LS_SCALE] = scale
+    f[LS_INV] = 1.0 / scale
+    block[LS_LAST] = 1 if flag != 0 else 0
+    block[LS_FLAG] = 0
 
 
 def sumsq_reference(grads) -> torch.Tensor:
@@ -555,25 +723,33 @@ def clip_scales_reference(sumsq: torch.Tensor, omega: float, grad_scale: float =
 
 
 def clip_total_(sumsq: torch.Tensor, slot: torch.Tensor, *, accumulate: bool = False, omega: float = 0.0,
-                grad_scale: float = 1.0) -> None:
+                grad_scale: float = 1.0, dev_pre: torch.Tensor | None = None) -> None:
     """Fold per-leaf sums of squares into the fp32 device slot ``[sum, norm, scale]``:
     ``slot[0] = (slot[0] if accumulate else 0) + sum(sumsq)`` (fixed order), ``slot[1] = grad_scale *
     sqrt(slot[0])`` (the global gradient norm) and ``slot[2] = min(1, omega / slot[1])`` (1 when
-    ``omega <= 0``). ``slot[2:3]`` is the ``dev_gscale`` of a global-norm clipped update."""
+    ``omega <= 0``). ``slot[2:3]`` is the ``dev_gscale`` of a global-norm clipped update. With
+    ``dev_pre`` (one fp32 on the device, the inverse loss scale) ``slot[1]`` and ``slot[2]`` are
+    multiplied by it: the norm of the unscaled gradient, and one scalar that unscales and clips."""
     if slot.dtype != torch.float32 or slot.numel() < 3 or not slot.is_contiguous():
         raise TypeError("clip_total_: slot is a contiguous fp32 tensor of 3 entries")
     if sumsq.dtype not in (torch.float32, torch.float64) or not sumsq.is_contiguous():
         raise TypeError("clip_total_: sumsq is a contiguous fp32 or fp64 tensor")
     if sumsq.is_cuda:
         C = _ext.get(required=True)
-        C.clip_total(sumsq.data_ptr(), sumsq.numel(), DTYPE_CODE[sumsq.dtype], slot.data_ptr(), int(bool(accumulate)),
-                     float(omega), float(grad_scale), torch.cuda.current_stream(sumsq.device).cuda_stream)
+        _call(C, "clip_total", sumsq.data_ptr(), sumsq.numel(), DTYPE_CODE[sumsq.dtype], slot.data_ptr(),
+              int(bool(accumulate)),
+              float(omega), float(grad_scale), torch.cuda.current_stream(sumsq.device).cuda_stream,
+              _scaling={"dev_pre": _pre_ptr(dev_pre)})
         return
     total = (slot[0] if accumulate else 0.0) + sumsq.sum().float()
     nrm = grad_scale * torch.sqrt(total)
+    pre = dev_pre.reshape(-1)[0] if dev_pre is not None else None
+    if pre is not None:
+        nrm = nrm * pre
+    cs = torch.clamp(omega / nrm, max=1.0) if omega > 0 else torch.ones((), dtype=torch.float32)
     slot[0] = total
     slot[1] = nrm
-    slot[2] = torch.clamp(omega / nrm, max=1.0) if omega > 0 else 1.0
+    slot[2] = cs * pre if pre is not None else cs
 
 
 def bias_corrections(beta1_t: float, beta2_t: float) -> tuple[float, float]:
@@ -583,4 +759,7 @@ def bias_corrections(beta1_t: float, beta2_t: float) -> tuple[float, float]:
 __all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_", "supported", "bias_corrections",
            "rule_", "rule_reference_", "RULES",
            "lars_", "lamb_", "lars_reference_", "lamb_reference_", "layerwise_workspace", "LAYERWISE",
-           "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_"]
+           "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_",
+           "check_finite_", "check_finite_reference_", "loss_scale_block", "loss_scale_update_",
+           "loss_scale_update_reference_", "LS_WORDS", "LS_SCALE", "LS_INV", "LS_TRACKER", "LS_SKIPPED", "LS_LAST",
+           "LS_FLAG"]

@@ -46,6 +46,7 @@ into the flat moment buffers).
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from contextlib import contextmanager
@@ -74,6 +75,56 @@ def engine_for(module: torch.nn.Module) -> "DDP | None":
     """The DDP engine managing ``module`` (None if there is none, or it was discarded)."""
     ref = _ENGINES.get(module)
     return ref() if ref is not None else None
+
+
+@dataclass
+class LossScale:
+    """Dynamic loss scaling (``torch.cuda.amp.GradScaler``'s rule) for :class:`DDP`.
+
+    The loss is multiplied by ``scale`` (:meth:`DDP.scale_loss`) so that small fp16 gradients do not
+    underflow; the update kernels divide it out again. A step whose reduced gradient holds an inf or
+    a NaN is skipped and the scale multiplied by ``backoff``; after ``interval`` clean steps in a
+    row it is multiplied by ``growth``. The scale stays in ``[min_scale, max_scale]``.
+    ``growth = backoff = 1`` is a static scale (which still skips non-finite steps)."""
+    init: float = 2.0 ** 16
+    growth: float = 2.0
+    backoff: float = 0.5
+    interval: int = 2000
+    min_scale: float = 1.0
+    max_scale: float = 2.0 ** 24
+
+    def __post_init__(self):
+        vals = (self.init, self.growth, self.backoff, self.min_scale, self.max_scale)
+        if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in vals):
+            raise ValueError(f"LossScale: scales and factors are finite numbers, got {vals}")
+        if self.init <= 0 or self.min_scale <= 0:
+            raise ValueError(f"LossScale: the scale must be positive, got init={self.init} min_scale={self.min_scale}")
+        if not self.min_scale <= self.init <= self.max_scale:
+            raise ValueError(f"LossScale: need min_scale <= init <= max_scale, got {self.min_scale}, {self.init}, "
+                             f"{self.max_scale}")
+        if self.growth < 1.0:
+            raise ValueError(f"LossScale: growth must be >= 1 (it raises the scale), got {self.growth}")
+        if not 0.0 < self.backoff <= 1.0:
+            raise ValueError(f"LossScale: backoff must be in (0, 1] (it lowers the scale), got {self.backoff}")
+        if isinstance(self.interval, bool) or int(self.interval) != self.interval or self.interval < 1:
+            raise ValueError(f"LossScale: interval is a positive number of steps, got {self.interval}")
+        self.interval = int(self.interval)
+
+    @staticmethod
+    def parse(spec) -> "LossScale | None":
+        """``None | "dynamic" | float | LossScale`` as :class:`DDP` takes it; a float is a static scale."""
+        if spec is None or isinstance(spec, LossScale):
+            return spec
+        if isinstance(spec, str):
+            if spec == "dynamic":
+                return LossScale()
+            raise ValueError(f"DDP: loss_scale is None, 'dynamic', a number or a LossScale, got {spec!r}")
+        if isinstance(spec, bool) or not isinstance(spec, (int, float)):
+            raise TypeError(f"DDP: loss_scale is None, 'dynamic', a number or a LossScale, got {type(spec).__name__}")
+        v = float(spec)
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError(f"DDP: a static loss scale must be positive and finite, got {spec}")
+        return LossScale(init=v, growth=1.0, backoff=1.0, min_scale=v, max_scale=v)
 
 
 @dataclass
@@ -152,6 +203,23 @@ class DDP:
             update cannot start before the last bucket is reduced) and not with a ``ClipNorm``
             chain; with ``ClipGrad`` the global scale is applied first.
             :meth:`grad_norm` returns the step's global gradient norm in either clip mode.
+    loss_scale: ``None`` (default: nothing is launched that was not before), ``"dynamic"``
+            (``LossScale()``), a number (a static scale, which still skips non-finite steps:
+            ``loss_scale=1.0`` is the plain non-finite guard of a bf16 / fp32 model) or a
+            :class:`LossScale`. Train on ``ddp.scale_loss(loss).backward()``. In ``step()``, on the
+            updates' stream and without a host read (HIP-graph capturable): every bucket's reduced
+            gradient is tested element by element for inf / NaN (inside the norm pass when the
+            engine clips by a norm, else in one multi-tensor pass), every update kernel divides the
+            scale out (norms and clamps see the unscaled gradient) and leaves at once when the test
+            found something, and one thread then updates the scale. The test reads the REDUCED
+            gradient, whose bits are the same on every rank, so the decision needs no collective
+            and the replicas cannot disagree; an fp16 SUM that overflows on the wire is caught the
+            same way and backs the scale off. A skipped step leaves parameters, masters, moments,
+            ``beta^t`` and trust ratios bit-identical. Every bucket is tested before the first
+            update, so not with ``overlap_opt=True``; and not with ``step(zero_grad=False)`` (two
+            backwards at two scales cannot be summed in one carry; ``no_sync()`` accumulation
+            between two steps is fine). :meth:`loss_scale`, :meth:`skipped_steps` and
+            :meth:`step_skipped` read the scaler.
     master_weights: keep fp32 master copies (+ fp32 moments) for low-precision params.
     average: divide the summed gradient by the world size (default False = reference SUM).
     overlap: launch bucket allreduces from backward hooks (default: ``FLUXMPI_OVERLAP``).
@@ -173,8 +241,12 @@ class DDP:
                  comm_dtype: torch.dtype | None = None, watchdog: bool | None = None,
                  grad_mode: str | None = None, force_comm: bool | None = None,
                  tail_bucket_mb: float | None = None, overlap_opt: bool | None = None,
-                 clip_global_norm: float | None = None):
+                 clip_global_norm: float | None = None, loss_scale=None):
         cfg = get_config()
+        self._ls = LossScale.parse(loss_scale)
+        if self._ls is not None and overlap_opt:
+            raise ValueError("DDP: loss_scale tests every bucket's gradient before the first update, so the "
+                             "updates cannot overlap with backward: drop overlap_opt=True")
         if clip_global_norm is not None and overlap_opt:
             raise ValueError("DDP: clip_global_norm needs every bucket's norm before the first update, so the "
                              "updates cannot overlap with backward: drop overlap_opt=True")
@@ -257,7 +329,7 @@ class DDP:
         # allreduce) when it has one, on a side stream when nothing is communicated, else in
         # step() (host-synchronous collectives: nothing to overlap with)
         want_opt = cfg.overlap_opt if overlap_opt is None else bool(overlap_opt)
-        if self.clip_global_norm is not None:
+        if self.clip_global_norm is not None or self._ls is not None:
             want_opt = False
         self.overlap_opt = want_opt and self.overlap and self.grad_mode == "steal"
         self._opt_stream = None  # None: the update runs right after the (host-waited) reduction
@@ -469,6 +541,14 @@ class DDP:
                     off, woff = off + len(b.adapted), woff + kw
         # [sum of squares, norm, global clip scale] of the step's whole gradient (device, fp32)
         self._clip_slot = torch.zeros(3, dtype=torch.float32, device=dev) if self._norms else None
+        # loss scaling: the scaler's device block {scale, 1/scale, growth tracker, skipped steps, last
+        # step skipped, non-finite flag} and the views the kernels and the accessors take of it
+        self._ls_block = None
+        if self._ls is not None:
+            self._ls_block = fused.loss_scale_block(self._ls.init, dev)
+            f = self._ls_block.view(torch.float32)
+            self._ls_scale, self._ls_inv = f[fused.LS_SCALE], f[fused.LS_INV:fused.LS_INV + 1]
+            self._ls_flag = self._ls_block[fused.LS_FLAG:fused.LS_FLAG + 1]
         if self._has_bt:
             a = self._inner
             # device hyper block [lr, beta1^t, beta2^t]; beta^t starts at beta (Optimisers.jl init)
@@ -773,6 +853,10 @@ class DDP:
         launches, packs and waits on every bucket again; the applied gradient of that
         step is the sum over ranks of both backwards' gradients (see ``_arm_carry``).
         """
+        if self._ls is not None and not zero_grad:
+            raise RuntimeError("DDP.step(zero_grad=False) with loss_scale: the kept gradient and the next backward's "
+                               "may carry two different scales and cannot be summed; accumulate inside "
+                               "`with ddp.no_sync():` between two steps instead")
         gscale = 1.0 / self.world if self.average else 1.0
         if not (self.overlap_opt and self._masters_synced):
             self._sync_masters()
@@ -845,16 +929,25 @@ class DDP:
         if self._deferred:
             # gradient norms with the updates in step(): ONE multi-tensor sum of squares over the
             # leaves of all buckets of a dtype (two launches per 24 leaves instead of per bucket)
-            # and one fold into the global sum, then every bucket's update
+            # and one fold into the global sum, then every bucket's update. Loss scaling: the
+            # non-finite test of every bucket in front of the first update, inside that pass when
+            # there is one, else one multi-tensor pass of its own
             grads = {b.index: (gs, gscale) for b, _, gs, gscale in self._deferred}
             for bs, buf, parts in self._clip_groups:
                 gs_all = [g for b in bs for g in grads[b.index][0]]
                 self._enqueue_norms(gs_all, buf, parts, grads[bs[0].index][1])
+            if self._ls is not None and not self._norms:
+                fused.check_finite_([g for _, _, gs, _ in self._deferred for g in gs], self._ls_flag)
             for b, st, gs, gscale in self._deferred:
                 self._run_update(st, gs, gscale, b)
             self._deferred = []
         if self._has_bt:
-            fused.adam_advance_(self.hyper, self._inner.beta[0], self._inner.beta[1])
+            fused.adam_advance_(self.hyper, self._inner.beta[0], self._inner.beta[1],
+                                dev_skip=self._ls_flag if self._ls is not None else None)
+        if self._ls is not None:
+            ls = self._ls
+            fused.loss_scale_update_(self._ls_block, growth=ls.growth, backoff=ls.backoff, interval=ls.interval,
+                                     min_scale=ls.min_scale, max_scale=ls.max_scale)
         self.step_count += 1
         if self.watchdog is not None:
             self.watchdog.check()
@@ -923,7 +1016,11 @@ class DDP:
         elif self._per_leaf:
             kw["tscale"] = b.clip[1]
         if self.clip_global_norm is not None:
-            kw["dev_gscale"] = self._clip_slot[2:3]
+            kw["dev_gscale"] = self._clip_slot[2:3]  # under a loss scale: inverse scale x clip scale
+        elif self._ls is not None:
+            kw["dev_gscale"] = self._ls_inv
+        if self._ls is not None:
+            kw["dev_skip"] = self._ls_flag
         if self._layerwise:
             self._run_layerwise(st, gs, gscale, b, kw)
         elif self.kind == "adam":
@@ -969,10 +1066,13 @@ class DDP:
         leaves) with the ClipNorm scales into ``buf[1]``, then the fold into the step's global sum
         / norm / global scale (one workgroup; the step's first call starts the sum afresh) — all on
         the current stream, no host read."""
+        # loss scaling: the non-finite check rides in the pass, and the norms are the unscaled gradient's
+        flag, pre = (self._ls_flag, self._ls_inv) if self._ls is not None else (None, None)
         fused.sumsq_(gs, buf[0], scales=buf[1] if self._per_leaf else None,
-                     omega=self._clip_rule.omega if self._per_leaf else 0.0, grad_scale=gscale, partials=parts)
+                     omega=self._clip_rule.omega if self._per_leaf else 0.0, grad_scale=gscale, partials=parts,
+                     flag=flag, dev_pre=pre)
         fused.clip_total_(buf[0], self._clip_slot, accumulate=self._norm_started,
-                          omega=self.clip_global_norm or 0.0, grad_scale=gscale)
+                          omega=self.clip_global_norm or 0.0, grad_scale=gscale, dev_pre=pre)
         self._norm_started = True
 
     def _update(self, b: _Bucket, st: tuple, gs: list, gscale: float):
@@ -980,7 +1080,7 @@ class DDP:
         bucket's norms are enqueued right in front of it (a leaf never spans buckets); otherwise
         the update waits for ``_finish_step``, which takes the norms of all buckets at once —
         ``clip_global_norm`` needs the last bucket's norm before the first update anyway."""
-        if self._norms:
+        if self._norms or self._ls is not None:  # (a loss scale switches overlap_opt off)
             if not self.overlap_opt:
                 self._deferred.append((b, st, gs, gscale))
                 return
@@ -1023,6 +1123,36 @@ class DDP:
             raise RuntimeError("DDP.grad_norm: the engine computes gradient norms only when it clips by one: "
                                "use an OptimiserChain(ClipNorm(omega), rule) or clip_global_norm=...")
         return self._clip_slot[1]
+
+    def scale_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """``loss * scale`` with the scaler's device scalar (no host read: usable inside a
+        ``GraphedStep`` ``loss_fn``); call ``backward()`` on the result. A 16-bit loss is taken to
+        fp32 first (2^16 is beyond fp16). Without ``loss_scale`` the loss comes back as it is."""
+        if self._ls is None:
+            return loss
+        if loss.dtype in (torch.float16, torch.bfloat16):
+            loss = loss.float()
+        return loss * self._ls_scale
+
+    def _scaler(self, what: str) -> torch.Tensor:
+        if self._ls is None:
+            raise RuntimeError(f"DDP.{what}: the engine was built without loss_scale")
+        return self._ls_block
+
+    def loss_scale(self) -> torch.Tensor:
+        """The current loss scale (the one the next backward is to be scaled by): a 0-dim fp32 view
+        of the scaler's device block. Never synchronises (read it after ``step()``, on the stream
+        ``step()`` ran on), like :meth:`skipped_steps` and :meth:`step_skipped`."""
+        return self._scaler("loss_scale").view(torch.float32)[fused.LS_SCALE]
+
+    def skipped_steps(self) -> torch.Tensor:
+        """Steps skipped so far for a non-finite gradient (0-dim int32 device view). ``step_count``
+        counts them too: the host never learns which steps were skipped."""
+        return self._scaler("skipped_steps")[fused.LS_SKIPPED]
+
+    def step_skipped(self) -> torch.Tensor:
+        """1 if the last ``step()`` was skipped, else 0 (0-dim int32 device view)."""
+        return self._scaler("step_skipped")[fused.LS_LAST]
 
     def trust_ratios(self) -> dict:
         """``{name: ratio}`` of the last step's trust ratios under LARS / LAMB: 0-dim device tensors
@@ -1082,6 +1212,10 @@ class DDP:
         for b, s in zip(self.buckets, sd["buckets"]):
             if b.state3 is not None:  # only the rules with a third state buffer (AMSGrad) add the key
                 s["s3"] = b.state3.detach().cpu()
+        if self._ls is not None:
+            blk = self._ls_block.detach().cpu()
+            sd["loss_scale"] = {"scale": float(blk.view(torch.float32)[fused.LS_SCALE]),
+                                "growth_tracker": int(blk[fused.LS_TRACKER]), "skipped": int(blk[fused.LS_SKIPPED])}
         return sd
 
     def load_state_dict(self, sd):
@@ -1101,6 +1235,12 @@ class DDP:
                     b.exp_avg_sq.copy_(s["v"])
                 if b.state3 is not None:
                     b.state3.copy_(s["s3"])
+            if self._ls is not None:
+                # in place: captured graphs and the accessors' views keep pointing at the block; a
+                # checkpoint without a scaler state starts from the constructor's values
+                ls = sd.get("loss_scale") or {"scale": self._ls.init, "growth_tracker": 0, "skipped": 0}
+                self._ls_block.copy_(fused.loss_scale_block(ls["scale"], "cpu", tracker=ls["growth_tracker"],
+                                                            skipped=ls["skipped"]))
         self._record_versions()
 
     def num_parameters(self) -> int:
@@ -1131,4 +1271,4 @@ class DDP:
         self._hooks.clear()
 
 
-__all__ = ["DDP"]
+__all__ = ["DDP", "LossScale"]
