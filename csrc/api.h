@@ -132,6 +132,21 @@ void mt_check_finite(const std::vector<uintptr_t>& grad, const std::vector<int64
 void loss_scale_update(void* block, float growth, float backoff, int interval, float min_scale, float max_scale,
                        hipStream_t stream);
 
+// ---- exponential moving average of the weights (optim_ema.hip) -------------------------
+// ema[i] <- ema[i] + omd * (src[i] - ema[i]) per element, in this form (src == ema keeps the bits), in
+// the update kernels' job layout. src: the fp32 master of a leaf, or its parameter (src_dtype: fp32,
+// bf16, fp16, fp64); ema: fp32 (fp64 sources: fp64). dev_block (the block below, or null) overrides
+// omd with its first word and calls the launch off while its `hold` word is set; dev_skip (or null)
+// calls it off as it does the update kernels. A launch that is called off loads no tensor data.
+void mt_ema(const std::vector<uintptr_t>& ema, const std::vector<uintptr_t>& src, const std::vector<int64_t>& numel,
+            int src_dtype, double omd, const int32_t* dev_block, const int32_t* dev_skip, hipStream_t stream);
+// The EMA device block, 8 words: {float omd = 1 - d_t, float d_t, int32 n (EMA updates done), int32 k
+// (optimiser steps since the last EMA update), int32 hold (the coming step is not an EMA step), 3
+// unused}. One thread, after a step's mt_ema launches; nothing changes when *dev_skip != 0. The step
+// was an EMA step (hold == 0): n += 1, k = 0; else k += 1. Then hold = (k + 1 < every), d_t = warmup ?
+// min(decay, (1 + n) / (10 + n)) : decay, omd = 1 - d_t.
+void ema_advance(void* block, float decay, int warmup, int every, const int32_t* dev_skip, hipStream_t stream);
+
 // ---- BatchNorm (NHWC, channels innermost) + ReLU / residual-add fusions ----------
 // Training forward: per-channel batch statistics over rows = N*H*W, then
 //   y = act(x * scale_c + shift_c [+ residual]).

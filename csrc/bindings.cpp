@@ -124,6 +124,16 @@ PYBIND11_MODULE(_C_scale, m) {
         py::arg("interval"), py::arg("min_scale"), py::arg("max_scale"), py::arg("stream"));
 }
 
+// The weight-EMA surface (DDP(ema=...), optimisers.ema_update): a third module of this shared object,
+// loaded by fluxmpi_amd.ops._ext.ema(), so that `_C` and `_C_scale` keep the entries they have.
+PYBIND11_MODULE(_C_ema, m) {
+  m.doc() = "fluxmpi_amd native library: exponential moving average of the weights";
+  m.def("mt_ema", raw(&mt_ema), py::arg("ema"), py::arg("src"), py::arg("numel"), py::arg("src_dtype"),
+        py::arg("omd"), py::arg("dev_block"), py::arg("dev_skip"), py::arg("stream"));
+  m.def("ema_advance", raw(&ema_advance), py::arg("block"), py::arg("decay"), py::arg("warmup"), py::arg("every"),
+        py::arg("dev_skip"), py::arg("stream"));
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
 

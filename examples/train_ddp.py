@@ -23,6 +23,8 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--lr", type=float, default=None, help="default: 1e-3 (adamw, lamb), 0.1 (lars)")
 ap.add_argument("--opt", default="adamw", choices=["adamw", "lars", "lamb"],
                 help="lars / lamb: the layer-wise rules for large global batches")
+ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                help="keep an exponential moving average of the weights (e.g. 0.9999) and evaluate with it")
 args = ap.parse_args()
 
 FluxMPI.Init()
@@ -38,7 +40,7 @@ if dev.type == "cuda":
 lr = args.lr if args.lr is not None else (0.1 if args.opt == "lars" else 1e-3)
 rule = {"adamw": lambda: O.AdamW(lr, decay=1e-4), "lars": lambda: O.LARS(lr, 0.9, trust=0.001, decay=1e-4),
         "lamb": lambda: O.LAMB(lr, decay=0.01)}[args.opt]()
-ddp = DDP(model, rule, average=True)
+ddp = DDP(model, rule, average=True, ema=args.ema)
 if FluxMPI.local_rank() == 0:
     print("buckets:", ddp.bucket_summary())
 
@@ -61,6 +63,17 @@ for step in range(args.steps):
         if args.opt != "adamw" and FluxMPI.local_rank() == 0:
             q = torch.stack(list(ddp.trust_ratios().values())).float()
             print(f"  trust ratios: min {q.min().item():.3g} median {q.median().item():.3g} max {q.max().item():.3g}")
+if args.ema is not None:
+    # evaluation with the averaged weights: inside the context the module's parameters hold the EMA,
+    # afterwards the training weights are back bit for bit (ddp.ema_state_dict() is what to checkpoint)
+    model.eval()
+    with torch.no_grad():
+        live = F.cross_entropy(ddp(x).float(), y).item()
+        with ddp.ema_weights():
+            avg = F.cross_entropy(ddp(x).float(), y).item()
+    model.train()
+    FluxMPI.fluxmpi_println(f"eval loss {live:.4f}, with the averaged weights {avg:.4f} "
+                            f"({int(ddp.ema_updates())} EMA updates, decay now {float(ddp.ema_decay()):.4f})")
 if FluxMPI.local_rank() == 0:
     print({k: round(v, 3) for k, v in timer.summary().items()}, "ms;",
           f"{args.steps * args.batch * FluxMPI.total_workers() / (time.time() - t0):.1f} samples/s")

@@ -29,7 +29,7 @@ from .parallel import (COMM_WORLD, Barrier, DistributedDataContainer, Distribute
                        ReduceOp, Wait, Waitall, allgather, allreduce, allreduce_gradients, backend_name, barrier,
                        bcast, device, fluxmpi_print, fluxmpi_println, local_rank, reduce, reduce_scatter,
                        synchronize, total_workers)
-from .parallel.ddp import LossScale  # noqa: F401
+from .parallel.ddp import EMA, LossScale  # noqa: F401
 from .ops.syncbn import SyncBatchNorm2d, convert_sync_batchnorm, sync_batch_norm  # noqa: F401
 from .utils.config import disable_cudampi_support  # noqa: F401
 from .utils.errors import FluxMPINotInitializedError  # noqa: F401
@@ -58,5 +58,5 @@ __all__ = [
     "FluxMPIFluxModel", "FlatParams", "allreduce", "bcast", "reduce", "Iallreduce", "Ibcast", "Wait", "Waitall",
     "allgather", "reduce_scatter", "COMM_WORLD", "ReduceOp", "disable_cudampi_support",
     "FluxMPINotInitializedError", "optimisers", "build", "barrier", "Barrier", "device", "backend_name",
-    "SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm", "LossScale",
+    "SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm", "LossScale", "EMA",
 ]

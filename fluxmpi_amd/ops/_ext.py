@@ -74,31 +74,39 @@ def get(required: bool = True):
     return mod
 
 
-_SCALE = None
+_EXTRA: dict = {}
 
 
-def scale():
-    """The ``_C_scale`` module: the fused optimisers' entries with the loss-scaling arguments
-    (``dev_skip``, ``nonfinite_flag``, ``dev_pre``), ``mt_check_finite`` and ``loss_scale_update``.
-
-    It is a second module of the shared object ``_C`` was loaded from (its ``PyInit__C_scale``), so
-    ``_C`` itself keeps the surface ``tests/golden/c_api_surface.json`` records. Missing: an error,
-    as for ``_C``."""
-    global _SCALE
-    if _SCALE is None:
+def _extra(name: str, what: str):
+    """A further pybind11 module ``fluxmpi_amd.<name>`` of the shared object ``_C`` was loaded from (its
+    ``PyInit_<name>``): new entries get a module of their own, so ``_C`` itself keeps the surface
+    ``tests/golden/c_api_surface.json`` records. Missing: an error, as for ``_C``."""
+    if name not in _EXTRA:
         C = get(required=True)
         if C is None:
-            raise NativeExtensionError("fluxmpi_amd._C_scale needs the native extension fluxmpi_amd._C")
-        spec = importlib.util.spec_from_file_location("fluxmpi_amd._C_scale", C.__file__)
+            raise NativeExtensionError(f"fluxmpi_amd.{name} needs the native extension fluxmpi_amd._C")
+        spec = importlib.util.spec_from_file_location(f"fluxmpi_amd.{name}", C.__file__)
         try:
             mod = importlib.util.module_from_spec(spec)
             spec.loader.exec_module(mod)
         except Exception as e:
             raise NativeExtensionError(
-                f"fluxmpi_amd._C_scale (the loss-scaling entries of {C.__file__}) failed to load: {e!r}. "
+                f"fluxmpi_amd.{name} ({what} of {C.__file__}) failed to load: {e!r}. "
                 "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
-        _SCALE = mod
-    return _SCALE
+        _EXTRA[name] = mod
+    return _EXTRA[name]
+
+
+def scale():
+    """The ``_C_scale`` module: the fused optimisers' entries with the loss-scaling arguments
+    (``dev_skip``, ``nonfinite_flag``, ``dev_pre``), ``mt_check_finite`` and ``loss_scale_update``."""
+    return _extra("_C_scale", "the loss-scaling entries")
+
+
+def ema():
+    """The ``_C_ema`` module: ``mt_ema`` and ``ema_advance`` (the exponential moving average of the
+    weights, ``csrc/kernels/optim_ema.hip``)."""
+    return _extra("_C_ema", "the weight-EMA entries")
 
 
 def require_for(t: torch.Tensor):

@@ -712,6 +712,161 @@ def loss_scale_update_reference_(block: torch.Tensor, *, growth, backoff, interv
     block[LS_FLAG] = 0
 
 
+# ---- exponential moving average of the weights (csrc/kernels/optim_ema.hip) -----------------------
+# the EMA device block (csrc/api.h: ema_advance): 8 int32 words, the first two fp32 bits
+EMA_WORDS = 8
+EMA_OMD, EMA_DECAY, EMA_UPDATES, EMA_SINCE, EMA_HOLD = range(5)
+
+
+def _ema_decay_at(decay: float, warmup: bool, n: int) -> torch.Tensor:
+    """``d_t`` after ``n`` EMA updates, in fp32 as the kernel computes it."""
+    d = torch.tensor(decay, dtype=torch.float32)
+    if warmup:
+        d = torch.minimum(d, torch.tensor(1.0 + n, dtype=torch.float32) / torch.tensor(10.0 + n, dtype=torch.float32))
+    return d
+
+
+def ema_block(decay: float, warmup: bool, every: int, device, *, updates: int = 0, since: int = 0) -> torch.Tensor:
+    """A fresh EMA block on ``device`` with the values of the coming step: ``d_t`` (``warmup``:
+    ``min(decay, (1 + n) / (10 + n))`` with ``n = updates``), ``omd = 1 - d_t``, the counters, and
+    ``hold = since + 1 < every`` (the coming optimiser step is not an EMA step)."""
+    if not 0.0 <= decay < 1.0 or int(every) < 1:
+        raise ValueError(f"ema_block: need 0 <= decay < 1 and every >= 1, got decay={decay} every={every}")
+    blk = torch.zeros(EMA_WORDS, dtype=torch.int32)
+    f = blk.view(torch.float32)
+    f[EMA_DECAY] = _ema_decay_at(decay, warmup, int(updates))
+    f[EMA_OMD] = 1.0 - f[EMA_DECAY]
+    blk[EMA_UPDATES], blk[EMA_SINCE] = int(updates), int(since)
+    blk[EMA_HOLD] = 1 if int(since) + 1 < int(every) else 0
+    return blk.to(device)
+
+
+def _ema_block_ok(block, what: str) -> None:
+    if block.dtype != torch.int32 or block.numel() < EMA_WORDS or not block.is_contiguous():
+        raise TypeError(f"{what}: the EMA block is a contiguous int32 tensor of {EMA_WORDS} entries (ema_block)")
+
+
+def _ema_check(emas, srcs) -> None:
+    if len(emas) != len(srcs):
+        raise ValueError(f"ema_: {len(emas)} EMA leaves for {len(srcs)} sources")
+    for i, (e, x) in enumerate(zip(emas, srcs)):
+        if x.dtype not in (torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise TypeError(f"ema_: leaf {i}: unsupported source dtype {x.dtype}")
+        if e.dtype != _acc_dtype(x.dtype):
+            raise TypeError(f"ema_: leaf {i}: the EMA of a {x.dtype} source is kept in {_acc_dtype(x.dtype)}, "
+                            f"got {e.dtype}")
+        if e.numel() != x.numel() or e.device != x.device:
+            raise TypeError(f"ema_: leaf {i}: EMA and source differ in size or device")
+        if e.numel() and not _one_memory_order(e, x):
+            raise TypeError(f"ema_: leaf {i}: EMA and source must be dense with one memory order")
+
+
+def _one_memory_order(e: torch.Tensor, x: torch.Tensor) -> bool:
+    """Both contiguous, or the same shape and (dense) strides: element ``i`` in memory is the same leaf entry."""
+    if e.is_contiguous() and x.is_contiguous():
+        return True
+    if e.shape != x.shape or e.stride() != x.stride():
+        return False
+    expect = 1
+    for st, n in sorted(zip(x.stride(), x.shape)):
+        if n != 1 and st != expect:
+            return False
+        expect *= n
+    return True
+
+
+def ema_(emas, srcs, *, decay: float | None = None, dev_block: torch.Tensor | None = None,
+         dev_skip: torch.Tensor | None = None) -> None:
+    """In-place fused exponential moving average over lists of tensors (``optim_ema.hip``):
+    ``e <- e + omd * (x - e)`` per element, in this form (``x == e`` keeps ``e``'s bits), computed in
+    fp32 (fp64 for fp64 sources). ``srcs``: the fp32 masters where a leaf has one, else the parameters
+    (fp32, bf16, fp16, fp64); ``emas``: fp32 (fp64 sources: fp64) tensors of the same sizes, else
+    ``TypeError``. One launch per 24 leaves of a source dtype; leaves without elements are skipped.
+
+    ``omd = 1 - decay`` from the host, or, with ``dev_block`` (:func:`ema_block`, advanced by
+    :func:`ema_advance_`), the block's: the device value wins, and a block whose ``hold`` word is set
+    calls the launch off. ``dev_skip``: as in :func:`adam_`. A launch that is called off reads and
+    writes no tensor. No host read: graph-capturable."""
+    emas, srcs = list(emas), list(srcs)
+    _ema_check(emas, srcs)
+    if dev_block is None and decay is None:
+        raise ValueError("ema_: needs decay or dev_block")
+    if dev_block is not None:
+        _ema_block_ok(dev_block, "ema_")
+    if not emas:
+        return
+    if not emas[0].is_cuda:
+        ema_reference_(emas, srcs, decay=decay, dev_block=dev_block, dev_skip=dev_skip)
+        return
+    E = _ext.ema()
+    stream = torch.cuda.current_stream(emas[0].device).cuda_stream
+    omd = 1.0 - float(decay) if decay is not None else 0.0
+    groups: dict = {}
+    for e, x in zip(emas, srcs):
+        if e.numel():
+            groups.setdefault(x.dtype, []).append((e, x))
+    for xd, leaves in groups.items():
+        E.mt_ema([e.data_ptr() for e, _ in leaves], [x.data_ptr() for _, x in leaves], [e.numel() for e, _ in leaves],
+                 DTYPE_CODE[xd], omd, _ptr(dev_block), _skip_ptr(dev_skip), stream)
+
+
+def ema_reference_(emas, srcs, *, decay=None, dev_block=None, dev_skip=None) -> None:
+    """PyTorch reference of :func:`ema_`: the same expression, three roundings in the compute type.
+    The CPU path of the engine and the kernel's oracle."""
+    emas, srcs = list(emas), list(srcs)
+    _ema_check(emas, srcs)
+    if _skipped(dev_skip):
+        return
+    if dev_block is not None:
+        _ema_block_ok(dev_block, "ema_reference_")
+        if int(dev_block[EMA_HOLD]) != 0:
+            return
+        omd = dev_block.view(torch.float32)[EMA_OMD].detach().cpu()
+    else:
+        omd = torch.tensor(1.0 - float(decay), dtype=torch.float64)
+    with torch.no_grad():
+        for e, x in zip(emas, srcs):
+            if e.numel():
+                d = x.to(e.dtype) - e
+                e.add_(omd.to(device=e.device, dtype=e.dtype) * d)
+
+
+def ema_advance_(block: torch.Tensor, *, decay: float, warmup: bool, every: int,
+                 dev_skip: torch.Tensor | None = None) -> None:
+    """The EMA block's bookkeeping after an optimiser step's :func:`ema_` launches, one thread on the
+    device. Nothing changes when ``dev_skip`` is non-zero (a skipped step does not count). The step
+    was an EMA step (``hold == 0``): ``n += 1``, ``k = 0``; else ``k += 1``. Then, for the coming
+    step, ``hold = k + 1 < every``, ``d_t = min(decay, (1 + n) / (10 + n))`` (``warmup``; else
+    ``decay``) and ``omd = 1 - d_t``. No host read: graph-capturable."""
+    _ema_block_ok(block, "ema_advance_")
+    if int(every) < 1:
+        raise ValueError(f"ema_advance_: every must be >= 1, got {every}")
+    if block.is_cuda:
+        _ext.ema().ema_advance(block.data_ptr(), float(decay), int(bool(warmup)), int(every), _skip_ptr(dev_skip),
+                               torch.cuda.current_stream(block.device).cuda_stream)
+        return
+    ema_advance_reference_(block, decay=decay, warmup=warmup, every=every, dev_skip=dev_skip)
+
+
+def ema_advance_reference_(block: torch.Tensor, *, decay, warmup, every, dev_skip=None) -> None:
+    """PyTorch reference of :func:`ema_advance_` on a CPU block, in fp32 as the kernel computes."""
+    _ema_block_ok(block, "ema_advance_reference_")
+    if int(every) < 1:
+        raise ValueError(f"ema_advance_reference_: every must be >= 1, got {every}")
+    if _skipped(dev_skip):
+        return
+    n, k = int(block[EMA_UPDATES]), int(block[EMA_SINCE])
+    if int(block[EMA_HOLD]) == 0:
+        n, k = n + 1, 0
+    else:
+        k += 1
+    f = block.view(torch.float32)
+    f[EMA_DECAY] = _ema_decay_at(decay, warmup, n)
+    f[EMA_OMD] = 1.0 - f[EMA_DECAY]
+    block[EMA_UPDATES], block[EMA_SINCE] = n, k
+    block[EMA_HOLD] = 1 if k + 1 < int(every) else 0
+
+
 def sumsq_reference(grads) -> torch.Tensor:
     """fp64 CPU sums of squares of ``grads`` (the oracle of :func:`sumsq_`)."""
     return torch.stack([g.detach().cpu().double().pow(2).sum() for g in grads]) if grads else torch.zeros(0, dtype=torch.float64)
@@ -762,4 +917,6 @@ __all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_"
            "sumsq_", "sumsq_partials", "sumsq_reference", "clip_scales_reference", "clip_total_",
            "check_finite_", "check_finite_reference_", "loss_scale_block", "loss_scale_update_",
            "loss_scale_update_reference_", "LS_WORDS", "LS_SCALE", "LS_INV", "LS_TRACKER", "LS_SKIPPED", "LS_LAST",
-           "LS_FLAG"]
+           "LS_FLAG",
+           "ema_", "ema_reference_", "ema_block", "ema_advance_", "ema_advance_reference_", "EMA_WORDS", "EMA_OMD",
+           "EMA_DECAY", "EMA_UPDATES", "EMA_SINCE", "EMA_HOLD"]

@@ -128,6 +128,38 @@ class LossScale:
 
 
 @dataclass
+class EMA:
+    """Exponential moving average of the weights for :class:`DDP` (``timm``'s ``ModelEmaV2/V3``, the
+    DeiT and "ResNet strikes back" recipes): after every ``every``-th applied optimiser step
+    ``e <- e + (1 - d_t) (x - e)`` with ``x`` the fp32 master (else the parameter).
+
+    ``warmup``: ``d_t = min(decay, (1 + n) / (10 + n))`` with ``n`` the EMA updates done so far, so
+    that the first updates follow the weights closely; without it ``d_t = decay``. ``every > 1``
+    updates the average on every ``every``-th applied step only (choose ``decay`` for that cadence)."""
+    decay: float = 0.9999
+    warmup: bool = True
+    every: int = 1
+
+    def __post_init__(self):
+        d = self.decay
+        if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0.0 <= d < 1.0:
+            raise ValueError(f"EMA: need 0 <= decay < 1, got {d!r}")
+        if isinstance(self.every, bool) or not isinstance(self.every, (int, float)) \
+                or int(self.every) != self.every or self.every < 1:
+            raise ValueError(f"EMA: every is a positive number of steps, got {self.every!r}")
+        self.decay, self.every, self.warmup = float(d), int(self.every), bool(self.warmup)
+
+    @staticmethod
+    def parse(spec) -> "EMA | None":
+        """``None | float | EMA`` as :class:`DDP` takes it; a float is ``EMA(decay=float)``."""
+        if spec is None or isinstance(spec, EMA):
+            return spec
+        if isinstance(spec, bool) or not isinstance(spec, (int, float)):
+            raise TypeError(f"DDP: ema is None, a decay or an EMA, got {type(spec).__name__}")
+        return EMA(decay=float(spec))
+
+
+@dataclass
 class _Bucket:
     index: int
     dtype: torch.dtype
@@ -156,6 +188,7 @@ class _Bucket:
     plain: list = field(default_factory=list)    # ... and of the 1-D leaves that take Momentum / Adam
     ratios: torch.Tensor | None = None     # ... the adapted leaves' trust ratios (a slice of the dtype's table)
     lw_work: torch.Tensor | None = None    # ... and the layer-wise kernels' norm partials
+    ema: torch.Tensor | None = None  # DDP(ema=...): the averaged weights, flat, fp32 (fp64 buckets: fp64)
 
 
 def _strided_view(flat: torch.Tensor, like: torch.Tensor, offset: int) -> torch.Tensor:
@@ -220,6 +253,18 @@ class DDP:
             backwards at two scales cannot be summed in one carry; ``no_sync()`` accumulation
             between two steps is fine). :meth:`loss_scale`, :meth:`skipped_steps` and
             :meth:`step_skipped` read the scaler.
+    ema:    ``None`` (default: nothing is allocated or launched that was not before), a decay
+            (``EMA(decay=...)``) or an :class:`EMA`: the engine keeps an exponential moving average of
+            the weights, one flat buffer per bucket in fp32 (fp64 buckets: fp64), taken from the fp32
+            masters (the parameters where there are none) by one streaming kernel per bucket right
+            behind the bucket's update, on its stream, with every rule, clip mode, ``loss_scale``,
+            ``overlap_opt``, ``no_sync()``, ``step(zero_grad=False)`` and ``GraphedStep``. A step the
+            loss scaler skips leaves the average, its update count and its decay bit-identical. The
+            buffers are broadcast with the masters at construction and every rank then applies the
+            same arithmetic to the same bits, so replicas stay equal without a collective per step.
+            :meth:`ema_parameters`, :meth:`ema_decay` and :meth:`ema_updates` read it,
+            :meth:`ema_state_dict` exports it, ``with ddp.ema_weights():`` evaluates with it, and
+            :meth:`state_dict` carries it. Parameter changes from outside the engine do not reset it.
     master_weights: keep fp32 master copies (+ fp32 moments) for low-precision params.
     average: divide the summed gradient by the world size (default False = reference SUM).
     overlap: launch bucket allreduces from backward hooks (default: ``FLUXMPI_OVERLAP``).
@@ -241,9 +286,11 @@ class DDP:
                  comm_dtype: torch.dtype | None = None, watchdog: bool | None = None,
                  grad_mode: str | None = None, force_comm: bool | None = None,
                  tail_bucket_mb: float | None = None, overlap_opt: bool | None = None,
-                 clip_global_norm: float | None = None, loss_scale=None):
+                 clip_global_norm: float | None = None, loss_scale=None, ema=None):
         cfg = get_config()
         self._ls = LossScale.parse(loss_scale)
+        self._ema = EMA.parse(ema)
+        self._ema_swapped = False  # inside `with ema_weights():`
         if self._ls is not None and overlap_opt:
             raise ValueError("DDP: loss_scale tests every bucket's gradient before the first update, so the "
                              "updates cannot overlap with backward: drop overlap_opt=True")
@@ -549,6 +596,16 @@ class DDP:
             f = self._ls_block.view(torch.float32)
             self._ls_scale, self._ls_inv = f[fused.LS_SCALE], f[fused.LS_INV:fused.LS_INV + 1]
             self._ls_flag = self._ls_block[fused.LS_FLAG:fused.LS_FLAG + 1]
+        # weight EMA: per bucket one flat buffer in compute precision, started from the master (else the
+        # parameters) leaf by leaf, so that the alignment padding between leaves is zero: finite. And the
+        # EMA device block {1 - d_t, d_t, updates, steps since the last one, hold}
+        self._ema_block = None
+        if self._ema is not None:
+            for b in self.buckets:
+                b.ema = torch.zeros(b.numel, dtype=torch.float64 if b.dtype == torch.float64 else torch.float32,
+                                    device=dev)
+                self._ema_restart(b)
+            self._ema_block = fused.ema_block(self._ema.decay, self._ema.warmup, self._ema.every, dev)
         if self._has_bt:
             a = self._inner
             # device hyper block [lr, beta1^t, beta2^t]; beta^t starts at beta (Optimisers.jl init)
@@ -566,6 +623,8 @@ class DDP:
                 self.comm.broadcast(b.flat_param, root_rank)
                 if b.master is not None:
                     self.comm.broadcast(b.master, root_rank)
+                if b.ema is not None:  # replicas start from one average and apply the same arithmetic to it
+                    self.comm.broadcast(b.ema, root_rank)
             # buffers and the parameters outside every bucket (requires_grad=False: a frozen
             # backbone or embedding) — the reference's synchronize! reaches every leaf
             bucketed = {id(p) for b in self.buckets for p in b.params}
@@ -857,6 +916,9 @@ class DDP:
             raise RuntimeError("DDP.step(zero_grad=False) with loss_scale: the kept gradient and the next backward's "
                                "may carry two different scales and cannot be summed; accumulate inside "
                                "`with ddp.no_sync():` between two steps instead")
+        if self._ema_swapped:
+            raise RuntimeError("DDP.step inside `with ddp.ema_weights():`: the parameters hold the averaged weights; "
+                               "leave the context before training on")
         gscale = 1.0 / self.world if self.average else 1.0
         if not (self.overlap_opt and self._masters_synced):
             self._sync_masters()
@@ -944,6 +1006,10 @@ class DDP:
         if self._has_bt:
             fused.adam_advance_(self.hyper, self._inner.beta[0], self._inner.beta[1],
                                 dev_skip=self._ls_flag if self._ls is not None else None)
+        if self._ema is not None:  # in front of the scaler update, which clears the flag the EMA kernels read
+            e = self._ema
+            fused.ema_advance_(self._ema_block, decay=e.decay, warmup=e.warmup, every=e.every,
+                               dev_skip=self._ls_flag if self._ls is not None else None)
         if self._ls is not None:
             ls = self._ls
             fused.loss_scale_update_(self._ls_block, growth=ls.growth, backoff=ls.backoff, interval=ls.interval,
@@ -1034,6 +1100,11 @@ class DDP:
             mom = {"descent": 0.0}.get(self.kind, getattr(self._upd, "rho", 0.0))
             fused.sgd_(ps, gs, ms, lr=self._upd.eta, momentum=mom, nesterov=self.kind == "nesterov",
                        weight_decay=self.wd, grad_scale=gscale, masters=ws, dev_lr=self.hyper, **kw)
+        if self._ema is not None:
+            # directly behind the bucket's last update launch, on its stream: one launch over the whole
+            # flat bucket (padding included), reading the master the update wrote a moment ago
+            fused.ema_([b.ema], [b.master if b.master is not None else b.flat_param], dev_block=self._ema_block,
+                       dev_skip=kw.get("dev_skip"))
 
     def _run_layerwise(self, st: tuple, gs: list, gscale: float, b: _Bucket, kw: dict):
         """LARS / LAMB over the bucket's per-leaf lists: the two-phase kernels on the adapted leaves,
@@ -1163,6 +1234,81 @@ class DDP:
             raise RuntimeError("DDP.trust_ratios: only the layer-wise rules (LARS, LAMB) have trust ratios")
         return {b.names[i]: b.ratios[k] for b in self.buckets for k, i in enumerate(b.adapted)}
 
+    # ------------------------------------------------------------------ weight EMA
+    def _ema_restart(self, b: _Bucket):
+        """Bucket ``b``'s average := its master (else its parameters), in place, leaf by leaf (the
+        padding between leaves keeps its zeros)."""
+        src = b.master if b.master is not None else b.flat_param
+        with torch.no_grad():
+            for p, o in zip(b.params, b.offsets):
+                b.ema[o:o + p.numel()].copy_(src[o:o + p.numel()])
+
+    def _averaging(self, what: str) -> EMA:
+        if self._ema is None:
+            raise RuntimeError(f"DDP.{what}: the engine was built without ema")
+        return self._ema
+
+    def ema_parameters(self) -> dict:
+        """``{name: averaged weight}``: views of the engine's flat EMA buffers (fp32; fp64 for fp64
+        parameters) with the parameter's shape and strides, so they follow later steps. Never
+        synchronises (read them after ``step()``, on the stream ``step()`` ran on), like
+        :meth:`ema_decay` and :meth:`ema_updates`.
+
+        The average follows the fp32 masters (the parameters where there are none) as the optimiser
+        writes them. A parameter change from outside the engine (``load_state_dict`` on the module,
+        an in-place edit: what ``step()`` copies into the masters) does NOT reset it: the average
+        moves towards the new weights at the rate ``1 - d_t`` like after any other step."""
+        self._averaging("ema_parameters")
+        return {n: _strided_view(b.ema, p, o) for b in self.buckets for n, p, o in zip(b.names, b.params, b.offsets)}
+
+    def ema_decay(self) -> torch.Tensor:
+        """The decay ``d_t`` the coming EMA update uses (0-dim fp32 device view)."""
+        self._averaging("ema_decay")
+        return self._ema_block.view(torch.float32)[fused.EMA_DECAY]
+
+    def ema_updates(self) -> torch.Tensor:
+        """EMA updates done so far (0-dim int32 device view): applied steps, every ``every``-th one."""
+        self._averaging("ema_updates")
+        return self._ema_block[fused.EMA_UPDATES]
+
+    def ema_state_dict(self) -> dict:
+        """``module.state_dict()`` (its keys and dtypes, copies) with every parameter the engine
+        trains replaced by its average, cast to the parameter's dtype. Everything else — buffers,
+        frozen parameters, BatchNorm's running statistics, which are averages already and are not
+        averaged again — is the live tensor's copy."""
+        avg = self.ema_parameters()
+        sd = self.module.state_dict()
+        out = type(sd)()
+        for k, v in sd.items():
+            out[k] = avg[k].to(v.dtype, copy=True) if k in avg else v.detach().clone()
+        if hasattr(sd, "_metadata"):
+            out._metadata = sd._metadata
+        return out
+
+    @contextmanager
+    def ema_weights(self):
+        """Evaluation with the averaged weights: inside, the module's parameters hold the EMA cast to
+        their dtype; on exit the training parameters are back bit for bit. The masters, the moments
+        and the average itself are never touched, and the swap does not count as an outside edit of
+        the parameters. ``step()`` inside raises. Plain copies, not a hot path."""
+        self._averaging("ema_weights")
+        if self._ema_swapped:
+            raise RuntimeError("DDP.ema_weights: already inside the context")
+        self._sync_masters()  # an outside edit made before the swap reaches the masters first
+        with torch.no_grad():
+            saved = [b.flat_param.clone() for b in self.buckets]
+            for b in self.buckets:
+                b.flat_param.copy_(b.ema)
+        self._ema_swapped = True
+        try:
+            yield self.module
+        finally:
+            with torch.no_grad():
+                for b, s in zip(self.buckets, saved):
+                    b.flat_param.copy_(s)
+            self._ema_swapped = False
+            self._record_versions()
+
     def set_lr(self, lr: float):
         """Change the learning rate (device-side, so captured graphs see it)."""
         if not hasattr(self._inner, "eta"):
@@ -1216,6 +1362,10 @@ class DDP:
             blk = self._ls_block.detach().cpu()
             sd["loss_scale"] = {"scale": float(blk.view(torch.float32)[fused.LS_SCALE]),
                                 "growth_tracker": int(blk[fused.LS_TRACKER]), "skipped": int(blk[fused.LS_SKIPPED])}
+        if self._ema is not None:
+            blk = self._ema_block.detach().cpu()
+            sd["ema"] = {"buckets": [b.ema.detach().to("cpu", copy=True) for b in self.buckets],
+                         "num_updates": int(blk[fused.EMA_UPDATES]), "since": int(blk[fused.EMA_SINCE])}
         return sd
 
     def load_state_dict(self, sd):
@@ -1241,6 +1391,19 @@ class DDP:
                 ls = sd.get("loss_scale") or {"scale": self._ls.init, "growth_tracker": 0, "skipped": 0}
                 self._ls_block.copy_(fused.loss_scale_block(ls["scale"], "cpu", tracker=ls["growth_tracker"],
                                                             skipped=ls["skipped"]))
+            if self._ema is not None:
+                # in place as well; a checkpoint without an average starts one from the loaded masters
+                # (parameters where there are none), with no update counted
+                saved = sd.get("ema")
+                for i, b in enumerate(self.buckets):
+                    if saved is not None:
+                        b.ema.copy_(saved["buckets"][i])
+                    else:
+                        self._ema_restart(b)
+                e = self._ema
+                self._ema_block.copy_(fused.ema_block(e.decay, e.warmup, e.every, "cpu",
+                                                      updates=saved["num_updates"] if saved else 0,
+                                                      since=saved["since"] if saved else 0))
         self._record_versions()
 
     def num_parameters(self) -> int:
@@ -1271,4 +1434,4 @@ class DDP:
         self._hooks.clear()
 
 
-__all__ = ["DDP", "LossScale"]
+__all__ = ["DDP", "LossScale", "EMA"]
