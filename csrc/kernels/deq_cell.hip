@@ -605,6 +605,21 @@ void check16(std::initializer_list<const void*> ps) {
       throw std::runtime_error("deq_cell: tensors must be 16-byte aligned");
 }
 
+// the sample's LDS footprint, refused before any launch (deq_cell_supported's criterion)
+size_t checked_lds(const CellShape& s) {
+  const size_t lds = cell_lds(s);
+  if (lds > 160 * 1024) throw std::runtime_error("deq_cell: sample does not fit in LDS");
+  return lds;
+}
+
+// The VJP parks d3 in `out` and reads its other operands afterwards: no overlap with any of them.
+void check_disjoint(const void* out, size_t out_bytes, const void* p, size_t bytes) {
+  if (p == nullptr) return;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(out), b = reinterpret_cast<uintptr_t>(p);
+  if (a < b + bytes && b < a + out_bytes)
+    throw std::runtime_error("deq_cell_vjp: out must not alias u, grad or the state");
+}
+
 template <typename K>
 void set_lds(K kernel, size_t lds) {
   if (lds > 160 * 1024) throw std::runtime_error("deq_cell: sample does not fit in LDS");
@@ -625,6 +640,7 @@ void deq_cell_fwd(const void* z, const void* x, const void* w1, const void* w2, 
                   float* const* mean, float* const* rstd, int64_t N, int64_t H, int64_t W, int64_t C, int64_t G,
                   float eps, hipStream_t stream, int64_t out_stride) {
   const CellShape s = cell_shape(N, H, W, C, G, eps);
+  const size_t lds = checked_lds(s);
   check16({z, x, w1, w2, out, out32, h[0], h[1], h[2]});
   if (out == nullptr && out32 == nullptr) throw std::runtime_error("deq_cell_fwd: no output");
   if (out32 != nullptr && out32_stride % 4 != 0) throw std::runtime_error("deq_cell_fwd: out32 stride % 4");
@@ -639,7 +655,6 @@ void deq_cell_fwd(const void* z, const void* x, const void* w1, const void* w2, 
     a.st.mean[i] = mean[i];
     a.st.rstd[i] = rstd[i];
   }
-  const size_t lds = cell_lds(s);
   static bool attr = false;
   if (!attr) {
     set_lds(deq_cell_fwd_kernel, 160 * 1024);
@@ -653,12 +668,28 @@ void deq_cell_vjp(const void* u, const void* const* h, const void* w2t, const vo
                   const float* const* mean, const float* const* rstd, void* out, const void* grad, float* ss_part,
                   int64_t N, int64_t H, int64_t W, int64_t C, int64_t G, hipStream_t stream) {
   const CellShape s = cell_shape(N, H, W, C, G, 0.f);
+  const size_t lds = checked_lds(s);
   check16({u, h[0], h[1], h[2], w2t, w1t, out, grad});
   if ((grad == nullptr) != (ss_part == nullptr)) throw std::runtime_error("deq_cell_vjp: grad and ss_part go together");
+  if (out == nullptr) throw std::runtime_error("deq_cell_vjp: no output");
   if (out == u) throw std::runtime_error("deq_cell_vjp: out must not alias u");
   for (int i = 0; i < 3; ++i)
     if (mean[i] == nullptr || rstd[i] == nullptr || h[i] == nullptr)
       throw std::runtime_error("deq_cell_vjp: missing state");
+  {
+    const size_t act = static_cast<size_t>(N) * s.HW * kC * sizeof(bf16), st = static_cast<size_t>(N) * s.G * sizeof(float);
+    check_disjoint(out, act, u, act);
+    check_disjoint(out, act, grad, act);
+    check_disjoint(out, act, ss_part, static_cast<size_t>(N) * sizeof(float));
+    check_disjoint(out, act, w2t, static_cast<size_t>(kC) * kK * sizeof(bf16));
+    check_disjoint(out, act, w1t, static_cast<size_t>(kC) * kK * sizeof(bf16));
+    for (int i = 0; i < 3; ++i) {
+      check_disjoint(out, act, h[i], act);
+      check_disjoint(out, act, mean[i], st);
+      check_disjoint(out, act, rstd[i], st);
+      check_disjoint(out, act, gn_w[i], kC * sizeof(float));
+    }
+  }
   VjpArgs a{static_cast<const bf16*>(u), {}, static_cast<const bf16*>(w2t), static_cast<const bf16*>(w1t), {}, {}, {},
             static_cast<bf16*>(out), static_cast<const bf16*>(grad), ss_part};
   for (int i = 0; i < 3; ++i) {
@@ -667,7 +698,6 @@ void deq_cell_vjp(const void* u, const void* const* h, const void* w2t, const vo
     a.mean[i] = mean[i];
     a.rstd[i] = rstd[i];
   }
-  const size_t lds = cell_lds(s);
   static bool attr = false;
   if (!attr) {
     set_lds(deq_cell_vjp_kernel, 160 * 1024);

@@ -33,6 +33,14 @@ def _cl(t: torch.Tensor) -> bool:
     return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
 
 
+def _overlap(a: torch.Tensor, b) -> bool:
+    """Whether two dense tensors share any byte."""
+    if b is None:
+        return False
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
 def supported(cell, z: torch.Tensor) -> bool:
     """Whether the fused kernels take this cell at ``z``'s shape (bf16 channels_last, 48 channels,
     H*W a multiple of 16 that fits LDS, equal group counts and eps in the three GroupNorms)."""
@@ -105,7 +113,8 @@ def cell_vjp(cell, state, u: torch.Tensor, grad: torch.Tensor | None = None, out
     ``grad``: the adjoint iteration's update is fused in — returns ``(u_new, part)`` with
     ``u_new = bf16(J^T u + grad)`` and ``part[n]`` the per-sample ``sum (u_new - u)^2`` (sum them
     with :func:`adjoint_check`): one launch instead of the VJP + ``adjoint_step`` pair. ``out``
-    (channels_last bf16 like ``u``, not ``u`` itself): written instead of a new tensor."""
+    (channels_last bf16 like ``u``, sharing no memory with ``u``, ``grad`` or the state's h tensors;
+    else a new tensor is made): written instead of a new tensor."""
     from .gemm import filter_t
     C = _ext.get(required=True)
     zs, (h1, m1, r1, w1), (h2, m2, r2, w2), (h3, m3, r3, w3) = state
@@ -118,9 +127,6 @@ def cell_vjp(cell, state, u: torch.Tensor, grad: torch.Tensor | None = None, out
             t.shape != (n, G) or t.dtype != torch.float32 for t in (m1, r1, m2, r2, m3, r3)):
         raise ValueError("deq_cell.cell_vjp: state does not match the gradient's shape")
     w2t, w1t = filter_t(cell.conv2.weight), filter_t(cell.conv1.weight)  # [ci][tap * co], taps flipped
-    if out is None or out.shape != u.shape or out.dtype != torch.bfloat16 or not _cl(out) or \
-            out.data_ptr() == u.data_ptr():
-        out = torch.empty_like(u, memory_format=torch.channels_last)
     part = None
     if grad is not None:
         if not _cl(grad) or grad.dtype != torch.bfloat16:
@@ -128,6 +134,11 @@ def cell_vjp(cell, state, u: torch.Tensor, grad: torch.Tensor | None = None, out
         if grad.shape != u.shape:
             raise ValueError("deq_cell.cell_vjp: grad does not match u")
         part = torch.empty(n, device=u.device, dtype=torch.float32)
+    # the kernel parks d3 in ``out`` and reads u, grad and the state afterwards: an ``out`` that
+    # shares memory with any of them is not written (the launcher raises on it)
+    if out is None or out.shape != u.shape or out.dtype != torch.bfloat16 or not _cl(out) or \
+            any(_overlap(out, t) for t in (u, grad, *hs)):
+        out = torch.empty_like(u, memory_format=torch.channels_last)
     C.deq_cell_vjp(u.data_ptr(), [t.data_ptr() for t in hs], w2t.data_ptr(), w1t.data_ptr(),
                    [_ptr(w1), _ptr(w2), _ptr(w3)], [m1.data_ptr(), m2.data_ptr(), m3.data_ptr()],
                    [r1.data_ptr(), r2.data_ptr(), r3.data_ptr()], out.data_ptr(), _ptr(grad), _ptr(part),

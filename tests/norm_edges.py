@@ -28,6 +28,8 @@ Reduction lengths L (closed forms that may over-count, never read from the exten
         are summed in float64 by the test)
     GroupNorm (HW pixels, C, G)      cv = C / 8, PL = max(1, min(256 // cv, (16384 - 2C - 2G) // (2C)))
         pixel lanes, cpg = C / G: L_px = ceil(HW / PL) + PL per channel, L_gn = L_px + cpg per group
+        (``gn_refs`` / ``gn_check_fwd`` take another kernel's L_gn as ``L``, ``gn_bwd_refs`` / ``gn_check_bwd`` its
+        L_px as ``Lpx``: the fused DEQ cell's are 19 + cpg and 19, ``deq_cell_edges``)
 
 Statistics of the single-pass form (BatchNorm per channel, GroupNorm per group; n values, A1 = mean|x|,
 A2 = mean x^2, kappa = (mean^2 + var) / var = A2 / var):
@@ -615,30 +617,32 @@ def gn_groups(t, G):
     return t.view(N, HW, G, C // G).permute(0, 2, 1, 3).reshape(N, G, -1)
 
 
-def gn_refs(h, w, b, G, dtype, eps=1e-5):
-    """h [N, HW, C] (the stored h). float64 mean / rstd [N, G], y [N, HW, C] and their bounds."""
+def gn_refs(h, w, b, G, dtype, eps=1e-5, L=None):
+    """h [N, HW, C] (the stored h). float64 mean / rstd [N, G], y [N, HW, C] and their bounds. ``L``: the
+    per-group reduction length L_gn of another kernel (default: groupnorm.hip's)."""
     N, HW, C = h.shape
     cpg = C // G
     mean, var, a1, a2 = stats_ref(gn_groups(h, G), 2)
-    rstd, dmean, drstd, kappa = single_pass_bounds(gn_Lpx(HW, C, G) + cpg, mean, var, a1, a2, eps)
+    rstd, dmean, drstd, kappa = single_pass_bounds(gn_Lpx(HW, C, G) + cpg if L is None else L, mean, var, a1, a2, eps)
     print(f"    kappa max {float(kappa.max()):.3g}")
     ex = lambda t: t.repeat_interleave(cpg, 1)[:, None, :]  # [N, G] -> [N, 1, C]
     _, y, _, dy = affine_fwd_ref(h, w, b, None, False, ex(mean), ex(rstd), ex(dmean), ex(drstd), dtype)
     return dict(mean=mean, rstd=rstd, y=y, dmean=dmean + TINY, drstd=drstd + TINY, dy=dy)
 
 
-def gn_check_fwd(tag, h, w, b, G, out, dtype, errs, eps=1e-5):
-    r = gn_refs(h, w, b, G, dtype, eps)
+def gn_check_fwd(tag, h, w, b, G, out, dtype, errs, eps=1e-5, L=None):
+    r = gn_refs(h, w, b, G, dtype, eps, L)
     E.check(f"{tag} mean", out["mean"], r["mean"], r["dmean"], errs)
     E.check(f"{tag} rstd", out["rstd"], r["rstd"], r["drstd"], errs)
     E.check(f"{tag} y", out["y"], r["y"], r["dy"], errs)
 
 
-def gn_check_bwd(tag, dy, h, mean32, rstd32, w, G, relu, out, dtype, errs, exact=False):
-    """``out``: dh [N, HW, C] and optionally part [N, 2, C] (dw, db per sample). Returns the per-sample
-    references and bounds (dw, ddw, db, ddb)."""
+def gn_bwd_refs(dy, h, mean32, rstd32, w, G, relu, dtype, Lpx=None):
+    """The float64 backward from the stored h and statistics and the gradient dy [N, HW, C] (any float
+    dtype), with its bounds: dict(dh, ddh (the stored dh's, u_T |dh| included), dw, ddw, db, ddb).
+    ``Lpx``: the per-channel reduction length L_px of another kernel (default: groupnorm.hip's)."""
     N, HW, C = h.shape
-    cpg, M, Lp = C // G, HW * (C // G), gn_Lpx(HW, C, G)
+    cpg, M, Lp = C // G, HW * (C // G), gn_Lpx(HW, C, G) if Lpx is None else Lpx
     dyd, hd = dy.double(), h.double()
     wd = torch.ones(C, dtype=torch.float64, device=h.device) if w is None else w.double()
     ex = lambda t: t.double().repeat_interleave(cpg, 1)  # [N, G] -> [N, C]
@@ -657,7 +661,15 @@ def gn_check_bwd(tag, dy, h, mean32, rstd32, w, G, relu, out, dtype, errs, exact
            + 4 * U32 * rs[:, None] * ((dyd * wd).abs() + m1.abs()[:, None] + (xh * m2[:, None]).abs()))
     if relu:
         dh, ddh = dh * (hd > 0), ddh * (hd > 0)
-    E.check(f"{tag} dh", out["dh"], dh, ddh + rt(dtype, dh) + TINY, errs)
+    return dict(dh=dh, ddh=ddh + rt(dtype, dh) + TINY, dw=dw, ddw=ddw, db=S, ddb=dS)
+
+
+def gn_check_bwd(tag, dy, h, mean32, rstd32, w, G, relu, out, dtype, errs, exact=False, Lpx=None):
+    """``out``: dh [N, HW, C] and optionally part [N, 2, C] (dw, db per sample). Returns the per-sample
+    references and bounds (dw, ddw, db, ddb)."""
+    r = gn_bwd_refs(dy, h, mean32, rstd32, w, G, relu, dtype, Lpx)
+    dw, ddw, S, dS = r["dw"], r["ddw"], r["db"], r["ddb"]
+    E.check(f"{tag} dh", out["dh"], r["dh"], r["ddh"], errs)
     if out.get("part") is not None:
         E.check(f"{tag} dw", out["part"][:, 0], dw, ddw + TINY, errs)
         E.check(f"{tag} db", out["part"][:, 1], S, None if exact else dS + TINY, errs)
