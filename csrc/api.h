@@ -26,9 +26,11 @@ void mt_sumsq(const std::vector<uintptr_t>& src, const std::vector<int64_t>& num
 
 // ---- fused optimisers ---------------------------------------------------------
 struct AdamHyper {
-  float lr, beta1, beta2, eps;
-  float bc1, bc2;     // 1 - beta1^t, 1 - beta2^t (host mode)
-  float weight_decay;  // Optimisers.jl WeightDecay after Adam (AdamW = chain)
+  // doubles, as RuleHyper's: fp64 leaves compute with the caller's values; the fp32 kernels round
+  // them once, to what the caller's fp32 value was
+  double lr, beta1, beta2, eps;
+  double bc1, bc2;     // 1 - beta1^t, 1 - beta2^t (host mode)
+  double weight_decay;  // Optimisers.jl WeightDecay after Adam (AdamW = chain)
   float grad_scale;    // multiplies the incoming gradient (e.g. 1/world for mean)
   const float* dev;    // optional device hyper block {lr, beta1^t, beta2^t} (graph mode)
   const float* dev_gscale;  // optional device gradient scale (e.g. 1/loss_scale, the global-norm clip)
@@ -51,7 +53,8 @@ void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
 void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream, const int32_t* dev_skip = nullptr);
 
 struct SgdHyper {
-  float lr, momentum, weight_decay, grad_scale;
+  double lr, momentum, weight_decay;  // doubles: as in AdamHyper
+  float grad_scale;
   int nesterov;  // 0: heavy ball (Optimisers.Momentum), 1: Optimisers.Nesterov
   const float* dev_lr;
   const float* dev_gscale = nullptr;  // as in AdamHyper

@@ -50,8 +50,8 @@ template <typename R, typename... A> auto skip_last(R (*fn)(uintptr_t, A...)) {
 }
 
 static void py_mt_adam(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
-                       const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, float lr, float beta1,
-                       float beta2, float eps, float bc1, float bc2, float weight_decay, float grad_scale,
+                       const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
+                       double beta2, double eps, double bc1, double bc2, double weight_decay, float grad_scale,
                        uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale, float clip_delta) {
   AdamHyper h{lr, beta1, beta2, eps, bc1, bc2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
               ptr<const float*>(dev_gscale)};
@@ -62,7 +62,7 @@ static void py_mt_adam(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptr
 }
 
 static void py_mt_sgd(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel,
-                      int p_dtype, int g_dtype, int s_dtype, float lr, float momentum, float weight_decay,
+                      int p_dtype, int g_dtype, int s_dtype, double lr, double momentum, double weight_decay,
                       float grad_scale, int nesterov, uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale,
                       uintptr_t tscale, float clip_delta) {
   SgdHyper h{lr, momentum, weight_decay, grad_scale, nesterov, ptr<const float*>(dev_lr)};

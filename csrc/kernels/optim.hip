@@ -50,6 +50,7 @@ struct AdamElem {
   using C = typename Comp<P>::type;
   C lr, b1, b2, eps, bc1, bc2, wd, gs, ts, delta;
   __device__ __forceinline__ void operator()(P& p, G g_in, S& m_io, S& v_io, float& w) const {
+#pragma clang fp contract(off)  // as written: see the note above the rule functors of optim_rules.hip
     const C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     const C m = b1 * static_cast<C>(m_io) + (C(1) - b1) * g;
     const C v = b2 * static_cast<C>(v_io) + (C(1) - b2) * (g * g);
@@ -72,15 +73,16 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
   const int t = ch.t;
 
   AdamElem<P, G, S, MASTER> op;
-  C lr = h.lr, bc1 = h.bc1, bc2 = h.bc2;
+  C lr = static_cast<C>(h.lr), bc1 = static_cast<C>(h.bc1), bc2 = static_cast<C>(h.bc2);
   if (h.dev != nullptr) {  // graph mode: step-dependent scalars live on the device
-    lr = h.dev[0];
+    lr = static_cast<C>(h.dev[0]);
     bc1 = C(1) - static_cast<C>(h.dev[1]);
     bc2 = C(1) - static_cast<C>(h.dev[2]);
   }
   op.lr = lr; op.bc1 = bc1; op.bc2 = bc2;
-  op.b1 = h.beta1; op.b2 = h.beta2; op.eps = h.eps; op.wd = h.weight_decay;
-  op.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  op.b1 = static_cast<C>(h.beta1); op.b2 = static_cast<C>(h.beta2); op.eps = static_cast<C>(h.eps);
+  op.wd = static_cast<C>(h.weight_decay);
+  op.gs = static_cast<C>(h.grad_scale) * (h.dev_gscale ? static_cast<C>(*h.dev_gscale) : C(1));
   op.ts = h.tscale ? static_cast<const C*>(h.tscale)[a.tidx[t]] : C(1);
   op.delta = h.clip_delta;
 
@@ -131,6 +133,7 @@ struct SgdElem {
   C lr, rho, wd, gs, ts, delta;
   int mode;  // 0 descent, 1 momentum, 2 nesterov
   __device__ __forceinline__ void operator()(P& p, G g_in, S& buf, float& w) const {
+#pragma clang fp contract(off)
     C x = MASTER ? static_cast<C>(w) : static_cast<C>(p);
     C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     if (wd != C(0)) g += wd * x;
@@ -159,12 +162,12 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
   SgdElem<P, G, S, MASTER> op;
-  op.lr = h.dev_lr ? *h.dev_lr : h.lr;
-  op.rho = h.momentum; op.wd = h.weight_decay;
-  op.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  op.lr = h.dev_lr ? static_cast<C>(*h.dev_lr) : static_cast<C>(h.lr);
+  op.rho = static_cast<C>(h.momentum); op.wd = static_cast<C>(h.weight_decay);
+  op.gs = static_cast<C>(h.grad_scale) * (h.dev_gscale ? static_cast<C>(*h.dev_gscale) : C(1));
   op.ts = h.tscale ? static_cast<const C*>(h.tscale)[a.tidx[t]] : C(1);
   op.delta = h.clip_delta;
-  op.mode = h.momentum == 0.f ? 0 : (h.nesterov ? 2 : 1);
+  op.mode = h.momentum == 0. ? 0 : (h.nesterov ? 2 : 1);
   P* __restrict__ p = reinterpret_cast<P*>(a.p[t]);
   const G* __restrict__ g = reinterpret_cast<const G*>(a.g[t]);
   S* __restrict__ buf = reinterpret_cast<S*>(a.s1[t]);
@@ -392,7 +395,7 @@ void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& g
             const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype,
             const SgdHyper& h, hipStream_t stream) {
   const bool has_master = !master.empty();
-  if (h.momentum != 0.f && buf.size() != numel.size())
+  if (h.momentum != 0. && buf.size() != numel.size())
     throw std::runtime_error("mt_sgd: momentum needs buffers");
   for_each_group(param, grad, buf, {}, {}, master, numel, [&](const OptArgs& a, int blocks) {
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_sgd", [&](auto p, auto g, auto s, auto master) {

@@ -44,6 +44,27 @@ __device__ __forceinline__ C clip_grad(C g, C delta) {
   return g;
 }
 
+// load8 / store8 for a pointer that may miss 16-byte alignment (`vec` false): element by element then, in
+// the same thread -> element layout, so a reduction over a thread's elements adds in the same order
+template <typename T>
+__device__ __forceinline__ void load8_any(bool vec, const T* __restrict__ p, T (&out)[kVec]) {
+  if (vec) {
+    load8(p, out);
+  } else {
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) out[j] = p[j];
+  }
+}
+template <typename T>
+__device__ __forceinline__ void store8_any(bool vec, T* __restrict__ p, const T (&in)[kVec]) {
+  if (vec) {
+    store8(p, in);
+  } else {
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) p[j] = in[j];
+  }
+}
+
 // This workgroup's job: chunk c of the nb chunks of leaf t, elements [base, end) of the leaf.
 struct Chunk {
   int t, c, nb;

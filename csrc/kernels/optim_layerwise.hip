@@ -65,13 +65,14 @@ __device__ __forceinline__ LwScalars<C> lw_scalars(const RuleHyper& h, bool lamb
   s.b1 = static_cast<C>(h.beta1); s.b2 = static_cast<C>(h.beta2); s.eps = static_cast<C>(h.eps);
   s.trust = static_cast<C>(h.beta2);
   s.wd = static_cast<C>(h.weight_decay);
-  s.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  s.gs = static_cast<C>(h.grad_scale) * (h.dev_gscale ? static_cast<C>(*h.dev_gscale) : C(1));
   return s;
 }
 
 // LAMB's update direction from the stored moments (both phases call this on the same values)
 template <typename C>
 __device__ __forceinline__ C lamb_u(const LwScalars<C>& s, C m, C v, C x) {
+#pragma clang fp contract(off)  // as written: see the note above the rule functors of optim_rules.hip
   C u = m / s.bc1 / (sqrt(v / s.bc2) + s.eps);
   if (s.wd != C(0)) u += s.wd * x;
   return u;
@@ -80,6 +81,7 @@ __device__ __forceinline__ C lamb_u(const LwScalars<C>& s, C m, C v, C x) {
 // the trust ratio from the leaf's sums of squares (sx: of x; sy: of g (LARS) / u (LAMB))
 template <bool LAMB, typename C>
 __device__ __forceinline__ C lw_ratio(const LwScalars<C>& s, C sx, C sy) {
+#pragma clang fp contract(off)
   const C xn = sqrt(sx), yn = sqrt(sy);
   if (!(xn > C(0) && yn > C(0))) return C(1);
   return LAMB ? xn / yn : s.trust * xn / (yn + s.wd * xn + s.eps);
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper
   C ax = C(0), ay = C(0);
   // one element: x, the scaled gradient and (LAMB) the moments in and out
   auto elem = [&](C x, G g_in, S& m_io, S& v_io) {
+#pragma clang fp contract(off)
     const C gg = static_cast<C>(g_in) * s.gs;
     ax += x * x;
     if (LAMB) {
@@ -127,27 +130,26 @@ __global__ __launch_bounds__(kThreads) void lw_stats_kernel(OptArgs a, RuleHyper
     }
   };
 
+  // A thread owns the same elements whether or not the leaf is 16-byte aligned (unaligned: element
+  // loads in the vector layout), so its sums add in one order and the ratio does not depend on alignment.
   const bool vec = aligned16(g) && (MASTER ? aligned16(w) : aligned16(p)) && (!LAMB || (aligned16(m) && aligned16(v)));
-  int64_t scalar_from = ch.base;
-  if (vec) {
-    const int64_t nvec = (ch.end - ch.base) / kVec;
+  const int64_t nvec = (ch.end - ch.base) / kVec;
 #pragma unroll
-    for (int k = 0; k < kIters; ++k) {
-      const int64_t vi = tid + k * kThreads;
-      if (vi < nvec) {
-        const int64_t off = ch.base + vi * kVec;
-        P pv[kVec]; G gv[kVec]; S mv[kVec]; S vv[kVec]; float wv[kVec];
-        load8(g + off, gv);
-        if (LAMB) { load8(m + off, mv); load8(v + off, vv); }
-        if (MASTER) load8(w + off, wv); else load8(p + off, pv);
+  for (int k = 0; k < kIters; ++k) {
+    const int64_t vi = tid + k * kThreads;
+    if (vi < nvec) {
+      const int64_t off = ch.base + vi * kVec;
+      P pv[kVec]; G gv[kVec]; S mv[kVec]; S vv[kVec]; float wv[kVec];
+      load8_any(vec, g + off, gv);
+      if (LAMB) { load8_any(vec, m + off, mv); load8_any(vec, v + off, vv); }
+      if (MASTER) load8_any(vec, w + off, wv); else load8_any(vec, p + off, pv);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j)
-          elem(MASTER ? static_cast<C>(wv[j]) : static_cast<C>(pv[j]), gv[j], mv[j], vv[j]);
-        if (LAMB) { store8(m + off, mv); store8(v + off, vv); }
-      }
+      for (int j = 0; j < kVec; ++j)
+        elem(MASTER ? static_cast<C>(wv[j]) : static_cast<C>(pv[j]), gv[j], mv[j], vv[j]);
+      if (LAMB) { store8_any(vec, m + off, mv); store8_any(vec, v + off, vv); }
     }
-    scalar_from = ch.base + nvec * kVec;
   }
+  const int64_t scalar_from = ch.base + nvec * kVec;
   for (int64_t i = scalar_from + tid; i < ch.end; i += kThreads) {
     S mv = LAMB ? m[i] : S(0), vv = LAMB ? v[i] : S(0);
     elem(MASTER ? static_cast<C>(w[i]) : static_cast<C>(p[i]), g[i], mv, vv);
@@ -202,6 +204,7 @@ __global__ __launch_bounds__(kThreads) void lw_apply_kernel(OptArgs a, RuleHyper
 
   // one element: LARS reads the gradient and rewrites the velocity; LAMB reads m and v
   auto elem = [&](P& p_io, G g_in, S& a_io, S v_in, float& w_io) {
+#pragma clang fp contract(off)
     C x = MASTER ? static_cast<C>(w_io) : static_cast<C>(p_io);
     if (LAMB) {
       x -= step * lamb_u(s, static_cast<C>(a_io), static_cast<C>(v_in), x);

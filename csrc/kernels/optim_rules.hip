@@ -48,13 +48,17 @@ struct RuleScalars {
 };
 
 // Rule functors: dx = op(g, s1, s2, s3) and the new state. kStates: state tensors the rule
-// keeps; kBt: it reads beta^t (bias correction).
+// keeps; kBt: it reads beta^t (bias correction). No fp contraction in any element functor of the
+// optimiser kernels: which product of a*b + c*d the compiler fused differed between the vector and
+// the scalar path of one kernel (Lion fp32: a packed fma against two multiplies and an add), so a
+// leaf's bits depended on its alignment. As written, both paths round alike.
 template <typename C>
 struct RmsPropRule {
   static constexpr int kStates = 1;
   static constexpr bool kBt = false;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& acc, C&, C&) const {
+#pragma clang fp contract(off)
     acc = h.b1 * acc + (C(1) - h.b1) * (g * g);
     return g * h.lr / (sqrt(acc) + h.eps);
   }
@@ -66,6 +70,7 @@ struct AdaGradRule {
   static constexpr bool kBt = false;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& acc, C&, C&) const {
+#pragma clang fp contract(off)
     acc = acc + g * g;
     return g * h.lr / (sqrt(acc) + h.eps);
   }
@@ -77,6 +82,7 @@ struct LionRule {
   static constexpr bool kBt = false;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& m, C&, C&) const {
+#pragma clang fp contract(off)
     const C a = h.b1 * m + (C(1) - h.b1) * g;
     m = h.b2 * m + (C(1) - h.b2) * g;
     // torch.sign: 0 -> 0, NaN -> NaN (a * 0 keeps the NaN)
@@ -91,6 +97,7 @@ struct AdaMaxRule {
   static constexpr bool kBt = true;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& m, C& u, C&) const {
+#pragma clang fp contract(off)
     m = h.b1 * m + (C(1) - h.b1) * g;
     u = nan_max(h.b2 * u, g < C(0) ? -g : g);
     return h.lr / (C(1) - h.bt1) * m / (u + h.eps);
@@ -103,6 +110,7 @@ struct AmsGradRule {
   static constexpr bool kBt = false;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& m, C& v, C& vh) const {
+#pragma clang fp contract(off)
     m = h.b1 * m + (C(1) - h.b1) * g;
     v = h.b2 * v + (C(1) - h.b2) * (g * g);
     vh = nan_max(vh, v);
@@ -116,6 +124,7 @@ struct NAdamRule {
   static constexpr bool kBt = true;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& m, C& v, C&) const {
+#pragma clang fp contract(off)
     m = h.b1 * m + (C(1) - h.b1) * g;
     v = h.b2 * v + (C(1) - h.b2) * (g * g);
     const C num = h.b1 * m / (C(1) - h.b1 * h.bt1) + (C(1) - h.b1) * g / (C(1) - h.bt1);
@@ -129,6 +138,7 @@ struct AdaBeliefRule {
   static constexpr bool kBt = true;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& m, C& s, C&) const {
+#pragma clang fp contract(off)
     m = h.b1 * m + (C(1) - h.b1) * g;
     const C d = g - m;
     s = h.b2 * s + (C(1) - h.b2) * (d * d) + h.eps;
@@ -142,6 +152,7 @@ struct AdaDeltaRule {
   static constexpr bool kBt = false;
   RuleScalars<C> h;
   __device__ __forceinline__ C operator()(C g, C& acc, C& delta, C&) const {
+#pragma clang fp contract(off)
     acc = h.b1 * acc + (C(1) - h.b1) * (g * g);
     const C dx = g * sqrt(delta + h.eps) / sqrt(acc + h.eps);
     delta = h.b1 * delta + (C(1) - h.b1) * (dx * dx);
@@ -156,6 +167,7 @@ struct RuleElem {
   R rule;
   C wd, gs, ts, delta;
   __device__ __forceinline__ void operator()(P& p, G g_in, S& a_io, S& b_io, S& c_io, float& w) const {
+#pragma clang fp contract(off)
     const C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     C a = static_cast<C>(a_io);
     C b = R::kStates > 1 ? static_cast<C>(b_io) : C(0);
@@ -194,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
   op.rule.h.b1 = static_cast<C>(h.beta1); op.rule.h.b2 = static_cast<C>(h.beta2);
   op.rule.h.eps = static_cast<C>(h.eps);
   op.wd = static_cast<C>(h.weight_decay);
-  op.gs = h.grad_scale * (h.dev_gscale ? *h.dev_gscale : 1.f);
+  op.gs = static_cast<C>(h.grad_scale) * (h.dev_gscale ? static_cast<C>(*h.dev_gscale) : C(1));
   op.ts = h.tscale ? static_cast<const C*>(h.tscale)[a.tidx[t]] : C(1);
   op.delta = h.clip_delta;
 

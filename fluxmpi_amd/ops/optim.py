@@ -54,6 +54,18 @@ def _tscale_ptr(tscale, idx, ct, n) -> int:
     return tscale[torch.tensor(idx, device=tscale.device)].data_ptr()
 
 
+def _f32(v: float) -> float:
+    """``v`` as the kernels' ``float`` arguments (``grad_scale``, ``clip_delta``) hold it."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _scalars(ct: torch.dtype, *vals):
+    """The step's scalars as the kernels hold them: each rounded once to the compute type ``ct``, so that
+    ``1 - beta`` is formed in ``ct`` from the rounded ``beta`` (fp32: off by up to 3e-5 of ``1 - 0.999``
+    from the double's) and a CPU step is the kernel's to rounding."""
+    return [torch.tensor(float(v), dtype=ct) for v in vals]
+
+
 def _ptr(t: torch.Tensor | None) -> int:
     """Device address of an optional tensor; 0 when it is not given."""
     return t.data_ptr() if t is not None else 0
@@ -92,11 +104,12 @@ def _dtype_groups(name: str, params, grads, states, masters, slots: int) -> list
     (empty without), the element counts and the three dtype codes.
 
     ``TypeError`` unless every leaf's gradient, states (of one dtype; a call without states counts as
-    the parameter's) and fp32 master have the parameter's element count — the kernels index all of
-    them by it — and the kernels are built for the group's dtypes."""
+    the parameter's, or as fp32 beside a master: the mixed-precision layout) and fp32 master have
+    the parameter's element count — the kernels index all of them by it — and the kernels are built
+    for the group's dtypes."""
     groups: dict = {}
     for i, p in enumerate(params):
-        sd = states[0][i].dtype if states else p.dtype
+        sd = states[0][i].dtype if states else (torch.float32 if masters is not None else p.dtype)
         if any(s[i].dtype != sd or s[i].numel() != p.numel() for s in states) or grads[i].numel() != p.numel() \
                 or (masters is not None and (masters[i].dtype != torch.float32 or masters[i].numel() != p.numel())):
             raise TypeError(f"fused {name}: leaf {i}: gradient, states and master must match the parameter's "
@@ -145,6 +158,7 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     if dev_hyper is not None:
         h = dev_hyper.tolist()
         lr, bc1, bc2 = h[0], 1.0 - float(torch.tensor(h[1])), 1.0 - float(torch.tensor(h[2]))
+    grad_scale, clip_delta = _f32(grad_scale), _f32(clip_delta)
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     adam_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bc1=bc1,
@@ -167,14 +181,15 @@ def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, e
         return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        lr_, b1, b2, eps_, c1, c2, wd = _scalars(ct, lr, beta1, beta2, eps, bc1, bc2, weight_decay)
         g = grads[i].to(ct) * grad_scale if grad_scale != 1.0 else grads[i].to(ct)
         g = _clip_reference(g, i, tscale, clip_delta)
-        m = exp_avgs[i].to(ct) * beta1 + (1 - beta1) * g
-        v = exp_avg_sqs[i].to(ct) * beta2 + (1 - beta2) * (g * g)
+        m = exp_avgs[i].to(ct) * b1 + (1 - b1) * g
+        v = exp_avg_sqs[i].to(ct) * b2 + (1 - b2) * (g * g)
         x = masters[i].to(ct) if masters is not None else p.to(ct)
-        dx = m / bc1 / (torch.sqrt(v / bc2) + eps) * lr
+        dx = m / c1 / (torch.sqrt(v / c2) + eps_) * lr_
         if weight_decay != 0.0:
-            dx = dx + weight_decay * x
+            dx = dx + wd * x
         x = x - dx
         exp_avgs[i].copy_(m)
         exp_avg_sqs[i].copy_(v)
@@ -219,6 +234,7 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
         return
     if dev_lr is not None:
         lr = float(dev_lr.reshape(-1)[0])
+    grad_scale, clip_delta = _f32(grad_scale), _f32(clip_delta)
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     sgd_reference_(params, grads, bufs, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay,
@@ -231,20 +247,21 @@ def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, wei
         return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        lr_, rho, wd = _scalars(ct, lr, momentum, weight_decay)
         x = masters[i].to(ct) if masters is not None else p.to(ct)
         g = _clip_reference(grads[i].to(ct) * grad_scale, i, tscale, clip_delta)
         if weight_decay:
-            g = g + weight_decay * x
+            g = g + wd * x
         if momentum == 0.0:
-            dx = g * lr
+            dx = g * lr_
         elif not nesterov:
-            vel = momentum * bufs[i].to(ct) + lr * g
+            vel = rho * bufs[i].to(ct) + lr_ * g
             bufs[i].copy_(vel)
             dx = vel
         else:
             vel0 = bufs[i].to(ct)
-            dx = -(momentum * momentum) * vel0 + (1 + momentum) * lr * g
-            bufs[i].copy_(momentum * vel0 - lr * g)
+            dx = -(rho * rho) * vel0 + (1 + rho) * lr_ * g
+            bufs[i].copy_(rho * vel0 - lr_ * g)
         x = x - dx
         if masters is not None:
             masters[i].copy_(x)
@@ -314,6 +331,7 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
         lr = h[0]
         if has_bt:
             bt1, bt2 = h[1], h[2]
+    grad_scale, clip_delta = _f32(grad_scale), _f32(clip_delta)
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     rule_reference_(kind, params, grads, states, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
@@ -331,9 +349,10 @@ def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta
         return
     if rho is not None:
         beta1 = rho
-    b1, b2 = beta1, beta2
+    hyper = (lr, beta1, beta2, eps, bt1, bt2, weight_decay)
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        lr, b1, b2, eps, bt1, bt2, wd = _scalars(ct, *hyper)
         g = grads[i].to(ct) * grad_scale if grad_scale != 1.0 else grads[i].to(ct)
         g = _clip_reference(g, i, tscale, clip_delta)
         s = [st[i].to(ct) for st in states]
@@ -345,7 +364,8 @@ def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta
             s[0] = s[0] + g * g
             dx = g * lr / (torch.sqrt(s[0]) + eps)
         elif kind == "lion":
-            dx = lr * torch.sign(s[0] * b1 + (1 - b1) * g)
+            a = s[0] * b1 + (1 - b1) * g
+            dx = lr * torch.where(torch.isnan(a), a, torch.sign(a))  # torch.sign(NaN) is 0; the kernel keeps the NaN
             s[0] = s[0] * b2 + (1 - b2) * g
         elif kind == "adamax":
             s[0] = s[0] * b1 + (1 - b1) * g
@@ -369,7 +389,7 @@ def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta
             dx = g * torch.sqrt(s[1] + eps) / torch.sqrt(s[0] + eps)
             s[1] = s[1] * b1 + (1 - b1) * (dx * dx)
         if weight_decay != 0.0:
-            dx = dx + weight_decay * x
+            dx = dx + wd * x
         x = x - dx
         for k in range(ns):
             states[k][i].copy_(s[k])
@@ -467,6 +487,7 @@ def lars_(params, grads, bufs, *, lr: float, momentum: float, trust: float, weig
         return
     if dev_hyper is not None:
         lr = float(dev_hyper.reshape(-1)[0])
+    grad_scale = _f32(grad_scale)
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     lars_reference_(params, grads, bufs, lr=lr, momentum=momentum, trust=trust, weight_decay=weight_decay, eps=eps,
@@ -497,6 +518,7 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
     if dev_hyper is not None:
         h = dev_hyper.tolist()
         lr, bt1, bt2 = h[0], h[1], h[2]
+    grad_scale = _f32(grad_scale)
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
@@ -515,12 +537,13 @@ def lars_reference_(params, grads, bufs, *, lr, momentum, trust, weight_decay=0.
         return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        lr_, rho, tr, wd, eps_ = _scalars(ct, lr, momentum, trust, weight_decay, eps)
         x = masters[i].to(ct) if masters is not None else p.to(ct)
         g = grads[i].to(ct) * grad_scale
         xn, gn = _norm(x), _norm(g)
-        q = torch.where((xn > 0) & (gn > 0), trust * xn / (gn + weight_decay * xn + eps), torch.ones_like(xn))
-        d = g + weight_decay * x if weight_decay else g
-        vel = momentum * bufs[i].to(ct) + lr * (q * d)
+        q = torch.where((xn > 0) & (gn > 0), tr * xn / (gn + wd * xn + eps_), torch.ones_like(xn))
+        d = g + wd * x if weight_decay else g
+        vel = rho * bufs[i].to(ct) + lr_ * (q * d)
         bufs[i].copy_(vel)
         x = x - vel
         if ratios is not None:
@@ -538,16 +561,17 @@ def lamb_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, e
         return
     for i, p in enumerate(params):
         ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+        lr_, b1, b2, eps_, t1, t2, wd = _scalars(ct, lr, beta1, beta2, eps, bt1, bt2, weight_decay)
         x = masters[i].to(ct) if masters is not None else p.to(ct)
         g = grads[i].to(ct) * grad_scale
-        exp_avgs[i].copy_(exp_avgs[i].to(ct) * beta1 + (1 - beta1) * g)
-        exp_avg_sqs[i].copy_(exp_avg_sqs[i].to(ct) * beta2 + (1 - beta2) * (g * g))
-        u = exp_avgs[i].to(ct) / (1 - bt1) / (torch.sqrt(exp_avg_sqs[i].to(ct) / (1 - bt2)) + eps)
+        exp_avgs[i].copy_(exp_avgs[i].to(ct) * b1 + (1 - b1) * g)
+        exp_avg_sqs[i].copy_(exp_avg_sqs[i].to(ct) * b2 + (1 - b2) * (g * g))
+        u = exp_avgs[i].to(ct) / (1 - t1) / (torch.sqrt(exp_avg_sqs[i].to(ct) / (1 - t2)) + eps_)
         if weight_decay:
-            u = u + weight_decay * x
+            u = u + wd * x
         xn, un = _norm(x), _norm(u)
         q = torch.where((xn > 0) & (un > 0), xn / un, torch.ones_like(xn))
-        x = x - (lr * q) * u
+        x = x - (lr_ * q) * u
         if ratios is not None:
             ratios[i] = q
         if masters is not None:
