@@ -341,6 +341,9 @@ void check_layout(const void* X, const void* F, int64_t d, int64_t row_stride, i
     throw std::runtime_error("anderson: d and strides must be multiples of 4 elements");
   if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(F)) & 15u) != 0)
     throw std::runtime_error("anderson: X and F must be 16-byte aligned");
+  // every kernel reads rows 0 .. n-1 of each batch element
+  if ((n - 1) * row_stride + d > batch_stride)
+    throw std::runtime_error("anderson: rows 0 .. n-1 do not fit in batch_stride");
 }
 
 }  // namespace
@@ -376,7 +379,8 @@ void anderson_gram(const void* X, const void* F, int f_dtype, void* G, unsigned 
   if (G != nullptr && (reinterpret_cast<uintptr_t>(G) & 15u) != 0)
     throw std::runtime_error("anderson_gram: G must be 16-byte aligned");
   if (last < 0 || last >= n) throw std::runtime_error("anderson_gram: last row out of range");
-  if (bsz > 65535) throw std::runtime_error("anderson_gram: bsz > 65535");
+  if (bsz < 1 || bsz > 65535) throw std::runtime_error("anderson_gram: need 1 <= bsz <= 65535");
+  if (chunks < 1) throw std::runtime_error("anderson_gram: need chunks >= 1");
   const int64_t d4 = d / 4;
   const int64_t chunk4 = (d4 + chunks - 1) / chunks;
   dim3 grid(chunks, static_cast<unsigned>(bsz));

@@ -127,20 +127,24 @@ def mix(X: torch.Tensor, F: torch.Tensor, alpha: torch.Tensor, slot: int, beta: 
         z_dtype: torch.dtype | None = None):
     """``X[:, slot] = beta * alpha F[:, :n] + (1 - beta) * alpha X[:, :n]`` in place (n = alpha.shape[1]).
 
-    Returns the new iterate as a ``[bsz, d]`` tensor of ``z_dtype`` (a fresh copy when it is not fp32;
-    the ``X[:, slot]`` view otherwise)."""
+    Returns the new iterate as a ``[bsz, d]`` tensor of ``z_dtype`` (``None``: the history's dtype) for
+    every (history, ``z_dtype``) pair: the ``X[:, slot]`` view where that is the stored row (``None``, or an
+    fp32 ``z_dtype`` on an fp32 history), otherwise a fresh tensor holding the fp32 mix rounded once to
+    ``z_dtype`` (unrounded for an fp32 ``z_dtype`` on a bf16 history)."""
     n = alpha.shape[1]
     if not _native(X, F, n):
         new = beta * torch.bmm(alpha[:, None], F[:, :n].float())[:, 0]
         if beta != 1.0:
             new = new + (1 - beta) * torch.bmm(alpha[:, None], X[:, :n].float())[:, 0]
         X[:, slot] = new
-        return X[:, slot] if z_dtype in (None, X.dtype) else new.to(z_dtype)
+        if z_dtype is None or (z_dtype == torch.float32 and X.dtype == torch.float32):
+            return X[:, slot]
+        return new.to(z_dtype)
     C = _ext.get(required=True)
     bsz, _, d = X.shape
     a = alpha.float().contiguous()
     z = None
-    if z_dtype not in (None, torch.float32):
+    if not (z_dtype is None or (z_dtype == torch.float32 and X.dtype == torch.float32)):
         z = torch.empty(bsz, d, device=X.device, dtype=z_dtype)
     C.anderson_mix(X.data_ptr(), F.data_ptr(), DTYPE_CODE[F.dtype], a.data_ptr(), z.data_ptr() if z is not None else 0,
                    DTYPE_CODE[z_dtype] if z is not None else 7, bsz, d, X.stride(1), X.stride(0), n, slot, float(beta),

@@ -127,8 +127,8 @@ def test_anderson_mix_gpu(n, beta, zdt, fdt, hdt):
     assert torch.equal(X[:, others], keep[:, others])
     if zdt is not None:
         assert z.dtype == zdt and z.shape == (bsz, d)
-        if hdt == torch.float32:
-            torch.testing.assert_close(z.float(), X[:, slot].to(zdt).float())
+        if hdt == torch.float32:  # one fp32 value, rounded once to zdt by the kernel and by the cast
+            assert torch.equal(z, X[:, slot].to(zdt))
         else:  # z is the fp32 mix rounded to zdt, X[:, slot] the same value rounded to bf16
             torch.testing.assert_close(z.double(), want, rtol=8e-3, atol=1e-3)
 
@@ -364,7 +364,7 @@ def test_anderson_gram_stored_g_gpu(n, fdt, hdt):
     exact = hdt == torch.float32
     tol = dict(rtol=1e-4, atol=1e-3 * d ** 0.5) if exact else dict(rtol=1e-2, atol=2e-2 * d ** 0.5)
     H0, _ = AO.gram(X, Fv, n, n - 1, G, tuple(range(n)))  # all rows fresh: fills G
-    torch.testing.assert_close(G[:, :n], (Fv[:, :n].float() - X[:, :n].float()).to(hdt))
+    assert torch.equal(G[:, :n], (Fv[:, :n].float() - X[:, :n].float()).to(hdt))  # one correctly rounded operation
     s = n // 2  # one row changes (the newest, `last`): only it is recomputed, the others come from G
     X[:, s].normal_()
     Fv[:, s].normal_()
@@ -372,7 +372,7 @@ def test_anderson_gram_stored_g_gpu(n, fdt, hdt):
     Hr, fr = _ref_gram(X.float(), Fv.float(), n, s)
     torch.testing.assert_close(H.double(), Hr, **tol)
     torch.testing.assert_close(fn.double(), fr, rtol=1e-4, atol=1e-3)
-    torch.testing.assert_close(G[:, s], (Fv[:, s].float() - X[:, s].float()).to(hdt))
+    assert torch.equal(G[:, s], (Fv[:, s].float() - X[:, s].float()).to(hdt))
     # a fresh row that is not `last`: every row is recomputed from F - X (same result)
     t = (s + 1) % n
     X[:, t].normal_()
