@@ -10,14 +10,17 @@ namespace fluxmpi {
 
 // ---- multi-tensor copy / cast / scale (pack, unpack, scale) -----------------
 // dst[i][k] = (Tout)(src[i][k] * scale) for k < numel[i]. src[i] may equal dst[i]
-// (in-place scale / cast is not allowed when the element sizes differ).
+// (in-place scale / cast is not allowed when the element sizes differ). The product is formed in
+// fp64 with the caller's double when the source or the destination is fp64, else in fp32 with the
+// scale rounded once to fp32; it is then rounded once to Tout.
 void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& dst,
-             const std::vector<int64_t>& numel, int in_dtype, int out_dtype, float scale,
+             const std::vector<int64_t>& numel, int in_dtype, int out_dtype, double scale,
              hipStream_t stream);
 
-// Fill every tensor with `value` (zeroing flat grad buckets).
+// Fill every tensor with `value` (zeroing flat grad buckets): fp64 leaves take the double, the
+// others the value rounded once to fp32 and then to the leaf's dtype.
 void mt_fill(const std::vector<uintptr_t>& dst, const std::vector<int64_t>& numel, int dtype,
-             float value, hipStream_t stream);
+             double value, hipStream_t stream);
 
 // Sum of squares of all tensors into out[0] (fp32, atomically accumulated; out must be
 // zeroed by the caller). Used by ClipNorm and by debug checksums.

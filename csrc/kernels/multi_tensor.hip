@@ -34,22 +34,23 @@ struct CopyArgs {
   int n;
 };
 
+// The product type of a copy: fp64 when the source or the destination is fp64 (the caller's double
+// scale, unrounded), else fp32 (the scale rounded once to fp32 on the host). One IEEE multiply in
+// that type, then one round-to-nearest-even conversion to Tout.
 template <typename Tin, typename Tout>
-__device__ __forceinline__ Tout cvt(Tin x, float scale) {
-  using A = typename Acc<Tin>::type;
-  return static_cast<Tout>(static_cast<A>(x) * static_cast<A>(scale));
-}
-template <>
-__device__ __forceinline__ double cvt<double, double>(double x, float scale) {
-  return x * static_cast<double>(scale);
-}
-template <>
-__device__ __forceinline__ double cvt<float, double>(float x, float scale) {
-  return static_cast<double>(x) * static_cast<double>(scale);
+using Prod = std::conditional_t<std::is_same_v<Tin, double> || std::is_same_v<Tout, double>, double, float>;
+
+template <typename Tin, typename Tout>
+__device__ __forceinline__ Tout cvt(Tin x, Prod<Tin, Tout> scale) {
+  Prod<Tin, Tout> p = static_cast<Prod<Tin, Tout>>(x) * scale;
+  // fp16 stores: keep the multiply apart from the conversion. The compiler otherwise contracts the scalar
+  // loops' pair into v_fma_mixlo_f16 x, scale, +0, and (-0) * scale + (+0) is +0: the sign of a zero was lost
+  if constexpr (std::is_same_v<Tout, f16> && std::is_same_v<Prod<Tin, Tout>, float>) asm("" : "+v"(p));
+  return static_cast<Tout>(p);
 }
 
 template <typename Tin, typename Tout>
-__global__ __launch_bounds__(kThreads) void mt_copy_kernel(CopyArgs a, float scale) {
+__global__ __launch_bounds__(kThreads) void mt_copy_kernel(CopyArgs a, Prod<Tin, Tout> scale) {
   const int b = blockIdx.x;
   const int t = find_tensor(a.start, a.n, b);
   const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void mt_copy_kernel(CopyArgs a, float sca
 }
 
 template <typename T>
-__global__ __launch_bounds__(kThreads) void mt_fill_kernel(CopyArgs a, float value) {
+__global__ __launch_bounds__(kThreads) void mt_fill_kernel(CopyArgs a, typename Acc<T>::type value) {
   const int b = blockIdx.x;
   const int t = find_tensor(a.start, a.n, b);
   const int64_t base = static_cast<int64_t>(b - a.start[t]) * kChunk;
@@ -193,7 +194,7 @@ void for_each_group(const std::vector<uintptr_t>& src, const std::vector<uintptr
 }  // namespace
 
 void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& dst,
-             const std::vector<int64_t>& numel, int in_dtype, int out_dtype, float scale,
+             const std::vector<int64_t>& numel, int in_dtype, int out_dtype, double scale,
              hipStream_t stream) {
   if (src.size() != numel.size() || dst.size() != numel.size())
     throw std::runtime_error("mt_copy: list length mismatch");
@@ -208,7 +209,7 @@ void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& ds
         using Tin = typename decltype(in)::type;
         using Tout = typename decltype(out)::type;
         if constexpr (std::is_same_v<Tin, double> && sizeof(Tout) == 2) dispatch_fail(bad_out);
-        else mt_copy_kernel<Tin, Tout><<<blocks, kThreads, 0, stream>>>(a, scale);
+        else mt_copy_kernel<Tin, Tout><<<blocks, kThreads, 0, stream>>>(a, static_cast<Prod<Tin, Tout>>(scale));
       });
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
@@ -216,10 +217,12 @@ void mt_copy(const std::vector<uintptr_t>& src, const std::vector<uintptr_t>& ds
 }
 
 void mt_fill(const std::vector<uintptr_t>& dst, const std::vector<int64_t>& numel, int dtype,
-             float value, hipStream_t stream) {
+             double value, hipStream_t stream) {
   for_each_group({}, dst, numel, [&](const CopyArgs& a, int blocks) {
     dispatch_float64(dtype, "mt_fill: unsupported dtype", [&](auto t) {
-      mt_fill_kernel<typename decltype(t)::type><<<blocks, kThreads, 0, stream>>>(a, value);
+      // fp64 leaves take the caller's double, the others the value rounded once to fp32
+      using T = typename decltype(t)::type;
+      mt_fill_kernel<T><<<blocks, kThreads, 0, stream>>>(a, static_cast<typename Acc<T>::type>(value));
     });
     FLUXMPI_HIP_CHECK(hipGetLastError());
   });

@@ -43,6 +43,14 @@ def _code(dt: torch.dtype) -> int:
         raise TypeError(f"dtype {dt} not supported by the multi-tensor kernels") from None
 
 
+def _scaled(src: torch.Tensor, out_dtype: torch.dtype, scale: float) -> torch.Tensor:
+    """``src * scale`` as the kernels form it: one multiply in fp64 with the caller's double when the source
+    or the destination is fp64, else in fp32 with the scale rounded once to fp32; then one rounding to
+    ``out_dtype``."""
+    wide = torch.float64 if torch.float64 in (src.dtype, out_dtype) else torch.float32
+    return (src.to(wide) * torch.tensor(scale, dtype=wide)).to(out_dtype)
+
+
 def pack(tensors, flat: torch.Tensor, offsets, scale: float = 1.0) -> torch.Tensor:
     """Gather ``tensors`` into ``flat`` at element ``offsets`` (cast to ``flat.dtype``, times ``scale``)."""
     if not tensors:
@@ -65,7 +73,7 @@ def pack(tensors, flat: torch.Tensor, offsets, scale: float = 1.0) -> torch.Tens
         if scale == 1.0:
             seg.copy_(t.reshape(-1))
         else:
-            seg.copy_(t.reshape(-1).to(torch.promote_types(t.dtype, torch.float32)) * scale)
+            seg.copy_(_scaled(t.reshape(-1), flat.dtype, scale))
     return flat
 
 
@@ -91,7 +99,7 @@ def unpack(flat: torch.Tensor, tensors, offsets, scale: float = 1.0):
         if scale == 1.0:
             t.copy_(seg)
         else:
-            t.copy_(seg.to(torch.promote_types(seg.dtype, torch.float32)) * scale)
+            t.copy_(_scaled(seg, t.dtype, scale))
     return tensors
 
 
@@ -100,7 +108,7 @@ def scale_(tensors, scale: float):
     gpu = [t for t in tensors if t.is_cuda]
     cpu = [t for t in tensors if not t.is_cuda]
     for t in cpu:
-        t.mul_(scale)
+        t.copy_(_scaled(t, t.dtype, scale))
     if gpu:
         C = _ext.get(required=True)
         groups: dict = {}
@@ -116,7 +124,9 @@ def fill_(tensors, value: float = 0.0):
     gpu = [t for t in tensors if t.is_cuda]
     for t in tensors:
         if not t.is_cuda:
-            t.fill_(value)
+            # as the kernel: fp64 leaves take the double, the others the value rounded once to fp32 and then to
+            # the leaf's dtype (70000 is +inf in fp16, where Tensor.fill_ refuses the double)
+            t.copy_(torch.tensor(value, dtype=torch.float64 if t.dtype == torch.float64 else torch.float32))
     if gpu:
         C = _ext.get(required=True)
         groups: dict = {}

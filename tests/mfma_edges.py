@@ -261,11 +261,14 @@ def check_colsums(name, family, shards, y, errs, squares=True):
 
 # ------------------------------------------------------------------------------- guard bands
 
+_BITS16 = (torch.bfloat16, torch.float16)  # the 16-bit sentinel serves both (0x5A5A is 203.25 as fp16)
+
+
 def guarded(rows, cols, ld, dtype, device, lead=1, fill=float("nan")):
     """A ``[rows, cols]`` view (row stride ``ld``) filled with NaN (``fill``) inside a buffer of sentinel bit
     patterns: ``lead`` whole rows before it, the columns ``cols .. ld`` of every row, one row after."""
-    it = torch.int16 if dtype == torch.bfloat16 else torch.int32
-    sent = BF16_SENTINEL if dtype == torch.bfloat16 else F32_SENTINEL
+    it = torch.int16 if dtype in _BITS16 else torch.int32
+    sent = BF16_SENTINEL if dtype in _BITS16 else F32_SENTINEL
     buf = torch.full(((rows + lead + 1) * ld,), sent, dtype=it, device=device).view(dtype)
     view = buf[lead * ld:(lead + rows) * ld].view(rows, ld)[:, :cols]
     view.fill_(fill)
@@ -275,8 +278,8 @@ def guarded(rows, cols, ld, dtype, device, lead=1, fill=float("nan")):
 def take_guarded(name, buf, view, errs):
     """The view's contents, after checking that every sentinel around it survived."""
     out = view.clone()
-    it = torch.int16 if buf.dtype == torch.bfloat16 else torch.int32
-    sent = BF16_SENTINEL if buf.dtype == torch.bfloat16 else F32_SENTINEL
+    it = torch.int16 if buf.dtype in _BITS16 else torch.int32
+    sent = BF16_SENTINEL if buf.dtype in _BITS16 else F32_SENTINEL
     view.view(it).fill_(sent)
     broken = int((buf.view(it) != sent).sum())
     if broken:
@@ -325,9 +328,14 @@ def _rcp(x):
     return 1.0 / x
 
 
-def gelu_emulated(x, form):
+def gelu_emulated(x, form, dtype=torch.bfloat16):
     """(gelu(x), gelu'(x)) as the EPI 1 epilogue of gemm_nt.hip / gelu_tanh.h evaluates and stores them
-    (bf16), in float32 PyTorch (exp2 and the reciprocal are correctly rounded here, 1 ulp on the device)."""
+    (bf16), in float32 PyTorch (exp2 and the reciprocal are correctly rounded here, 1 ulp on the device).
+    ``dtype``: the store's type (fp16: the fp16 instantiations of gelu.hip); ``None``: the unrounded
+    float32 values (gelu.hip's backward multiplies the fp32 derivative and rounds only the product)."""
+    def rn_bf16(v):  # the store
+        return v if dtype is None else v.float().to(dtype)
+
     x = x.float()
     one, half = torch.tensor(1.0), torch.tensor(0.5)
     if form == "tanh":

@@ -86,7 +86,9 @@ def test_gelu_bwd_bias_kernel_gpu(form):
     dh, db = gelu_bwd_bias(dy, h)
     hf = h.float().requires_grad_()
     GL.gelu(hf).backward(dy.float())
-    torch.testing.assert_close(dh.float(), hf.grad, rtol=1e-2, atol=1e-2)
+    # test_glue_edges_gpu's criterion: the bf16 store's 2^-8 (here with room for the fp32 reference), and
+    # |dy| c32 2^-23 (|d| + 1) <= 5.5 * 33 * 2^-23 * 2.2 = 4.8e-5 for the unrounded fp32 derivative
+    torch.testing.assert_close(dh.float(), hf.grad, rtol=4e-3, atol=1e-4)
     torch.testing.assert_close(db, dh.float().sum(0), rtol=1e-4, atol=1e-3)
 
 

@@ -59,7 +59,8 @@ def test_scale_fill_sumsq(gpu_ext):
         assert torch.equal(t, r)
     s = mt.sumsq(ts)
     exp = sum(float((t.double() ** 2).sum()) for t in ts)
-    assert abs(float(s) - exp) / exp < 1e-5
+    # glue_edges' bound: 32 fmas per lane, 6 wave levels, 3 wave totals, one atomic for each of the 17 workgroups
+    assert abs(float(s) - exp) / exp < (32 + 6 + 3 + 17) * 2.0 ** -23
     mt.fill_(ts, 0.25)
     assert all(torch.all(t == 0.25) for t in ts)
     bf = _tensors(torch.bfloat16, dev, 2)
