@@ -216,6 +216,8 @@ void bn_sync_bwd_dx(const void* dy, const void* x, const void* y, const uint8_t*
 // Dual BatchNorm of a downsample block: y = relu(BN(x) + BN2(x2)) (+ 1-bit ReLU mask), and its
 // backward: dx, dx2 and both BatchNorms' dweight/dbias from one reduce + one dx pass over
 // (dy, mask, x, x2). ws/ws2: two zeroed statistics workspaces. C/8 must divide 256.
+// bn_bwd_dual with dx == dx2 == null stops after the reduce and the finalize (the four finished sums
+// in dweight / dbias / dweight2 / dbias2), as bn_bwd does for a null dx; exactly one null is an error.
 void bn_apply_dual(const void* x, const void* x2, void* y, const float* w, const float* b, const float* save_mean,
                    const float* save_invstd, const float* w2, const float* b2, const float* save_mean2,
                    const float* save_invstd2, int64_t rows, int64_t C, uint8_t* relu_mask, int dtype,
@@ -354,6 +356,21 @@ void gemm_bf16(const GemmProblem& g, hipStream_t stream);
 // res = a2 [M][64] (ldr = 64); ldc = 64. splits = the slab count = the workgroups launched, the
 // caller's choice: min(ceil(M / 64), 2 x compute units) fills the device with one round.
 void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream);
+// conv3ds_bwd.hip: the same around the dual BatchNorm of a stage-1 downsample block,
+// out = relu(bn3(conv3(a2)) + bn_ds(conv_ds(x))), both convolutions 1x1, 64 -> 256, stride 1. One pass
+// over (dy [P][256], the 1-bit ReLU mask, c3, c_ds [P][256], a2, x [P][64]) forms dx3 and dx_ds in
+// registers (bit for bit what bn_bwd_dual's dx pass stores from the same finished sums) and writes
+// d_a2 = dx3 . W3, d_xside = dx_ds . W_ds ([P][64] bf16) and the fp32 partials ws3 / wsds
+// [slabs][256][64] of dx3^T . a2 / dx_ds^T . x (sum each with gemm_splitk_reduce). w / w2: the
+// BatchNorm weights (nullable: 1); sum_dy* / sum_dy_xhat*: [256] fp32, bn_bwd_dual's dbias* / dweight*
+// (call it with dx = dx2 = null). wt3 / wtds: the filters [256][64] as stored. Every pointer 16-byte
+// aligned. slabs = the workgroups launched, the caller's choice: min(ceil(P / 32), compute units)
+// fills the device with one round (one workgroup of 512 lanes and 112 KiB of LDS per compute unit).
+void conv3ds_bwd(const void* dy, const uint8_t* relu_mask, const void* c3, const void* cds, const float* w,
+                 const float* save_mean, const float* save_invstd, const float* sum_dy, const float* sum_dy_xhat,
+                 const float* w2, const float* save_mean2, const float* save_invstd2, const float* sum_dy2,
+                 const float* sum_dy_xhat2, const void* a2, const void* x, const void* wt3, const void* wtds,
+                 void* d_a2, void* d_xside, float* ws3, float* wsds, int64_t P, int slabs, hipStream_t stream);
 // the LDS-DMA pipelined kernel: K-major A (or implicit conv) and B, modes 0/1, optional residual,
 // no prologue affine / split-K / BN-backward epilogue
 bool gemm_glds_supported(const GemmProblem& g);

@@ -134,6 +134,17 @@ PYBIND11_MODULE(_C_ema, m) {
         py::arg("dev_skip"), py::arg("stream"));
 }
 
+// The one-pass backward of the stage-1 downsample block (conv3ds_bwd.hip): a fourth module, loaded by
+// fluxmpi_amd.ops._ext.c3ds().
+PYBIND11_MODULE(_C_c3ds, m) {
+  m.doc() = "fluxmpi_amd native library: one-pass backward around the dual BatchNorm of a downsample block";
+  m.def("conv3ds_bwd", raw(&conv3ds_bwd), py::arg("dy"), py::arg("mask"), py::arg("c3"), py::arg("cds"), py::arg("w"),
+        py::arg("mean"), py::arg("inv"), py::arg("sum_dy"), py::arg("sum_dy_xhat"), py::arg("w2"), py::arg("mean2"),
+        py::arg("inv2"), py::arg("sum_dy2"), py::arg("sum_dy_xhat2"), py::arg("a2"), py::arg("x"), py::arg("wt3"),
+        py::arg("wtds"), py::arg("d_a2"), py::arg("d_xside"), py::arg("ws3"), py::arg("wsds"), py::arg("P"),
+        py::arg("slabs"), py::arg("stream"));
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
 

@@ -608,7 +608,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
 }
 
 // The dx pass: dx = A*dy_eff + B*x + D per channel (DxCoef, dx_coef, dx_vec: bn_dx.h, shared with
-// conv3bn3_bwd.hip). Coefficients in registers (FIXED) or LDS as in bn_norm_kernel; two vectors
+// conv3bn3_bwd.hip and conv3ds_bwd.hip). Coefficients in registers (FIXED) or LDS as in bn_norm_kernel; two vectors
 // per lane per iteration.
 template <typename T, int RM, bool DRES, bool FIXED, int U = 2>
 __global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ x,
@@ -802,12 +802,11 @@ __device__ __forceinline__ void dx_coef8(const float* __restrict__ w, const floa
   ld8ch(dw, c0, kdw);
   ld8ch(w ? w : mean, c0, ww);  // unconditional: see bn_norm_kernel
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float sc = (w ? ww[j] : 1.f) * iv[j];
-    const float k2 = kdb[j] * inv_n, k3 = kdw[j] * inv_n;
-    a[j] = sc;
-    bb[j] = -sc * iv[j] * k3;
-    d[j] = sc * (m[j] * iv[j] * k3 - k2);
+  for (int j = 0; j < 8; ++j) {  // the one copy of the arithmetic (bn_dx.h); no ReLU recompute here: no shift
+    const DxCoef k = dx_coef_of(w != nullptr, ww[j], false, 0.f, m[j], iv[j], kdw[j], kdb[j], inv_n);
+    a[j] = k.a;
+    bb[j] = k.b;
+    d[j] = k.d;
   }
 }
 
@@ -1018,6 +1017,8 @@ void bn_bwd_dual(const void* dy, const uint8_t* mask, const void* x, const void*
                  hipStream_t s) {
   check_dual(C, mask);
   check_aligned({w, sm, si, w2, sm2, si2, dw, db, dw2, db2});
+  if ((dx == nullptr) != (dx2 == nullptr))
+    throw std::runtime_error("dual batchnorm: bn_bwd_dual takes both dx and dx2, or neither (reduce and finalize only)");
   dispatch_float(dtype, kBadDualDtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     const T* dyr = static_cast<const T*>(dy);
@@ -1030,6 +1031,8 @@ void bn_bwd_dual(const void* dy, const uint8_t* mask, const void* x, const void*
     bn_finalize_bwd2_kernel<<<dim3(finalize_blocks(C), 2), kFinCh * kFinGroups, 0, s>>>(ws, ws2, (int)C, dw, db, dw2,
                                                                                         db2);
     FLUXMPI_HIP_CHECK(hipGetLastError());
+    // dx == dx2 == nullptr: reduce and finalize only (the consumer forms both dx itself from the four sums)
+    if (dx == nullptr) return;
     const int64_t nvec = rows * C / 8;
     auto k = bn_bwd_dx_dual_kernel<T>;
     k<<<elementwise_grid(reinterpret_cast<const void*>(k), 0, nvec), kThreads, 0, s>>>(

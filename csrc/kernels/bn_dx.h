@@ -1,5 +1,6 @@
 // The BatchNorm input-gradient arithmetic, shared by every kernel that forms dx (batchnorm.hip's dx
-// pass and conv3bn3_bwd.hip, which forms the same dx in registers): one copy, so the bits agree.
+// passes, single and dual, and conv3bn3_bwd.hip / conv3ds_bwd.hip, which form the same dx in registers): one
+// copy, so the bits agree.
 //
 // dx = w*invstd * (dy_eff - sum_dy/R - xhat * sum_dy_xhat/R); dres = dy_eff
 // (sum_dy = db, sum_dy_xhat = dw, produced by bn_finalize_bwd_kernel), evaluated as

@@ -161,6 +161,7 @@ class Bottleneck(nn.Module):
                 # it. (And after bn1 consumed conv1's epilogue statistics: the downsample BN uses
                 # the same statistics workspace.)
                 cds = None  # downsample conv output whose BN is fused into bn3 (dual_bn_relu)
+                c3ds = False
                 if self.downsample is None:
                     identity = x
                 elif fused_ds:
@@ -168,13 +169,18 @@ class Bottleneck(nn.Module):
                     dual = fb.dual_bn_ok(x, ds[0].out_channels, self.bn3, ds[1])
                     # our GEMM (+ the downsample BN's sums in its epilogue) where measured faster
                     ds_stats = dual and fb.ds_forward_is_ours(x, ds[0].weight, ds[0].stride[0])
-                    identity = fb.conv1x1_downsample(x, ds[0].weight, ds[0].stride[0],
-                                                     link if isinstance(link, fb.SideGradLink) else None,
-                                                     ours_stats=ds_stats)
-                    if dual:
-                        cds, identity = identity, None
-                    else:
-                        identity = ds[1](identity)
+                    # stage-1 downsample block: the downsample conv, conv3 and the dual BatchNorm become
+                    # one node below (after conv2), whose backward forms neither BatchNorm's input gradient
+                    c3ds = self.hybrid and fb.conv3ds_ok(x, self.conv2, self.conv3, self.bn3, ds[0], ds[1])
+                    identity = None
+                    if not c3ds:
+                        identity = fb.conv1x1_downsample(x, ds[0].weight, ds[0].stride[0],
+                                                         link if isinstance(link, fb.SideGradLink) else None,
+                                                         ours_stats=ds_stats)
+                        if dual:
+                            cds, identity = identity, None
+                        else:
+                            identity = ds[1](identity)
                 else:
                     identity = self.downsample(x)
                 if self.hybrid:
@@ -197,6 +203,9 @@ class Bottleneck(nn.Module):
                         # stage-1 identity block: conv3 -> bn3 as one node, whose backward forms bn3's
                         # input gradient in registers (one pass instead of dx + dgrad + wgrad)
                         return fb.conv3_bn3_relu(a2, self.conv3, self.bn3, identity, link, ours_fwd=o3)
+                    if c3ds:
+                        return fb.conv3ds_bn_relu(a2, self.conv3, self.bn3, x, ds[0], ds[1], link, ours3=o3,
+                                                  ours_ds=ds_stats)
                     c3 = fb.conv1x1_hybrid(a2, self.conv3.weight, None, ours_stats=o3)
                 else:
                     c2 = fb.conv3x3(a1, self.conv2.weight) if fb.conv3x3_supported(a1, self.conv2) else self.conv2(a1)

@@ -109,6 +109,12 @@ def ema():
     return _extra("_C_ema", "the weight-EMA entries")
 
 
+def c3ds():
+    """The ``_C_c3ds`` module: ``conv3ds_bwd`` (the one-pass backward around the dual BatchNorm of a
+    stage-1 downsample block, ``csrc/kernels/conv3ds_bwd.hip``)."""
+    return _extra("_C_c3ds", "the downsample-block backward entry")
+
+
 def require_for(t: torch.Tensor):
     """The extension if ``t`` lives on the GPU (mandatory there), else ``None``."""
     if t.is_cuda:

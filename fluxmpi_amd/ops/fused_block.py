@@ -503,6 +503,39 @@ def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True):
                            bn.eps, nbt, link, bool(ours_fwd))
 
 
+def _dual_bn_fwd(c3, bn, stats_ready, cds, bn2, ds_ready):
+    """The forward launches of relu(bn(c3) + bn2(cds)): two finalizes (a statistics pass first where the
+    sums are not pending) and one dual apply. ``bn`` / ``bn2``: (weight, bias, running_mean, running_var,
+    momentum, eps, num_batches_tracked). Returns y and (c3, cds, mask, w32, mean, inv, w232, mean2, inv2)."""
+    C = _ext.get(required=True)
+    cl = torch.channels_last
+    w, b, rm, rv, mom, eps, nbt = bn
+    w2, b2, rm2, rv2, mom2, eps2, nbt2 = bn2
+    c3 = c3 if c3.is_contiguous(memory_format=cl) else c3.contiguous(memory_format=cl)
+    cds = cds if cds.is_contiguous(memory_format=cl) else cds.contiguous(memory_format=cl)
+    ch = c3.shape[1]
+    rows = c3.numel() // ch
+    f32 = dict(device=c3.device, dtype=torch.float32)
+    w32, b32, w232, b232 = w.float(), b.float(), w2.float(), b2.float()
+    mean, inv, mean2, inv2 = (torch.empty(ch, **f32) for _ in range(4))
+    ws, code, st = _workspace(c3), DTYPE_CODE[c3.dtype], _stream(c3)
+    # bn3 first: its sums may be pending in the workspace (conv3's GEMM epilogue)
+    C.bn_stats_finalize(c3.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(rm), _p(rv), mean.data_ptr(),
+                        inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(mom), float(eps), int(stats_ready),
+                        code, st, _p(nbt))
+    # bn_ds: its sums pending in the dual workspace (the downsample GEMM's epilogue), or a stats pass
+    ws2 = _dual_workspace(c3) if ds_ready else ws
+    C.bn_stats_finalize(cds.data_ptr(), w232.data_ptr(), b232.data_ptr(), _p(rm2), _p(rv2), mean2.data_ptr(),
+                        inv2.data_ptr(), 0, 0, ws2.data_ptr(), rows, ch, float(mom2), float(eps2), int(ds_ready),
+                        code, st, _p(nbt2))
+    y = torch.empty_like(c3)
+    mask = torch.empty(c3.numel() // 8, device=c3.device, dtype=torch.uint8)
+    C.bn_apply_dual(c3.data_ptr(), cds.data_ptr(), y.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
+                    inv.data_ptr(), w232.data_ptr(), b232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), rows, ch,
+                    mask.data_ptr(), code, st)
+    return y, (c3, cds, mask, w32, mean, inv, w232, mean2, inv2)
+
+
 class _DualBN(torch.autograd.Function):
     """out = relu(bn3(c3) + bn_ds(c_ds)) for a ResNet downsample block, without materialising the
     downsample branch's output bn_ds(c_ds). Forward: bn3's statistics (pending from the conv3
@@ -516,33 +549,11 @@ class _DualBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c3, w, b, rm, rv, mom, eps, nbt, stats_ready, cds, w2, b2, rm2, rv2, mom2, eps2, nbt2,
                 ds_ready=False):
-        C = _ext.get(required=True)
-        cl = torch.channels_last
-        c3 = c3 if c3.is_contiguous(memory_format=cl) else c3.contiguous(memory_format=cl)
-        cds = cds if cds.is_contiguous(memory_format=cl) else cds.contiguous(memory_format=cl)
-        ch = c3.shape[1]
-        rows = c3.numel() // ch
-        f32 = dict(device=c3.device, dtype=torch.float32)
-        w32, b32, w232, b232 = w.float(), b.float(), w2.float(), b2.float()
-        mean, inv, mean2, inv2 = (torch.empty(ch, **f32) for _ in range(4))
-        ws, code, st = _workspace(c3), DTYPE_CODE[c3.dtype], _stream(c3)
-        # bn3 first: its sums may be pending in the workspace (conv3's GEMM epilogue)
-        C.bn_stats_finalize(c3.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(rm), _p(rv), mean.data_ptr(),
-                            inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(mom), float(eps), int(stats_ready),
-                            code, st, _p(nbt))
-        # bn_ds: its sums pending in the dual workspace (the downsample GEMM's epilogue), or a stats pass
-        ws2 = _dual_workspace(c3) if ds_ready else ws
-        C.bn_stats_finalize(cds.data_ptr(), w232.data_ptr(), b232.data_ptr(), _p(rm2), _p(rv2), mean2.data_ptr(),
-                            inv2.data_ptr(), 0, 0, ws2.data_ptr(), rows, ch, float(mom2), float(eps2), int(ds_ready),
-                            code, st, _p(nbt2))
-        y = torch.empty_like(c3)
-        mask = torch.empty(c3.numel() // 8, device=c3.device, dtype=torch.uint8)
-        C.bn_apply_dual(c3.data_ptr(), cds.data_ptr(), y.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
-                        inv.data_ptr(), w232.data_ptr(), b232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), rows, ch,
-                        mask.data_ptr(), code, st)
+        y, saved = _dual_bn_fwd(c3, (w, b, rm, rv, mom, eps, nbt), stats_ready, cds,
+                                (w2, b2, rm2, rv2, mom2, eps2, nbt2), ds_ready)
         ctx.wdtypes = (w.dtype, w2.dtype)
         ctx.params = (w, b, w2, b2)
-        ctx.save_for_backward(c3, cds, mask, w32, mean, inv, w232, mean2, inv2)
+        ctx.save_for_backward(*saved)
         return y
 
     @staticmethod
@@ -594,6 +605,121 @@ def dual_bn_ok(x, ch, bn, bn_ds) -> bool:
             and ch % 8 == 0 and 8 <= ch <= 2048 and (ch & (ch - 1)) == 0
             and all(isinstance(m, FusedBatchNorm2d) and m.training and m.affine and m.track_running_stats
                     for m in (bn, bn_ds)))
+
+
+class _Conv3DsBN(torch.autograd.Function):
+    """out = relu(bn3(conv3(a2)) + bn_ds(conv_ds(x))) of a stage-1 downsample block (both convolutions
+    1x1, 64 -> 256, stride 1), whose backward materialises neither BatchNorm's input gradient. Forward:
+    exactly the launches of ``conv1x1_hybrid`` + ``conv1x1_downsample`` + ``dual_bn_relu`` (each
+    convolution on its per-shape choice). Backward: the dual reduce + finalize (``bn_bwd_dual`` without a
+    dx), then either one kernel over both branches (``form`` 2: csrc/kernels/conv3ds_bwd.hip) or the
+    identity blocks' kernel once per branch (``form`` 1: ``gemm_bf16`` mode 4 on (dy, c3, mask, a2, W3),
+    then on (dy, c_ds, mask, x, W_ds)), and the two split-K reduces into the filters' gradients. The
+    downsample convolution's input gradient goes to conv1's dgrad epilogue through the block's
+    :class:`SideGradLink`, as ``_Conv1x1Downsample`` hands it over.
+
+    As for ``_Conv3BN3`` the filter gradients always come from the one-pass kernel (no ``wgrad_best``
+    choice), measured at ResNet-50's 56 x 56, batch 256 only (``profiles/c3ds_conv3ds.md``)."""
+
+    @staticmethod
+    def forward(ctx, a2, w3, x, wds, w, b, w2, b2, rm, rv, mom, eps, nbt, rm2, rv2, mom2, eps2, nbt2, link, ours3,
+                ours_ds, form):
+        cl = torch.channels_last
+        a2 = a2 if a2.is_contiguous(memory_format=cl) else a2.contiguous(memory_format=cl)
+        x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
+        note_filter(w3)
+        note_filter(wds)
+        c3 = _fwd1x1_stats(a2, w3, _workspace(a2)) if ours3 else torch.nn.functional.conv2d(a2, w3)
+        cds = _ds_fwd_ours(x, wds, 1, _dual_workspace(x)) if ours_ds else torch.nn.functional.conv2d(x, wds)
+        y, saved = _dual_bn_fwd(c3, (w, b, rm, rv, mom, eps, nbt), ours3, cds, (w2, b2, rm2, rv2, mom2, eps2, nbt2),
+                                ours_ds)
+        ctx.link, ctx.form = link, form
+        ctx.wdtypes = (w.dtype, w2.dtype)
+        ctx.params = (w, b, w2, b2)
+        ctx.save_for_backward(a2, w3, x, wds, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ext.get(required=True)
+        a2, w3, x, wds, c3, cds, mask, w32, mean, inv, w232, mean2, inv2 = ctx.saved_tensors
+        if not dy.is_contiguous(memory_format=torch.channels_last):
+            dy = dy.contiguous(memory_format=torch.channels_last)
+        n, ci, h, w = a2.shape
+        co, rows = w3.shape[0], n * h * w
+        dev, st = dy.device, _stream(dy)
+        dw, db, dw2, db2 = (_grad_out(p, co, c3) for p in ctx.params)
+        # reduce + finalize only (dx = dx2 = null): the four finished sums land in dw / db / dw2 / db2
+        C.bn_bwd_dual(dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(), mean.data_ptr(),
+                      inv.data_ptr(), w232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), 0, 0, dw.data_ptr(),
+                      db.data_ptr(), dw2.data_ptr(), db2.data_ptr(), _workspace(c3).data_ptr(),
+                      _dual_workspace(c3).data_ptr(), rows, co, DTYPE_CODE[c3.dtype], st)
+        d_a2, d_x = _empty_nhwc(n, ci, h, w, a2), _empty_nhwc(n, ci, h, w, x)
+        if ctx.form == 2:
+            slabs = conv3ds_slabs(rows, dev)
+            part = torch.empty(2, slabs, co, ci, device=dev, dtype=torch.float32)
+            _ext.c3ds().conv3ds_bwd(dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(),
+                                    mean.data_ptr(), inv.data_ptr(), db.data_ptr(), dw.data_ptr(), w232.data_ptr(),
+                                    mean2.data_ptr(), inv2.data_ptr(), db2.data_ptr(), dw2.data_ptr(), a2.data_ptr(),
+                                    x.data_ptr(), w3.data_ptr(), wds.data_ptr(), d_a2.data_ptr(), d_x.data_ptr(),
+                                    part[0].data_ptr(), part[1].data_ptr(), rows, slabs, st)
+        else:
+            slabs = conv3bn3_slabs(rows, dev)
+            part = torch.empty(2, slabs, co, ci, device=dev, dtype=torch.float32)
+            for i, (c, cw, cm, civ, sdy, sdx, act, wt, out) in enumerate((
+                    (c3, w32, mean, inv, db, dw, a2, w3, d_a2), (cds, w232, mean2, inv2, db2, dw2, x, wds, d_x))):
+                gemm(dy, wt, out, M=rows, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False, mode=4,
+                     splits=slabs, a_affine=(sdy, sdx), stats=part[i], residual=_nhwc2d(act),
+                     bn_bwd=(c, cw, None, cm, civ, mask, 3))
+        grads = [None, None]
+        for i, wt in enumerate((w3, wds)):
+            if ctx.needs_input_grad[1 + 2 * i]:
+                with graddst.into(wt):
+                    g = graddst.empty((co, ci), wt.dtype, dev)
+                C.gemm_splitk_reduce(part[i].data_ptr(), slabs, co * ci, g.data_ptr(), DTYPE_CODE[g.dtype], st)
+                grads[i] = g.view(co, ci, 1, 1)
+        if ctx.link is not None and ctx.link.offer(d_x):
+            d_x = None  # delivered to conv1's dgrad epilogue
+        t1, t2 = ctx.wdtypes
+        return (d_a2, grads[0], d_x, grads[1], dw.to(t1), db.to(t1), dw2.to(t2), db2.to(t2)) + (None,) * 14
+
+
+# the one-pass backward around the dual BatchNorm of the stage-1 downsample block (FLUXMPI_CONV3DS=0:
+# the dual dx pass + two input-gradient GEMMs + two weight-gradient kernels; 1, the default: the
+# identity blocks' one-pass kernel once per branch; 2: one kernel over both branches,
+# csrc/kernels/conv3ds_bwd.hip, 366 us against 2 x 191 us per step and no faster end to end than
+# the run-to-run spread: profiles/c3ds_conv3ds.md)
+CONV3DS = int(os.environ.get("FLUXMPI_CONV3DS", "1"))
+
+
+def conv3ds_slabs(rows: int, device) -> int:
+    """Workgroups (= fp32 partial slabs per branch) of the dual kernel: one resident round, one
+    workgroup per compute unit, never more than the 32-pixel tiles there are."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return max(1, min(-(-rows // 32), cus))
+
+
+def conv3ds_ok(x, conv2, conv3, bn, ds_conv, bn_ds) -> bool:
+    """:func:`conv3ds_bn_relu` applies to the block whose input is ``x``: bf16 NHWC, a stride-1
+    conv2 (so a2 has x's pixels), both 1x1 filters 64 -> 256 and contiguous, downsample stride 1,
+    training-mode affine fused BatchNorms (:func:`dual_bn_ok`), and pixels x 64 below 2^31."""
+    w3, wds = conv3.weight, ds_conv.weight
+    return (CONV3DS in (1, 2) and G.ENGINE != 1 and x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and x.shape[1] == 64 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.numel() < 2 ** 31 and tuple(conv2.stride) == (1, 1) and tuple(ds_conv.stride) == (1, 1)
+            and all(wt.dtype == torch.bfloat16 and tuple(wt.shape) == (256, 64, 1, 1) and wt.is_contiguous()
+                    for wt in (w3, wds))
+            and dual_bn_ok(x, 256, bn, bn_ds))
+
+
+def conv3ds_bn_relu(a2, conv3, bn, x, ds_conv, bn_ds, link=None, ours3=True, ours_ds=True):
+    """relu(bn(conv3(a2)) + bn_ds(ds_conv(x))) with the one-pass backward (check :func:`conv3ds_ok`);
+    ``ours3`` / ``ours_ds``: :func:`conv1x1_forward_is_ours` / :func:`ds_forward_is_ours` for the shapes."""
+    mom, nbt = bn_counter(bn)
+    mom2, nbt2 = bn_counter(bn_ds)
+    return _Conv3DsBN.apply(a2, conv3.weight, x, ds_conv.weight, bn.weight, bn.bias, bn_ds.weight, bn_ds.bias,
+                            bn.running_mean, bn.running_var, mom, bn.eps, nbt, bn_ds.running_mean, bn_ds.running_var,
+                            mom2, bn_ds.eps, nbt2, link, bool(ours3), bool(ours_ds), CONV3DS)
 
 
 class _BNReluConv1x1(torch.autograd.Function):
