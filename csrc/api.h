@@ -28,6 +28,18 @@ void mt_sumsq(const std::vector<uintptr_t>& src, const std::vector<int64_t>& num
               float* out, hipStream_t stream);
 
 // ---- fused optimisers ---------------------------------------------------------
+// Stochastic rounding of the bf16 stores of an update (optim_sr.h): given to mt_adam / mt_sgd /
+// mt_rule as a trailing pointer (null: round to nearest, the kernels without it). Only the
+// (bf16, bf16, bf16, no master) and (bf16, bf16, fp32, no master) layouts take it; LARS / LAMB do not.
+struct SrHyper {
+  uint64_t seed;                      // the Philox key
+  uint32_t stream;                    // caller-chosen id below 2^30 (the engine: the bucket index)
+  uint32_t step;                      // host step, read when dev_step is null
+  const uint32_t* dev_step;           // optional device block {uint32 step, 7 unused} (sr_advance)
+  const int64_t* offsets = nullptr;   // per leaf of the call: its first element's index in the stream; null: 0
+  size_t n_offsets = 0;
+};
+
 struct AdamHyper {
   // doubles, as RuleHyper's: fp64 leaves compute with the caller's values; the fp32 kernels round
   // them once, to what the caller's fp32 value was
@@ -49,7 +61,8 @@ struct AdamHyper {
 void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
              const std::vector<uintptr_t>& m, const std::vector<uintptr_t>& v,
              const std::vector<uintptr_t>& master, const std::vector<int64_t>& numel,
-             int p_dtype, int g_dtype, int s_dtype, const AdamHyper& h, hipStream_t stream);
+             int p_dtype, int g_dtype, int s_dtype, const AdamHyper& h, hipStream_t stream,
+             const SrHyper* sr = nullptr);
 
 // dev[1] *= beta1, dev[2] *= beta2 (advance the bias-correction powers on device); not when
 // dev_skip is given and *dev_skip != 0 (a skipped step does not count).
@@ -69,7 +82,7 @@ struct SgdHyper {
 void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
             const std::vector<uintptr_t>& buf, const std::vector<uintptr_t>& master,
             const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype,
-            const SgdHyper& h, hipStream_t stream);
+            const SgdHyper& h, hipStream_t stream, const SrHyper* sr = nullptr);
 
 // The rest of the rule set (optim_rules.hip), one generic kernel with a per-element functor.
 // kLars / kLamb: the layer-wise rules (optim_layerwise.hip), two phases (norm partials, then the
@@ -101,7 +114,17 @@ void mt_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
              const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
              const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,
              const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, const RuleHyper& h,
-             hipStream_t stream);
+             hipStream_t stream, const SrHyper* sr = nullptr);
+
+// ---- stochastic rounding (optim_sr.hip) ------------------------------------------------
+// dst[i] (bf16) = sr(src[i] (fp32), bits of element offsets[leaf] + i of slot 0 of the stream): the
+// update kernels' rounding as a stand-alone multi-tensor cast in their job layout. dev_skip (or
+// null): non-zero calls the launch off before it loads tensor data.
+void mt_stochastic_round(const std::vector<uintptr_t>& dst, const std::vector<uintptr_t>& src,
+                         const std::vector<int64_t>& numel, const SrHyper& sr, const int32_t* dev_skip,
+                         hipStream_t stream);
+// The step block, 8 words: {uint32 step, 7 unused}. One thread: step += 1, unless *dev_skip != 0.
+void sr_advance(void* block, const int32_t* dev_skip, hipStream_t stream);
 
 // ---- gradient clipping: deterministic multi-tensor sum of squares ------------------
 // Two launches per group of leaves, no float atomics (bit-identical from run to run):

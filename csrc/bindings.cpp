@@ -41,15 +41,29 @@ using Ptrs3 = std::array<uintptr_t, 3>;
 // skip predicate of the update kernels, the non-finite flag and the inverse scale of the norm pass)
 // and entries live in `_C_scale`, a second module of this shared object, with `dev_skip` as a
 // trailing keyword argument. One body serves both: it takes dev_skip FIRST, no_skip binds it to
-// null and skip_last moves it behind the other parameters.
-template <typename R, typename... A> auto no_skip(R (*fn)(uintptr_t, A...)) {
-  return [fn](A... a) -> R { return fn(0, a...); };
+// null and skip_last moves it behind the other parameters. In front of dev_skip a body takes the
+// stochastic-rounding arguments (null in `_C` and `_C_scale`); with_sr, for `_C_sr`, builds them from
+// five more trailing keyword arguments.
+template <typename R, typename... A> auto no_skip(R (*fn)(const SrHyper*, uintptr_t, A...)) {
+  return [fn](A... a) -> R { return fn(nullptr, 0, a...); };
 }
-template <typename R, typename... A> auto skip_last(R (*fn)(uintptr_t, A...)) {
-  return [fn](A... a, uintptr_t dev_skip) -> R { return fn(dev_skip, a...); };
+template <typename R, typename... A> auto skip_last(R (*fn)(const SrHyper*, uintptr_t, A...)) {
+  return [fn](A... a, uintptr_t dev_skip) -> R { return fn(nullptr, dev_skip, a...); };
+}
+static SrHyper sr_hyper(uint64_t seed, uint32_t sr_stream, uint32_t step, uintptr_t dev_step,
+                        const std::vector<int64_t>& offsets) {
+  return SrHyper{seed, sr_stream, step, ptr<const uint32_t*>(dev_step), offsets.empty() ? nullptr : offsets.data(),
+                 offsets.size()};
+}
+template <typename R, typename... A> auto with_sr(R (*fn)(const SrHyper*, uintptr_t, A...)) {
+  return [fn](A... a, uintptr_t dev_skip, uint64_t seed, uint32_t sr_stream, uint32_t step, uintptr_t dev_step,
+              const std::vector<int64_t>& offsets) -> R {
+    const SrHyper sr = sr_hyper(seed, sr_stream, step, dev_step, offsets);
+    return fn(&sr, dev_skip, a...);
+  };
 }
 
-static void py_mt_adam(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
+static void py_mt_adam(const SrHyper* sr, uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
                        const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
                        double beta2, double eps, double bc1, double bc2, double weight_decay, float grad_scale,
                        uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale, float clip_delta) {
@@ -58,10 +72,10 @@ static void py_mt_adam(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptr
   h.tscale = ptr<const void*>(tscale);
   h.clip_delta = clip_delta;
   h.dev_skip = ptr<const int32_t*>(dev_skip);
-  mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+  mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
 }
 
-static void py_mt_sgd(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel,
+static void py_mt_sgd(const SrHyper* sr, uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel,
                       int p_dtype, int g_dtype, int s_dtype, double lr, double momentum, double weight_decay,
                       float grad_scale, int nesterov, uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale,
                       uintptr_t tscale, float clip_delta) {
@@ -70,16 +84,16 @@ static void py_mt_sgd(uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master,
   h.tscale = ptr<const void*>(tscale);
   h.clip_delta = clip_delta;
   h.dev_skip = ptr<const int32_t*>(dev_skip);
-  mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+  mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
 }
 
-static void py_mt_rule(uintptr_t dev_skip, int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master,
+static void py_mt_rule(const SrHyper* sr, uintptr_t dev_skip, int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master,
                        const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
                        double beta2, double eps, double bt1, double bt2, double weight_decay, float grad_scale,
                        uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta, uintptr_t stream) {
   RuleHyper h{kind, lr, beta1, beta2, eps, bt1, bt2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
               ptr<const float*>(dev_gscale), ptr<const void*>(tscale), clip_delta, ptr<const int32_t*>(dev_skip)};
-  mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream));
+  mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
 }
 
 #define ADAM_ARGS                                                                                                  \
@@ -132,6 +146,28 @@ PYBIND11_MODULE(_C_ema, m) {
         py::arg("omd"), py::arg("dev_block"), py::arg("dev_skip"), py::arg("stream"));
   m.def("ema_advance", raw(&ema_advance), py::arg("block"), py::arg("decay"), py::arg("warmup"), py::arg("every"),
         py::arg("dev_skip"), py::arg("stream"));
+}
+
+// The stochastic-rounding surface (DDP(stochastic_rounding=...), ops.optim's sr=): a further module,
+// loaded by fluxmpi_amd.ops._ext.sr(). The update entries take the loss-scaling dev_skip and the
+// generator's arguments as trailing keywords; the step comes from `step`, or from the device block
+// `dev_step` when that is given.
+#define SR_ARGS                                                                                        \
+  py::arg("seed"), py::arg("sr_stream"), py::arg("step"), py::arg("dev_step"), py::arg("offsets")
+PYBIND11_MODULE(_C_sr, m) {
+  m.doc() = "fluxmpi_amd native library: stochastic rounding of the fused optimisers' bf16 stores";
+  m.def("mt_adam", with_sr(&py_mt_adam), ADAM_ARGS, NO_SKIP, SR_ARGS);
+  m.def("mt_sgd", with_sr(&py_mt_sgd), SGD_ARGS, NO_SKIP, SR_ARGS);
+  m.def("mt_rule", with_sr(&py_mt_rule), RULE_ARGS, NO_SKIP, SR_ARGS);
+  m.def(
+      "mt_stochastic_round",
+      [](Ptrs dst, Ptrs src, const std::vector<int64_t>& numel, uintptr_t dev_skip, uintptr_t stream, uint64_t seed,
+         uint32_t sr_stream, uint32_t step, uintptr_t dev_step, const std::vector<int64_t>& offsets) {
+        mt_stochastic_round(dst, src, numel, sr_hyper(seed, sr_stream, step, dev_step, offsets),
+                            ptr<const int32_t*>(dev_skip), ptr<hipStream_t>(stream));
+      },
+      py::arg("dst"), py::arg("src"), py::arg("numel"), py::arg("dev_skip"), py::arg("stream"), SR_ARGS);
+  m.def("sr_advance", raw(&sr_advance), py::arg("block"), py::arg("dev_skip"), py::arg("stream"));
 }
 
 // The one-pass backward of the stage-1 downsample block (conv3ds_bwd.hip): a fourth module, loaded by

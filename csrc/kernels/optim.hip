@@ -41,6 +41,7 @@
 
 #include "../api.h"
 #include "optim_common.h"
+#include "optim_sr.h"
 
 namespace fluxmpi {
 namespace {
@@ -49,7 +50,9 @@ template <typename P, typename G, typename S, bool MASTER>
 struct AdamElem {
   using C = typename Comp<P>::type;
   C lr, b1, b2, eps, bc1, bc2, wd, gs, ts, delta;
-  __device__ __forceinline__ void operator()(P& p, G g_in, S& m_io, S& v_io, float& w) const {
+  // rnd: the stores' rounding policy (optim_sr.h), slot 0 the parameter, 1 / 2 the moments
+  template <typename Rnd>
+  __device__ __forceinline__ void operator()(P& p, G g_in, S& m_io, S& v_io, float& w, const Rnd& rnd) const {
 #pragma clang fp contract(off)  // as written: see the note above the rule functors of optim_rules.hip
     const C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     const C m = b1 * static_cast<C>(m_io) + (C(1) - b1) * g;
@@ -58,19 +61,23 @@ struct AdamElem {
     C dx = m / bc1 / (sqrt(v / bc2) + eps) * lr;
     if (wd != C(0)) dx += wd * x;
     x -= dx;
-    m_io = static_cast<S>(m);
-    v_io = static_cast<S>(v);
+    m_io = rnd.template cast<S>(m, 1);
+    v_io = rnd.template cast<S>(v, 2);
     if (MASTER) w = static_cast<float>(x);
-    p = static_cast<P>(x);
+    p = rnd.template cast<P>(x, 0);
   }
 };
 
-template <typename P, typename G, typename S, bool MASTER, bool SKIP>
-__global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper h) {
+// Sr: empty (round to nearest: the kernel and its arguments are what they were without the pack), or
+// one SrArgs, a third kernel parameter that only the stochastic-rounding instantiations take.
+template <typename P, typename G, typename S, bool MASTER, bool SKIP, typename... Sr>
+__global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper h, Sr... sr) {
   using C = typename Comp<P>::type;
   if (step_skipped<SKIP>(h.dev_skip)) return;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
+  const SrCtx<sizeof...(Sr) != 0> rc(t, sr...);
+  constexpr int kSrStates = std::is_same_v<S, bf16> ? 2 : 0;
 
   AdamElem<P, G, S, MASTER> op;
   C lr = static_cast<C>(h.lr), bc1 = static_cast<C>(h.bc1), bc2 = static_cast<C>(h.bc2);
@@ -92,7 +99,8 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
   S* __restrict__ v = reinterpret_cast<S*>(a.s2[t]);
   float* __restrict__ w = reinterpret_cast<float*>(a.w[t]);
   const int tid = threadIdx.x;
-  const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!MASTER || aligned16(w));
+  const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!MASTER || aligned16(w)) &&
+                   rc.vec_ok();
   int64_t scalar_from = ch.base;
   if (vec) {
     const int64_t nvec = (ch.end - ch.base) / kVec;
@@ -106,8 +114,9 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
         load8(m + off, mv);
         load8(v + off, vv);
         if (MASTER) load8(w + off, wv); else load8(p + off, pv);
+        const auto rv = rc.vec(off, kSrStates);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], mv[j], vv[j], wv[j]);
+        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], mv[j], vv[j], wv[j], rv.at(j));
         store8(m + off, mv);
         store8(v + off, vv);
         if (MASTER) store8(w + off, wv);
@@ -120,19 +129,21 @@ __global__ __launch_bounds__(kThreads) void mt_adam_kernel(OptArgs a, AdamHyper 
     P pv = p[i];
     S mv = m[i], vv = v[i];
     float wv = MASTER ? w[i] : 0.f;
-    op(pv, g[i], mv, vv, wv);
+    op(pv, g[i], mv, vv, wv, rc.one(i, kSrStates));
     m[i] = mv; v[i] = vv;
     if (MASTER) w[i] = wv;
     p[i] = pv;
   }
 }
 
+
 template <typename P, typename G, typename S, bool MASTER>
 struct SgdElem {
   using C = typename Comp<P>::type;
   C lr, rho, wd, gs, ts, delta;
   int mode;  // 0 descent, 1 momentum, 2 nesterov
-  __device__ __forceinline__ void operator()(P& p, G g_in, S& buf, float& w) const {
+  template <typename Rnd>
+  __device__ __forceinline__ void operator()(P& p, G g_in, S& buf, float& w, const Rnd& rnd) const {
 #pragma clang fp contract(off)
     C x = MASTER ? static_cast<C>(w) : static_cast<C>(p);
     C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
@@ -142,25 +153,26 @@ struct SgdElem {
       dx = g * lr;
     } else if (mode == 1) {
       const C vel = rho * static_cast<C>(buf) + lr * g;
-      buf = static_cast<S>(vel);
+      buf = rnd.template cast<S>(vel, 1);
       dx = vel;
     } else {
       const C vel0 = static_cast<C>(buf);
       dx = -(rho * rho) * vel0 + (C(1) + rho) * lr * g;
-      buf = static_cast<S>(rho * vel0 - lr * g);
+      buf = rnd.template cast<S>(rho * vel0 - lr * g, 1);
     }
     x -= dx;
     if (MASTER) w = static_cast<float>(x);
-    p = static_cast<P>(x);
+    p = rnd.template cast<P>(x, 0);
   }
 };
 
-template <typename P, typename G, typename S, bool MASTER, bool SKIP>
-__global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h) {
+template <typename P, typename G, typename S, bool MASTER, bool SKIP, typename... Sr>  // Sr: as in mt_adam_kernel
+__global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h, Sr... sr) {
   using C = typename Comp<P>::type;
   if (step_skipped<SKIP>(h.dev_skip)) return;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
+  const SrCtx<sizeof...(Sr) != 0> rc(t, sr...);
   SgdElem<P, G, S, MASTER> op;
   op.lr = h.dev_lr ? static_cast<C>(*h.dev_lr) : static_cast<C>(h.lr);
   op.rho = static_cast<C>(h.momentum); op.wd = static_cast<C>(h.weight_decay);
@@ -174,7 +186,9 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
   float* __restrict__ w = reinterpret_cast<float*>(a.w[t]);
   const bool has_buf = op.mode != 0;
   const int tid = threadIdx.x;
-  const bool vec = aligned16(p) && aligned16(g) && (!has_buf || aligned16(buf)) && (!MASTER || aligned16(w));
+  const bool vec = aligned16(p) && aligned16(g) && (!has_buf || aligned16(buf)) && (!MASTER || aligned16(w)) &&
+                   rc.vec_ok();
+  const int sr_states = std::is_same_v<S, bf16> && has_buf ? 1 : 0;
   int64_t scalar_from = ch.base;
   if (vec) {
     const int64_t nvec = (ch.end - ch.base) / kVec;
@@ -187,8 +201,9 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
         load8(g + off, gv);
         if (has_buf) load8(buf + off, bv);
         if (MASTER) load8(w + off, wv); else load8(p + off, pv);
+        const auto rv = rc.vec(off, sr_states);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], bv[j], wv[j]);
+        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], bv[j], wv[j], rv.at(j));
         if (has_buf) store8(buf + off, bv);
         if (MASTER) store8(w + off, wv);
         store8(p + off, pv);
@@ -200,12 +215,13 @@ __global__ __launch_bounds__(kThreads) void mt_sgd_kernel(OptArgs a, SgdHyper h)
     P pv = p[i];
     S bv = has_buf ? buf[i] : S(0);
     float wv = MASTER ? w[i] : 0.f;
-    op(pv, g[i], bv, wv);
+    op(pv, g[i], bv, wv, rc.one(i, sr_states));
     if (has_buf) buf[i] = bv;
     if (MASTER) w[i] = wv;
     p[i] = pv;
   }
 }
+
 
 // ---- deterministic multi-tensor sum of squares + clip scales -------------------------------
 // launch 1: the job layout of the update kernels; workgroup b writes partials[pbase + b].
@@ -371,10 +387,22 @@ __global__ void loss_scale_update_kernel(int32_t* __restrict__ blk, float growth
 void mt_adam(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
              const std::vector<uintptr_t>& m, const std::vector<uintptr_t>& v,
              const std::vector<uintptr_t>& master, const std::vector<int64_t>& numel,
-             int p_dtype, int g_dtype, int s_dtype, const AdamHyper& h, hipStream_t stream) {
+             int p_dtype, int g_dtype, int s_dtype, const AdamHyper& h, hipStream_t stream, const SrHyper* sr) {
   const bool has_master = !master.empty();
   if (m.size() != numel.size() || v.size() != numel.size()) throw std::runtime_error("mt_adam: need m and v");
+  if (sr != nullptr) sr_check_combo(*sr, numel.size(), p_dtype, g_dtype, s_dtype, has_master, "mt_adam");
   for_each_group(param, grad, m, v, {}, master, numel, [&](const OptArgs& a, int blocks) {
+    if (sr != nullptr) {
+      const SrArgs sa = sr_args_for(*sr, a);
+      dispatch_bool(s_dtype == kBF16, [&](auto sb) {
+        dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+          using S = std::conditional_t<decltype(sb)::value, bf16, float>;
+          mt_adam_kernel<bf16, bf16, S, false, decltype(skip)::value, SrArgs><<<blocks, kThreads, 0, stream>>>(a, h, sa);
+        });
+      });
+      FLUXMPI_HIP_CHECK(hipGetLastError());
+      return;
+    }
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_adam", [&](auto p, auto g, auto s, auto master) {
       dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
         mt_adam_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
@@ -393,11 +421,23 @@ void adam_advance(float* dev, float beta1, float beta2, hipStream_t stream, cons
 void mt_sgd(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
             const std::vector<uintptr_t>& buf, const std::vector<uintptr_t>& master,
             const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype,
-            const SgdHyper& h, hipStream_t stream) {
+            const SgdHyper& h, hipStream_t stream, const SrHyper* sr) {
   const bool has_master = !master.empty();
   if (h.momentum != 0. && buf.size() != numel.size())
     throw std::runtime_error("mt_sgd: momentum needs buffers");
+  if (sr != nullptr) sr_check_combo(*sr, numel.size(), p_dtype, g_dtype, s_dtype, has_master, "mt_sgd");
   for_each_group(param, grad, buf, {}, {}, master, numel, [&](const OptArgs& a, int blocks) {
+    if (sr != nullptr) {
+      const SrArgs sa = sr_args_for(*sr, a);
+      dispatch_bool(s_dtype == kBF16, [&](auto sb) {
+        dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+          using S = std::conditional_t<decltype(sb)::value, bf16, float>;
+          mt_sgd_kernel<bf16, bf16, S, false, decltype(skip)::value, SrArgs><<<blocks, kThreads, 0, stream>>>(a, h, sa);
+        });
+      });
+      FLUXMPI_HIP_CHECK(hipGetLastError());
+      return;
+    }
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_sgd", [&](auto p, auto g, auto s, auto master) {
       dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
         mt_sgd_kernel<typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,

@@ -31,6 +31,7 @@
 
 #include "../api.h"
 #include "optim_common.h"
+#include "optim_sr.h"
 
 namespace fluxmpi {
 namespace {
@@ -166,7 +167,10 @@ struct RuleElem {
   using C = typename Comp<P>::type;
   R rule;
   C wd, gs, ts, delta;
-  __device__ __forceinline__ void operator()(P& p, G g_in, S& a_io, S& b_io, S& c_io, float& w) const {
+  // rnd: the stores' rounding policy (optim_sr.h), slot 0 the parameter, 1..3 the states
+  template <typename Rnd>
+  __device__ __forceinline__ void operator()(P& p, G g_in, S& a_io, S& b_io, S& c_io, float& w,
+                                             const Rnd& rnd) const {
 #pragma clang fp contract(off)
     const C g = clip_grad(static_cast<C>(g_in) * gs * ts, delta);
     C a = static_cast<C>(a_io);
@@ -176,22 +180,27 @@ struct RuleElem {
     C dx = rule(g, a, b, c);
     if (wd != C(0)) dx += wd * x;
     x -= dx;
-    a_io = static_cast<S>(a);
-    if (R::kStates > 1) b_io = static_cast<S>(b);
-    if (R::kStates > 2) c_io = static_cast<S>(c);
+    a_io = rnd.template cast<S>(a, 1);
+    if (R::kStates > 1) b_io = rnd.template cast<S>(b, 2);
+    if (R::kStates > 2) c_io = rnd.template cast<S>(c, 3);
     if (MASTER) w = static_cast<float>(x);
-    p = static_cast<P>(x);
+    p = rnd.template cast<P>(x, 0);
   }
 };
 
-template <template <typename> class RuleT, typename P, typename G, typename S, bool MASTER, bool SKIP>
-__global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper h) {
+// Sr: empty (round to nearest: the kernel and its arguments are what they were without the pack), or
+// one SrArgs (optim_sr.h), a third kernel parameter that only the stochastic-rounding instantiations take.
+template <template <typename> class RuleT, typename P, typename G, typename S, bool MASTER, bool SKIP,
+          typename... Sr>
+__global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper h, Sr... sr) {
   using C = typename Comp<P>::type;
   if (step_skipped<SKIP>(h.dev_skip)) return;
   using R = RuleT<C>;
   constexpr int NS = R::kStates;
   const Chunk ch = chunk_of(a);
   const int t = ch.t;
+  const SrCtx<sizeof...(Sr) != 0> rc(t, sr...);
+  constexpr int kSrStates = std::is_same_v<S, bf16> ? NS : 0;
 
   RuleElem<R, P, G, S, MASTER> op;
   C lr = static_cast<C>(h.lr), bt1 = static_cast<C>(h.bt1), bt2 = static_cast<C>(h.bt2);
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
   float* __restrict__ w = reinterpret_cast<float*>(a.w[t]);
   const int tid = threadIdx.x;
   const bool vec = aligned16(p) && aligned16(g) && aligned16(s1) && (NS < 2 || aligned16(s2)) &&
-                   (NS < 3 || aligned16(s3)) && (!MASTER || aligned16(w));
+                   (NS < 3 || aligned16(s3)) && (!MASTER || aligned16(w)) && rc.vec_ok();
   int64_t scalar_from = ch.base;
   if (vec) {
     const int64_t nvec = (ch.end - ch.base) / kVec;
@@ -233,8 +242,9 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
         if (NS > 1) load8(s2 + off, bv);
         if (NS > 2) load8(s3 + off, cv);
         if (MASTER) load8(w + off, wv); else load8(p + off, pv);
+        const auto rv = rc.vec(off, kSrStates);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], av[j], bv[j], cv[j], wv[j]);
+        for (int j = 0; j < kVec; ++j) op(pv[j], gv[j], av[j], bv[j], cv[j], wv[j], rv.at(j));
         store8(s1 + off, av);
         if (NS > 1) store8(s2 + off, bv);
         if (NS > 2) store8(s3 + off, cv);
@@ -250,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
     S bv = NS > 1 ? s2[i] : S(0);
     S cv = NS > 2 ? s3[i] : S(0);
     float wv = MASTER ? w[i] : 0.f;
-    op(pv, g[i], av, bv, cv, wv);
+    op(pv, g[i], av, bv, cv, wv, rc.one(i, kSrStates));
     s1[i] = av;
     if (NS > 1) s2[i] = bv;
     if (NS > 2) s3[i] = cv;
@@ -259,12 +269,13 @@ __global__ __launch_bounds__(kThreads) void mt_rule_kernel(OptArgs a, RuleHyper 
   }
 }
 
+
 template <template <typename> class RuleT>
 void launch_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& grad,
                  const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
                  const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,
                  const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, const RuleHyper& h,
-                 hipStream_t stream) {
+                 hipStream_t stream, const SrHyper* sr) {
   constexpr int NS = RuleT<float>::kStates;
   const size_t N = numel.size();
   // every state tensor the kernel dereferences must be there: a missing list would be a null pointer
@@ -272,7 +283,19 @@ void launch_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_
     throw std::runtime_error("mt_rule: rule " + std::to_string(h.kind) + " needs " + std::to_string(NS) +
                              " state list(s) as long as the parameter list");
   const bool has_master = !master.empty();
+  if (sr != nullptr) sr_check_combo(*sr, N, p_dtype, g_dtype, s_dtype, has_master, "mt_rule");
   for_each_group(param, grad, s1, s2, s3, master, numel, [&](const OptArgs& a, int blocks) {
+    if (sr != nullptr) {
+      const SrArgs sa = sr_args_for(*sr, a);
+      dispatch_bool(s_dtype == kBF16, [&](auto sb) {
+        dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
+          using S = std::conditional_t<decltype(sb)::value, bf16, float>;
+          mt_rule_kernel<RuleT, bf16, bf16, S, false, decltype(skip)::value, SrArgs><<<blocks, kThreads, 0, stream>>>(a, h, sa);
+        });
+      });
+      FLUXMPI_HIP_CHECK(hipGetLastError());
+      return;
+    }
     dispatch_opt_combo(p_dtype, g_dtype, s_dtype, has_master, "mt_rule", [&](auto p, auto g, auto s, auto master) {
       dispatch_bool(h.dev_skip != nullptr, [&](auto skip) {
         mt_rule_kernel<RuleT, typename decltype(p)::type, typename decltype(g)::type, typename decltype(s)::type,
@@ -289,9 +312,11 @@ void mt_rule(const std::vector<uintptr_t>& param, const std::vector<uintptr_t>& 
              const std::vector<uintptr_t>& s1, const std::vector<uintptr_t>& s2,
              const std::vector<uintptr_t>& s3, const std::vector<uintptr_t>& master,
              const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, const RuleHyper& h,
-             hipStream_t stream) {
+             hipStream_t stream, const SrHyper* sr) {
+  if (sr != nullptr && (h.kind == kLars || h.kind == kLamb))
+    throw std::runtime_error("mt_rule: LARS / LAMB have no stochastic-rounding kernels");
 #define RULE(K, T) \
-  case K: launch_rule<T>(param, grad, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, stream); break;
+  case K: launch_rule<T>(param, grad, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, stream, sr); break;
   switch (h.kind) {
     RULE(kRmsProp, RmsPropRule)
     RULE(kAdaGrad, AdaGradRule)

@@ -109,6 +109,12 @@ def ema():
     return _extra("_C_ema", "the weight-EMA entries")
 
 
+def sr():
+    """The ``_C_sr`` module: the fused optimisers' entries with the stochastic-rounding arguments,
+    ``mt_stochastic_round`` and ``sr_advance`` (``csrc/kernels/optim_sr.h``, ``optim_sr.hip``)."""
+    return _extra("_C_sr", "the stochastic-rounding entries")
+
+
 def c3ds():
     """The ``_C_c3ds`` module: ``conv3ds_bwd`` (the one-pass backward around the dual BatchNorm of a
     stage-1 downsample block, ``csrc/kernels/conv3ds_bwd.hip``)."""

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _ext
+from . import _ext, philox
 from .multi_tensor import DTYPE_CODE
 
 _SUPPORTED = {
@@ -71,11 +71,14 @@ def _ptr(t: torch.Tensor | None) -> int:
     return t.data_ptr() if t is not None else 0
 
 
-def _call(C, name: str, *args, _scaling: dict, **kw):
+def _call(C, name: str, *args, _scaling: dict, _sr: dict | None = None, **kw):
     """Call the native entry ``name``: ``_C``'s, or, when one of the loss-scaling arguments
     ``_scaling`` (device addresses; 0: not given) is there, ``_C_scale``'s with those arguments.
     ``_C`` keeps its recorded surface; the loss-scaling surface is a second module of the same
-    library (``ops._ext.scale``)."""
+    library (``ops._ext.scale``). With ``_sr`` (the generator's arguments, :meth:`SR._native`):
+    ``_C_sr``'s entry, which takes both."""
+    if _sr is not None:
+        return getattr(_ext.sr(), name)(*args, **kw, **_scaling, **_sr)
     given = {k: v for k, v in _scaling.items() if v}
     if given:
         return getattr(_ext.scale(), name)(*args, **kw, **given)
@@ -94,6 +97,154 @@ def _skip_ptr(dev_skip) -> int:
 def _skipped(dev_skip) -> bool:
     """The reference path's reading of the skip predicate (a host read: CPU tensors)."""
     return bool(_skip_ptr(dev_skip)) and int(dev_skip.reshape(-1)[0]) != 0
+
+
+# ---- stochastic rounding of the bf16 stores (csrc/kernels/optim_sr.h, ops/philox.py) --------------
+SR_WORDS = 8  # the step block: {uint32 step, 7 unused}
+
+
+def sr_block(device, step: int = 0) -> torch.Tensor:
+    """A fresh step block on ``device`` (8 int32 words, the first the uint32 step counter's bits)."""
+    philox.check_ids(0, 0, 0, step)
+    blk = torch.zeros(SR_WORDS, dtype=torch.int32)
+    blk[0] = int(step) - (1 << 32) if int(step) >= 1 << 31 else int(step)
+    return blk.to(device)
+
+
+def _sr_block_ok(block, what: str) -> None:
+    if block.dtype != torch.int32 or block.numel() < SR_WORDS or not block.is_contiguous():
+        raise TypeError(f"{what}: the step block is a contiguous int32 tensor of {SR_WORDS} entries (sr_block)")
+
+
+class SR:
+    """The stochastic-rounding argument ``sr=`` of :func:`adam_`, :func:`sgd_`, :func:`rule_` and
+    :func:`stochastic_round_`: every bf16 store of the call (the parameter, slot 0, and bf16 state
+    tensors, slots 1..3) becomes ``sr(x, r)`` of ``ops.philox`` with Philox4x32-10 bits.
+
+    ``seed``: the key, below 2^64. ``stream``: a caller-chosen id below 2^30 (the engine: the bucket
+    index). ``step``: a uint32 from the host, or ``dev_block`` (:func:`sr_block`, advanced by
+    :func:`sr_advance_`), whose device value wins: HIP-graph replay. ``offsets``: per leaf of the call
+    the index of its first element in the random stream (default 0 for each); leaves of one flat
+    buffer given their offsets in it round like one launch over the buffer."""
+
+    def __init__(self, seed: int, stream: int = 0, step: int = 0, dev_block: torch.Tensor | None = None,
+                 offsets=None):
+        philox.check_ids(seed, stream, 0, step)
+        if dev_block is not None:
+            _sr_block_ok(dev_block, "SR")
+        self.seed, self.stream, self.step, self.dev_block = int(seed), int(stream), int(step), dev_block
+        self.offsets = None if offsets is None else [int(o) for o in offsets]
+        if self.offsets is not None and any(o < 0 for o in self.offsets):
+            raise ValueError("SR: offsets are not negative")
+
+    def _offsets(self, n: int) -> list:
+        if self.offsets is None:
+            return [0] * n
+        if len(self.offsets) != n:
+            raise ValueError(f"SR: {len(self.offsets)} offsets for {n} leaves")
+        return self.offsets
+
+    def _offset(self, i: int) -> int:
+        return 0 if self.offsets is None else self.offsets[i]
+
+    def _native(self, idx, n: int) -> dict:
+        off = self._offsets(n)
+        return {"seed": self.seed, "sr_stream": self.stream, "step": self.step, "dev_step": _ptr(self.dev_block),
+                "offsets": [off[i] for i in idx]}
+
+    def _host_step(self) -> int:
+        """The step as the reference path reads it (a host read of the block: CPU tensors)."""
+        if self.dev_block is not None:
+            return int(self.dev_block.reshape(-1)[0]) & 0xFFFFFFFF
+        return self.step
+
+
+def _sr_check(name: str, sr, params, grads, states, masters) -> None:
+    """``sr=`` is for bf16 parameters and gradients without masters, states bf16 or fp32."""
+    if sr is None:
+        return
+    if not isinstance(sr, SR):
+        raise TypeError(f"fused {name}: sr is an ops.optim.SR, got {type(sr).__name__}")
+    if masters is not None:
+        raise ValueError(f"fused {name}: stochastic rounding replaces the fp32 masters: pass masters=None")
+    for i, p in enumerate(params):
+        dts = [p.dtype, grads[i].dtype]
+        if any(d != torch.bfloat16 for d in dts) or any(s[i].dtype not in (torch.bfloat16, torch.float32)
+                                                        for s in states):
+            raise TypeError(f"fused {name}: leaf {i}: stochastic rounding takes bf16 parameters and gradients with "
+                            f"bf16 or fp32 states, got param={p.dtype} grad={grads[i].dtype}")
+    sr._offsets(len(params))
+
+
+def _flat(t: torch.Tensor) -> torch.Tensor:
+    """A dense tensor's elements in memory order."""
+    return t.reshape(-1) if t.is_contiguous() else t.as_strided((t.numel(),), (1,))
+
+
+def _store(dst: torch.Tensor, val: torch.Tensor, sr, slot: int, i: int) -> None:
+    """The reference path's store ``dst <- val``: a cast, or with ``sr`` and a bf16 ``dst`` the
+    stochastic rounding of slot ``slot`` of leaf ``i`` of the call."""
+    if sr is None or dst.dtype != torch.bfloat16 or val.dtype != torch.float32:
+        dst.copy_(val)
+        return
+    tmp = torch.empty_like(dst, dtype=torch.float32)  # dst's strides: memory order is the kernels' element order
+    tmp.copy_(val)
+    _flat(dst).copy_(philox.sr_reference(_flat(tmp), sr.seed, sr.stream, slot, sr._host_step(), sr._offset(i)))
+
+
+def sr_advance_(block: torch.Tensor, *, dev_skip: torch.Tensor | None = None) -> None:
+    """``step += 1`` on the step block (:func:`sr_block`), one thread on the device, after a step's
+    launches; not when ``dev_skip`` is non-zero: a skipped step does not count. Graph-capturable."""
+    _sr_block_ok(block, "sr_advance_")
+    if block.is_cuda:
+        _ext.sr().sr_advance(block.data_ptr(), _skip_ptr(dev_skip), torch.cuda.current_stream(block.device).cuda_stream)
+    elif not _skipped(dev_skip):
+        nxt = ((int(block[0]) & 0xFFFFFFFF) + 1) & 0xFFFFFFFF
+        block[0] = nxt - (1 << 32) if nxt >= 1 << 31 else nxt
+
+
+def _sr_cast_check(dsts, srcs, sr) -> None:
+    if not isinstance(sr, SR):
+        raise TypeError(f"stochastic_round_: sr is an ops.optim.SR, got {type(sr).__name__}")
+    if len(dsts) != len(srcs):
+        raise ValueError(f"stochastic_round_: {len(dsts)} destinations for {len(srcs)} sources")
+    for i, (d, x) in enumerate(zip(dsts, srcs)):
+        if d.dtype != torch.bfloat16 or x.dtype != torch.float32:
+            raise TypeError(f"stochastic_round_: leaf {i}: rounds fp32 to bf16, got {x.dtype} -> {d.dtype}")
+        if d.numel() != x.numel() or d.device != x.device or (d.numel() and not _one_memory_order(d, x)):
+            raise TypeError(f"stochastic_round_: leaf {i}: destination and source must be dense with one size, "
+                            "device and memory order")
+    sr._offsets(len(dsts))
+
+
+def stochastic_round_(dsts, srcs, sr: "SR", *, dev_skip: torch.Tensor | None = None) -> None:
+    """``dsts[i] (bf16) <- sr(srcs[i] (fp32))`` over lists of tensors with the bits of slot 0 of
+    ``sr``: the update kernels' rounding as a stand-alone multi-tensor cast (``optim_sr.hip``), one
+    launch per 24 leaves. ``dev_skip``: as in :func:`adam_`. Graph-capturable."""
+    dsts, srcs = list(dsts), list(srcs)
+    _sr_cast_check(dsts, srcs, sr)
+    if not dsts:
+        return
+    if not dsts[0].is_cuda:
+        stochastic_round_reference_(dsts, srcs, sr, dev_skip=dev_skip)
+        return
+    _ext.sr().mt_stochastic_round([d.data_ptr() for d in dsts], [x.data_ptr() for x in srcs],
+                                  [d.numel() for d in dsts], _skip_ptr(dev_skip),
+                                  torch.cuda.current_stream(dsts[0].device).cuda_stream,
+                                  **sr._native(range(len(dsts)), len(dsts)))
+
+
+def stochastic_round_reference_(dsts, srcs, sr: "SR", *, dev_skip: torch.Tensor | None = None) -> None:
+    """Reference of :func:`stochastic_round_` through ``ops.philox.sr_reference``: the CPU path and
+    the kernel's oracle."""
+    dsts, srcs = list(dsts), list(srcs)
+    _sr_cast_check(dsts, srcs, sr)
+    if _skipped(dev_skip):
+        return
+    with torch.no_grad():
+        for i, (d, x) in enumerate(zip(dsts, srcs)):
+            if d.numel():
+                _store(d, x, sr, 0, i)
 
 
 def _dtype_groups(name: str, params, grads, states, masters, slots: int) -> list:
@@ -129,7 +280,7 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
           bc1: float, bc2: float, weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
           tscale: torch.Tensor | None = None, clip_delta: float = 0.0,
-          dev_skip: torch.Tensor | None = None) -> None:
+          dev_skip: torch.Tensor | None = None, sr: "SR | None" = None) -> None:
     """In-place fused Adam over lists of tensors.
 
     ``bc1``/``bc2`` are ``1 - beta^t`` (Optimisers.jl keeps ``beta^t`` in the
@@ -143,7 +294,11 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
 
     ``dev_skip``: one int32 on the device (loss scaling's non-finite flag, :func:`check_finite_`).
     When it is non-zero the launch reads and writes no tensor: the step is called off.
+
+    ``sr`` (:class:`SR`): the bf16 stores — the parameter and bf16 moments — round stochastically
+    (bf16 parameters and gradients without masters; else ``TypeError`` / ``ValueError``).
     """
+    _sr_check("Adam", sr, params, grads, [exp_avgs, exp_avg_sqs], masters)
     if not params:
         return
     if params[0].is_cuda:
@@ -153,7 +308,7 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
             _call(C, "mt_adam", *head, float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
                   float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale), stream,
                   tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta),
-                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)}, _sr=sr and sr._native(idx, len(params)))
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -163,7 +318,7 @@ def adam_(params, grads, exp_avgs, exp_avg_sqs, *, lr: float, beta1: float, beta
         grad_scale = grad_scale * float(dev_gscale)
     adam_reference_(params, grads, exp_avgs, exp_avg_sqs, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bc1=bc1,
                     bc2=bc2, weight_decay=weight_decay, grad_scale=grad_scale, masters=masters, tscale=tscale,
-                    clip_delta=clip_delta, dev_skip=dev_skip)
+                    clip_delta=clip_delta, dev_skip=dev_skip, sr=sr)
 
 
 def _clip_reference(g, i, tscale, clip_delta):
@@ -175,8 +330,11 @@ def _clip_reference(g, i, tscale, clip_delta):
 
 
 def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps, bc1, bc2,
-                    weight_decay=0.0, grad_scale=1.0, masters=None, tscale=None, clip_delta=0.0, dev_skip=None):
-    """PyTorch reference of the fused kernel (compute in fp32, or fp64 for fp64 params)."""
+                    weight_decay=0.0, grad_scale=1.0, masters=None, tscale=None, clip_delta=0.0, dev_skip=None,
+                    sr=None):
+    """PyTorch reference of the fused kernel (compute in fp32, or fp64 for fp64 params); with ``sr``
+    the bf16 stores go through ``ops.philox.sr_reference``."""
+    _sr_check("Adam", sr, params, grads, [exp_avgs, exp_avg_sqs], masters)
     if _skipped(dev_skip):
         return
     for i, p in enumerate(params):
@@ -191,11 +349,11 @@ def adam_reference_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, e
         if weight_decay != 0.0:
             dx = dx + wd * x
         x = x - dx
-        exp_avgs[i].copy_(m)
-        exp_avg_sqs[i].copy_(v)
+        _store(exp_avgs[i], m, sr, 1, i)
+        _store(exp_avg_sqs[i], v, sr, 2, i)
         if masters is not None:
             masters[i].copy_(x)
-        p.copy_(x)
+        _store(p, x, sr, 0, i)
 
 
 def adam_advance_(dev_hyper: torch.Tensor, beta1: float, beta2: float, *,
@@ -215,10 +373,11 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
          weight_decay: float = 0.0, grad_scale: float = 1.0, masters=None,
          dev_lr: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
          tscale: torch.Tensor | None = None, clip_delta: float = 0.0,
-         dev_skip: torch.Tensor | None = None) -> None:
+         dev_skip: torch.Tensor | None = None, sr: "SR | None" = None) -> None:
     """Fused Descent / Momentum / Nesterov (Optimisers.jl semantics); ``dev_gscale``, ``tscale``,
-    ``clip_delta`` and ``dev_skip`` as in :func:`adam_` (the clipped gradient is formed before
+    ``clip_delta``, ``dev_skip`` and ``sr`` as in :func:`adam_` (the clipped gradient is formed before
     weight decay)."""
+    _sr_check("SGD", sr, params, grads, [bufs] if momentum != 0.0 else [], masters)
     if not params:
         return
     if params[0].is_cuda:
@@ -230,7 +389,7 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
                   int(bool(nesterov)),
                   _ptr(dev_lr), stream, dev_gscale=_ptr(dev_gscale),
                   tscale=_tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), clip_delta=float(clip_delta),
-                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)}, _sr=sr and sr._native(idx, len(params)))
         return
     if dev_lr is not None:
         lr = float(dev_lr.reshape(-1)[0])
@@ -238,11 +397,13 @@ def sgd_(params, grads, bufs, *, lr: float, momentum: float = 0.0, nesterov: boo
     if dev_gscale is not None:
         grad_scale = grad_scale * float(dev_gscale)
     sgd_reference_(params, grads, bufs, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay,
-                   grad_scale=grad_scale, masters=masters, tscale=tscale, clip_delta=clip_delta, dev_skip=dev_skip)
+                   grad_scale=grad_scale, masters=masters, tscale=tscale, clip_delta=clip_delta, dev_skip=dev_skip,
+                   sr=sr)
 
 
 def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, weight_decay=0.0, grad_scale=1.0,
-                   masters=None, tscale=None, clip_delta=0.0, dev_skip=None):
+                   masters=None, tscale=None, clip_delta=0.0, dev_skip=None, sr=None):
+    _sr_check("SGD", sr, params, grads, [bufs] if momentum != 0.0 else [], masters)
     if _skipped(dev_skip):
         return
     for i, p in enumerate(params):
@@ -256,16 +417,16 @@ def sgd_reference_(params, grads, bufs, *, lr, momentum=0.0, nesterov=False, wei
             dx = g * lr_
         elif not nesterov:
             vel = rho * bufs[i].to(ct) + lr_ * g
-            bufs[i].copy_(vel)
+            _store(bufs[i], vel, sr, 1, i)
             dx = vel
         else:
             vel0 = bufs[i].to(ct)
             dx = -(rho * rho) * vel0 + (1 + rho) * lr_ * g
-            bufs[i].copy_(rho * vel0 - lr_ * g)
+            _store(bufs[i], rho * vel0 - lr_ * g, sr, 1, i)
         x = x - dx
         if masters is not None:
             masters[i].copy_(x)
-        p.copy_(x)
+        _store(p, x, sr, 0, i)
 
 
 # kind -> (code of the kernel's rule switch, state tensors per leaf, reads beta^t)
@@ -292,7 +453,7 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
           rho: float | None = None, eps: float = 0.0, bt1: float = 0.0, bt2: float = 0.0, masters=None,
           dev_hyper: torch.Tensor | None = None, dev_gscale: torch.Tensor | None = None,
           tscale: torch.Tensor | None = None, clip_delta: float = 0.0, weight_decay: float = 0.0,
-          grad_scale: float = 1.0, dev_skip: torch.Tensor | None = None) -> None:
+          grad_scale: float = 1.0, dev_skip: torch.Tensor | None = None, sr: "SR | None" = None) -> None:
     """In-place fused step of one of :data:`RULES` over lists of tensors (``optim_rules.hip``).
 
     ``states``: one list of tensors per state slot of the rule, in the order of its Optimisers.jl
@@ -302,8 +463,8 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
     Optimisers.jl keeps them in the state and starts them at ``beta``); ``dev_hyper`` (fp32
     ``[lr, beta1^t, beta2^t]``, or ``[lr]`` for the rules without ``beta^t``) overrides them for
     HIP-graph replay, advanced by :func:`adam_advance_`. ``weight_decay`` adds ``wd * x`` to the
-    rule's ``dx'`` (an ``OptimiserChain(rule, WeightDecay)``); the clip arguments and ``dev_skip``
-    are :func:`adam_`'s."""
+    rule's ``dx'`` (an ``OptimiserChain(rule, WeightDecay)``); the clip arguments, ``dev_skip`` and
+    ``sr`` are :func:`adam_`'s."""
     code, ns, has_bt = _rule_info(kind)
     if rho is not None:
         beta1 = rho
@@ -312,6 +473,7 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
         raise ValueError(f"fused {kind}: needs {ns} state list(s) and a gradient per parameter")
     if masters is not None and len(masters) != len(params):
         raise ValueError(f"fused {kind}: needs a master per parameter")
+    _sr_check(kind, sr, params, grads, states, masters)
     if dev_hyper is not None and (dev_hyper.dtype != torch.float32 or dev_hyper.numel() < (3 if has_bt else 1)
                                   or not dev_hyper.is_contiguous()):
         raise TypeError(f"fused {kind}: dev_hyper is a contiguous fp32 tensor of {3 if has_bt else 1} entries")
@@ -324,7 +486,7 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
             _call(C, "mt_rule", code, *head, float(lr), float(beta1), float(beta2), float(eps), float(bt1), float(bt2),
                   float(weight_decay), float(grad_scale), _ptr(dev_hyper), _ptr(dev_gscale),
                   _tscale_ptr(tscale, idx, _acc_dtype(pd), len(params)), float(clip_delta), stream,
-                  _scaling={"dev_skip": _skip_ptr(dev_skip)})
+                  _scaling={"dev_skip": _skip_ptr(dev_skip)}, _sr=sr and sr._native(idx, len(params)))
         return
     if dev_hyper is not None:
         h = dev_hyper.tolist()
@@ -336,15 +498,16 @@ def rule_(kind: str, params, grads, states, *, lr: float = 0.0, beta1: float = 0
         grad_scale = grad_scale * float(dev_gscale)
     rule_reference_(kind, params, grads, states, lr=lr, beta1=beta1, beta2=beta2, eps=eps, bt1=bt1, bt2=bt2,
                     masters=masters, tscale=tscale, clip_delta=clip_delta, weight_decay=weight_decay,
-                    grad_scale=grad_scale, dev_skip=dev_skip)
+                    grad_scale=grad_scale, dev_skip=dev_skip, sr=sr)
 
 
 def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta2=0.0, rho=None, eps=0.0, bt1=0.0,
                     bt2=0.0, masters=None, tscale=None, clip_delta=0.0, weight_decay=0.0, grad_scale=1.0,
-                    dev_skip=None):
+                    dev_skip=None, sr=None):
     """PyTorch reference of :func:`rule_`, term by term as the rules of ``optimisers`` write them
     (compute in fp32, or fp64 for fp64 params): the CPU path and the kernels' oracle."""
     _, ns, _ = _rule_info(kind)
+    _sr_check(kind, sr, params, grads, [list(st) for st in states], masters)
     if _skipped(dev_skip):
         return
     if rho is not None:
@@ -392,10 +555,10 @@ def rule_reference_(kind: str, params, grads, states, *, lr=0.0, beta1=0.0, beta
             dx = dx + wd * x
         x = x - dx
         for k in range(ns):
-            states[k][i].copy_(s[k])
+            _store(states[k][i], s[k], sr, k + 1, i)
         if masters is not None:
             masters[i].copy_(x)
-        p.copy_(x)
+        _store(p, x, sr, 0, i)
 
 
 # ---- layer-wise adaptive rules (csrc/kernels/optim_layerwise.hip) ---------------------------------
@@ -943,4 +1106,5 @@ __all__ = ["adam_", "adam_reference_", "adam_advance_", "sgd_", "sgd_reference_"
            "loss_scale_update_reference_", "LS_WORDS", "LS_SCALE", "LS_INV", "LS_TRACKER", "LS_SKIPPED", "LS_LAST",
            "LS_FLAG",
            "ema_", "ema_reference_", "ema_block", "ema_advance_", "ema_advance_reference_", "EMA_WORDS", "EMA_OMD",
-           "EMA_DECAY", "EMA_UPDATES", "EMA_SINCE", "EMA_HOLD"]
+           "EMA_DECAY", "EMA_UPDATES", "EMA_SINCE", "EMA_HOLD",
+           "SR", "SR_WORDS", "sr_block", "sr_advance_", "stochastic_round_", "stochastic_round_reference_"]

@@ -266,6 +266,18 @@ class DDP:
             :meth:`ema_state_dict` exports it, ``with ddp.ema_weights():`` evaluates with it, and
             :meth:`state_dict` carries it. Parameter changes from outside the engine do not reset it.
     master_weights: keep fp32 master copies (+ fp32 moments) for low-precision params.
+    stochastic_rounding: ``None`` (default: nothing is allocated or launched that was not before),
+            ``True`` (seed 0) or an int, the seed, the same on every rank. With
+            ``master_weights=False`` the bf16 buckets' updates round every bf16 store — the parameter
+            and the bf16 moments — stochastically (``ops.philox``: Philox4x32-10 inside the update
+            kernels, the bucket index as stream, each leaf's offset in the bucket as its place in it,
+            so the flat and the per-leaf route draw the same bits), which makes the 14 B per element
+            layout without masters trainable: a store is unbiased, where round to nearest drops every
+            update below half an ulp. fp32 and fp64 buckets are untouched. One device counter, advanced
+            once per applied step (not by a step the loss scaler skips), read by :meth:`sr_step` and
+            carried by :meth:`state_dict`. Every rank applies the same arithmetic to the same bits
+            with the same random bits, so replicas stay equal. ``ValueError`` with
+            ``master_weights=True`` or LARS / LAMB, ``TypeError`` with an fp16 bucket.
     average: divide the summed gradient by the world size (default False = reference SUM).
     overlap: launch bucket allreduces from backward hooks (default: ``FLUXMPI_OVERLAP``).
     broadcast: synchronise parameters and buffers from ``root_rank`` at construction.
@@ -286,8 +298,17 @@ class DDP:
                  comm_dtype: torch.dtype | None = None, watchdog: bool | None = None,
                  grad_mode: str | None = None, force_comm: bool | None = None,
                  tail_bucket_mb: float | None = None, overlap_opt: bool | None = None,
-                 clip_global_norm: float | None = None, loss_scale=None, ema=None):
+                 clip_global_norm: float | None = None, loss_scale=None, ema=None,
+                 stochastic_rounding: bool | int | None = None):
         cfg = get_config()
+        self._sr_seed = None
+        if stochastic_rounding is not None and stochastic_rounding is not False:
+            if master_weights:
+                raise ValueError("DDP: stochastic_rounding rounds the bf16 parameters and moments themselves; it "
+                                 "replaces the fp32 masters: pass master_weights=False")
+            self._sr_seed = 0 if stochastic_rounding is True else int(stochastic_rounding)
+            if not 0 <= self._sr_seed < 1 << 64:
+                raise ValueError(f"DDP: stochastic_rounding seed must be in [0, 2^64), got {stochastic_rounding}")
         self._ls = LossScale.parse(loss_scale)
         self._ema = EMA.parse(ema)
         self._ema_swapped = False  # inside `with ema_weights():`
@@ -534,6 +555,14 @@ class DDP:
             raise ValueError("DDP: LARS rescales every leaf's gradient by its own norm, which undoes a global "
                              "clip: drop clip_global_norm (LAMB takes it)")
         dev = self.device
+        # stochastic rounding: the generator's step counter {uint32 step, 7 unused} on the device
+        self._sr_block = None
+        if self._sr_seed is not None:
+            if self._layerwise:
+                raise ValueError(f"DDP: stochastic_rounding has no {self.kind.upper()} kernels")
+            if any(b.dtype == torch.float16 for b in self.buckets):
+                raise TypeError("DDP: stochastic_rounding is defined for bf16 parameters; this model has fp16 ones")
+            self._sr_block = fused.sr_block(dev)
         for b in self.buckets:
             low = b.dtype in (torch.bfloat16, torch.float16)
             use_master = self.master_weights and low
@@ -1006,6 +1035,8 @@ class DDP:
         if self._has_bt:
             fused.adam_advance_(self.hyper, self._inner.beta[0], self._inner.beta[1],
                                 dev_skip=self._ls_flag if self._ls is not None else None)
+        if self._sr_seed is not None:
+            fused.sr_advance_(self._sr_block, dev_skip=self._ls_flag if self._ls is not None else None)
         if self._ema is not None:  # in front of the scaler update, which clears the flag the EMA kernels read
             e = self._ema
             fused.ema_advance_(self._ema_block, decay=e.decay, warmup=e.warmup, every=e.every,
@@ -1087,6 +1118,11 @@ class DDP:
             kw["dev_gscale"] = self._ls_inv
         if self._ls is not None:
             kw["dev_skip"] = self._ls_flag
+        if self._sr_seed is not None and b.dtype == torch.bfloat16:
+            # one launch over the flat bucket, or its leaves at their offsets in it: the same bits
+            flat = len(ps) == 1 and ps[0] is b.flat_param
+            kw["sr"] = fused.SR(self._sr_seed, stream=b.index, dev_block=self._sr_block,
+                                offsets=[0] if flat else b.offsets)
         if self._layerwise:
             self._run_layerwise(st, gs, gscale, b, kw)
         elif self.kind == "adam":
@@ -1225,6 +1261,14 @@ class DDP:
         """1 if the last ``step()`` was skipped, else 0 (0-dim int32 device view)."""
         return self._scaler("step_skipped")[fused.LS_LAST]
 
+    def sr_step(self) -> torch.Tensor:
+        """The stochastic-rounding generator's step counter — applied steps so far; a step the loss
+        scaler skipped does not count — as a 0-dim int32 device view (the uint32's bits). Never
+        synchronises (read it after ``step()``, on the stream ``step()`` ran on)."""
+        if self._sr_seed is None:
+            raise RuntimeError("DDP.sr_step: the engine was built without stochastic_rounding")
+        return self._sr_block[0]
+
     def trust_ratios(self) -> dict:
         """``{name: ratio}`` of the last step's trust ratios under LARS / LAMB: 0-dim device tensors
         (fp32; fp64 for fp64 parameters), views of the engine's tables, so they follow later steps.
@@ -1362,6 +1406,8 @@ class DDP:
             blk = self._ls_block.detach().cpu()
             sd["loss_scale"] = {"scale": float(blk.view(torch.float32)[fused.LS_SCALE]),
                                 "growth_tracker": int(blk[fused.LS_TRACKER]), "skipped": int(blk[fused.LS_SKIPPED])}
+        if self._sr_seed is not None:
+            sd["sr"] = {"seed": self._sr_seed, "step": int(self._sr_block[0]) & 0xFFFFFFFF}
         if self._ema is not None:
             blk = self._ema_block.detach().cpu()
             sd["ema"] = {"buckets": [b.ema.detach().to("cpu", copy=True) for b in self.buckets],
@@ -1391,6 +1437,9 @@ class DDP:
                 ls = sd.get("loss_scale") or {"scale": self._ls.init, "growth_tracker": 0, "skipped": 0}
                 self._ls_block.copy_(fused.loss_scale_block(ls["scale"], "cpu", tracker=ls["growth_tracker"],
                                                             skipped=ls["skipped"]))
+            if self._sr_seed is not None:
+                # in place too; the seed is the constructor's (every rank's); without the key: step 0
+                self._sr_block.copy_(fused.sr_block("cpu", step=int((sd.get("sr") or {}).get("step", 0))))
             if self._ema is not None:
                 # in place as well; a checkpoint without an average starts one from the loaded masters
                 # (parameters where there are none), with no update counted
