@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _ext
+from ._launch import stream as _stream
 from .multi_tensor import DTYPE_CODE
 
 _MAX_ROWS = 8
@@ -28,10 +29,6 @@ def _sym_index(n: int, device) -> torch.Tensor:
         pos[iu[1], iu[0]] = torch.arange(iu.shape[1])
         t = _SYM_IDX[key] = pos.reshape(-1).to(device)
     return t
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _native(X: torch.Tensor, F: torch.Tensor, n: int) -> bool:

@@ -16,7 +16,7 @@ import weakref
 import torch
 
 from . import _ext
-from .fused_block import _stream
+from ._launch import stream as _stream
 
 
 def supported(qkv: torch.Tensor, heads: int) -> bool:

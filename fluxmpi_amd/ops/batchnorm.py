@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from . import _ext
 from . import graddst
+from ._launch import nhwc, ptr, stream
 from .multi_tensor import DTYPE_CODE
 
 
@@ -27,18 +28,25 @@ def _rows_c(x: torch.Tensor):
     raise ValueError("fused batchnorm expects 2D [N,C] or 4D [N,C,H,W] input")
 
 
-def _nhwc(x: torch.Tensor) -> torch.Tensor:
-    if x.dim() == 4:
-        return x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(
-            memory_format=torch.channels_last)
-    return x.contiguous()
+_nhwc = nhwc  # the name ops/syncbn.py and scripts import
 
 
-_WS: dict = {}
 _SHARDS = 64  # == kShards in csrc/kernels/{batchnorm,gemm}.hip
 _MAXC = 2048
 # [_SHARDS][2][_MAXC] shards (+ 64 floats of slack)
 _WS_FLOATS = _SHARDS * 2 * _MAXC + 64
+_WS: dict = {}
+_LWS: dict = {}
+_DWS: dict = {}
+
+
+def _persistent(pool: dict, x: torch.Tensor) -> torch.Tensor:
+    """The zeroed fp32 accumulator of x's (device, stream) in ``pool``, made on first use."""
+    key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
+    ws = pool.get(key)
+    if ws is None:
+        ws = pool[key] = torch.zeros(_WS_FLOATS, device=x.device, dtype=torch.float32)
+    return ws
 
 
 def _workspace(x: torch.Tensor) -> torch.Tensor:
@@ -48,16 +56,7 @@ def _workspace(x: torch.Tensor) -> torch.Tensor:
     last workgroup of the reduction kernel — re-zeroes the shards it consumes), so there is no
     memset per BatchNorm launch.
     """
-    stream = torch.cuda.current_stream(x.device)
-    key = (x.device.index, stream.cuda_stream)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = torch.zeros(_WS_FLOATS, device=x.device, dtype=torch.float32)
-        _WS[key] = ws
-    return ws
-
-
-_LWS: dict = {}
+    return _persistent(_WS, x)
 
 
 def _link_workspace(x: torch.Tensor) -> torch.Tensor:
@@ -66,28 +65,13 @@ def _link_workspace(x: torch.Tensor) -> torch.Tensor:
     another BatchNorm backward in between (e.g. a ResNet downsample branch between conv2's
     dgrad and bn1's backward), which reduces into :func:`_workspace`; keeping the linked sums
     apart makes the two independent."""
-    stream = torch.cuda.current_stream(x.device)
-    key = (x.device.index, stream.cuda_stream)
-    ws = _LWS.get(key)
-    if ws is None:
-        ws = torch.zeros(_WS_FLOATS, device=x.device, dtype=torch.float32)
-        _LWS[key] = ws
-    return ws
-
-
-_DWS: dict = {}
+    return _persistent(_LWS, x)
 
 
 def _dual_workspace(x: torch.Tensor) -> torch.Tensor:
     """Third persistent zeroed accumulator: the downsample branch's sums of the dual
     (bn3 + downsample BN) backward, reduced in the same pass as bn3's into :func:`_workspace`."""
-    stream = torch.cuda.current_stream(x.device)
-    key = (x.device.index, stream.cuda_stream)
-    ws = _DWS.get(key)
-    if ws is None:
-        ws = torch.zeros(_WS_FLOATS, device=x.device, dtype=torch.float32)
-        _DWS[key] = ws
-    return ws
+    return _persistent(_DWS, x)
 
 
 def kernel_supported(x: torch.Tensor) -> bool:
@@ -100,6 +84,8 @@ def kernel_supported(x: torch.Tensor) -> bool:
 
 
 def _grad_out(p, ch, like):
+    """fp32 [ch] output for the gradient of BatchNorm parameter ``p``: its DDP bucket slice when
+    one is attached (``graddst``, fp32 parameters), else a fresh tensor."""
     t = graddst.take(p, (ch,), torch.float32)
     return t if t is not None else torch.empty(ch, device=like.device, dtype=torch.float32)
 
@@ -209,13 +195,94 @@ def bn_counter(bn):
     return bn.momentum, bn.num_batches_tracked
 
 
+# ---- the launch layer: one function per BatchNorm kernel. Each owns the allocation of what it returns, the
+# null pointers, the dtype code and the stream; callers pass tensors and get tensors back.
+
+def launch_finalize(x, w32, b32, running_mean, running_var, momentum, eps, nbt, pending, ws=None, affine=False):
+    """Batch statistics of ``x`` -> ``(mean, invstd)``, with ``affine`` ``(mean, invstd, scale, shift)``
+    (``scale = w * invstd``, ``shift = fma(-mean, scale, b)``: what a consumer applies on load). ``pending``:
+    the per-channel sums already lie in the workspace ``ws`` (default :func:`_workspace`) from the epilogue
+    of the kernel that produced ``x``; else a statistics pass over ``x`` comes first. Updates the running
+    statistics and increments the counter ``nbt`` where given."""
+    rows, ch = _rows_c(x)
+    out = [torch.empty(ch, device=x.device, dtype=torch.float32) for _ in range(4 if affine else 2)]
+    mean, inv, scale, shift = out if affine else (*out, None, None)
+    ws = _workspace(x) if ws is None else ws
+    _ext.get(required=True).bn_stats_finalize(
+        x.data_ptr(), w32.data_ptr(), b32.data_ptr(), ptr(running_mean), ptr(running_var), mean.data_ptr(),
+        inv.data_ptr(), ptr(scale), ptr(shift), ws.data_ptr(), rows, ch, float(momentum), float(eps), int(pending),
+        DTYPE_CODE[x.dtype], stream(x), ptr(nbt))
+    return out
+
+
+def launch_apply(x, w32, b32, mean, inv, relu, residual=None):
+    """``(y, mask)``: y = [relu](x * scale + shift [+ residual]) from finished statistics. ReLU after a
+    residual add keeps a 1-bit mask (1/16 of y's bytes) for the backward; otherwise the backward kernels
+    recompute the mask from x (bit-identical to the forward) and ``mask`` is None."""
+    rows, ch = _rows_c(x)
+    res = nhwc(residual) if residual is not None else None
+    y = torch.empty_like(x)
+    mask = torch.empty(x.numel() // 8, device=x.device, dtype=torch.uint8) if (relu and res is not None) else None
+    _ext.get(required=True).bn_apply(x.data_ptr(), y.data_ptr(), ptr(res), ptr(w32), ptr(b32), mean.data_ptr(),
+                                     inv.data_ptr(), rows, ch, int(relu), ptr(mask), DTYPE_CODE[x.dtype], stream(x))
+    return y, mask
+
+
+def launch_bwd(dy, x, mask, w32, b32, mean, inv, relu, want_dres=False, stats_ready=False, params=(None, None),
+               want_dx=True):
+    """The fused-BN backward; returns ``(dx, dres, dw, db)``, dw / db fp32: in the bucket slices of
+    ``params`` (the (weight, bias) leaves) where attached (``graddst``). ``stats_ready``: the producer of
+    dy already accumulated the two reductions into the link workspace, so the reduce pass is skipped.
+    ``want_dx=False``: reduce + finalize only (the finished sums land in dw / db; a later kernel forms dx)."""
+    rows, ch = _rows_c(x)
+    dx = torch.empty_like(x) if want_dx else None
+    dres = torch.empty_like(x) if want_dres else None
+    # the finalize kernel always produces both reductions (they feed dx)
+    dw, db = (_grad_out(p, ch, x) for p in params)
+    ws = _link_workspace(x) if stats_ready else _workspace(x)
+    _ext.get(required=True).bn_bwd(dy.data_ptr(), x.data_ptr(), 0, ptr(mask), ptr(w32), ptr(b32), mean.data_ptr(),
+                                   inv.data_ptr(), ptr(dx), ptr(dres), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                   rows, ch, int(relu), DTYPE_CODE[x.dtype], stream(x), int(stats_ready))
+    return dx, dres, dw, db
+
+
+def launch_bwd_dual(dy, mask, c3, cds, w32, mean, inv, w232, mean2, inv2, params, want_dx=True):
+    """The backward of relu(bn(c3) + bn2(cds)): one reduce pass for both BatchNorms' sums, one pass writing both
+    input gradients; returns ``(dx, dx2, dw, db, dw2, db2)`` (``params``: the four leaves, as in
+    :func:`launch_bwd`). ``want_dx=False``: reduce + finalize only, dx = dx2 = None."""
+    rows, ch = _rows_c(c3)
+    dx, dx2 = (torch.empty_like(c3), torch.empty_like(cds)) if want_dx else (None, None)
+    dw, db, dw2, db2 = (_grad_out(p, ch, c3) for p in params)
+    _ext.get(required=True).bn_bwd_dual(
+        dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(), mean.data_ptr(),
+        inv.data_ptr(), w232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), ptr(dx), ptr(dx2), dw.data_ptr(),
+        db.data_ptr(), dw2.data_ptr(), db2.data_ptr(), _workspace(c3).data_ptr(), _dual_workspace(c3).data_ptr(), rows,
+        ch, DTYPE_CODE[c3.dtype], stream(c3))
+    return dx, dx2, dw, db, dw2, db2
+
+
+def hands_masked(link, mask, relu) -> bool:
+    """A masked GradLink takes (dy, mask) instead of dres = dy * mask: one write pass less."""
+    return bool(link is not None and link.masked and relu and mask is not None and mask.dtype == torch.uint8)
+
+
+def finish_bwd(dw, db, wdtype, has_w, has_b, link, dy, mask, dres, hand_masked):
+    """The tail of a BatchNorm backward: ``(dw, db, dres)`` as autograd gets them: dw / db in the
+    parameters' dtype (None without affine), and the residual's gradient handed to ``link`` instead
+    (as ``(dy, mask)`` when ``hand_masked``)."""
+    dw = (dw if wdtype == torch.float32 else dw.to(wdtype)) if has_w else None
+    db = (db if wdtype == torch.float32 else db.to(wdtype)) if has_b else None
+    if link is not None:
+        link.grad, dres = ((dy, mask) if hand_masked else dres), None
+    return dw, db, dres
+
+
 class _FusedBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, momentum, eps, relu, link=None,
                 nbt=None, bnlink=None):
-        C = _ext.get(required=True)
-        x = _nhwc(x)
-        res = _nhwc(residual) if residual is not None else None
+        x = nhwc(x)
+        res = nhwc(residual) if residual is not None else None
         rows, ch = _rows_c(x)
         y = torch.empty_like(x)
         w32 = weight.float() if weight is not None else None
@@ -226,14 +293,10 @@ class _FusedBN(torch.autograd.Function):
         # ReLU after a residual add: keep a 1-bit mask (1/16 of y's bytes) for the backward
         mask = torch.empty(x.numel() // 8, device=x.device, dtype=torch.uint8) if (relu and res is not None) \
             else None
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        C.bn_fwd_train(x.data_ptr(), y.data_ptr(), res.data_ptr() if res is not None else 0,
-                       w32.data_ptr() if w32 is not None else 0, b32.data_ptr() if b32 is not None else 0,
-                       running_mean.data_ptr() if running_mean is not None else 0,
-                       running_var.data_ptr() if running_var is not None else 0,
-                       save_mean.data_ptr(), save_inv.data_ptr(), ws.data_ptr(), rows, ch, float(momentum),
-                       float(eps), int(relu), mask.data_ptr() if mask is not None else 0, DTYPE_CODE[x.dtype], stream,
-                       nbt.data_ptr() if nbt is not None else 0)
+        _ext.get(required=True).bn_fwd_train(
+            x.data_ptr(), y.data_ptr(), ptr(res), ptr(w32), ptr(b32), ptr(running_mean), ptr(running_var),
+            save_mean.data_ptr(), save_inv.data_ptr(), ws.data_ptr(), rows, ch, float(momentum), float(eps), int(relu),
+            ptr(mask), DTYPE_CODE[x.dtype], stream(x), ptr(nbt))
         ctx.relu = relu
         ctx.has_res = residual is not None
         ctx.link = link if residual is not None else None
@@ -252,38 +315,17 @@ class _FusedBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        C = _ext.get(required=True)
         x, mask, w32, b32, save_mean, save_inv = ctx.saved_tensors
-        dy = _nhwc(dy)
+        dy = nhwc(dy)
         # the producer of dy already accumulated this BN's reductions into the workspace
         stats_ready = ctx.bnlink is not None and ctx.bnlink.ready
-        rows, ch = _rows_c(x)
-        dx = torch.empty_like(x)
-        # a masked GradLink takes (dy, mask) instead of dres = dy * mask: one write pass less
-        hand_masked = ctx.link is not None and ctx.link.masked and mask is not None and ctx.relu
-        dres = torch.empty_like(x) if (ctx.has_res and not hand_masked) else None
-        # the finalize kernel always produces both reductions (they feed dx)
-        # fp32 parameters: straight into their DDP bucket slices when attached (graddst)
-        dw, db = (_grad_out(p, ch, x) for p in ctx.params)
-        ws = _link_workspace(x) if stats_ready else _workspace(x)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        C.bn_bwd(dy.data_ptr(), x.data_ptr(), 0, mask.data_ptr() if mask is not None else 0,
-                 w32.data_ptr() if w32 is not None else 0, b32.data_ptr() if b32 is not None else 0,
-                 save_mean.data_ptr(), save_inv.data_ptr(), dx.data_ptr(),
-                 dres.data_ptr() if dres is not None else 0, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, ch,
-                 int(ctx.relu), DTYPE_CODE[x.dtype], stream, int(stats_ready))
+        hand_masked = hands_masked(ctx.link, mask, ctx.relu)
+        dx, dres, dw, db = launch_bwd(dy, x, mask, w32, b32, save_mean, save_inv, ctx.relu,
+                                      ctx.has_res and not hand_masked, stats_ready, ctx.params)
         if ctx.bnlink is not None:
             ctx.bnlink.release()
-        if w32 is None:
-            dw = None
-        elif ctx.wdtype != torch.float32:
-            dw = dw.to(ctx.wdtype)
-        if not ctx.has_bias:
-            db = None
-        elif ctx.wdtype != torch.float32:
-            db = db.to(ctx.wdtype)
-        if ctx.link is not None:
-            ctx.link.grad, dres = ((dy, mask) if hand_masked else dres), None
+        dw, db, dres = finish_bwd(dw, db, ctx.wdtype, w32 is not None, ctx.has_bias, ctx.link, dy, mask, dres,
+                                  hand_masked)
         return dx, dw, db, dres, None, None, None, None, None, None, None, None
 
 
@@ -311,16 +353,15 @@ def fused_batch_norm(x, weight, bias, running_mean, running_var, training=True, 
     if num_batches_tracked is not None and training:
         num_batches_tracked.add_(1)
     if (not training) and kernel_supported(x) and not torch.is_grad_enabled():
-        C = _ext.get(required=True)
-        x = _nhwc(x)
+        x = nhwc(x)
         rows, ch = _rows_c(x)
         y = torch.empty_like(x)
-        res = _nhwc(residual) if residual is not None else None
-        C.bn_fwd_infer(x.data_ptr(), y.data_ptr(), res.data_ptr() if res is not None else 0,
-                       weight.float().data_ptr() if weight is not None else 0,
-                       bias.float().data_ptr() if bias is not None else 0, running_mean.data_ptr(),
-                       running_var.data_ptr(), rows, ch, float(eps), int(relu), DTYPE_CODE[x.dtype],
-                       torch.cuda.current_stream(x.device).cuda_stream)
+        res = nhwc(residual) if residual is not None else None
+        w32 = weight.float() if weight is not None else None
+        b32 = bias.float() if bias is not None else None
+        _ext.get(required=True).bn_fwd_infer(x.data_ptr(), y.data_ptr(), ptr(res), ptr(w32), ptr(b32),
+                                             running_mean.data_ptr(), running_var.data_ptr(), rows, ch, float(eps),
+                                             int(relu), DTYPE_CODE[x.dtype], stream(x))
         return y
     return batch_norm_reference(x, weight, bias, running_mean, running_var, training, momentum, eps, relu, residual)
 

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import _ext
 from . import graddst
+from ._launch import conv_backward
 from .multi_tensor import DTYPE_CODE
 
 
@@ -111,8 +112,7 @@ class _SmallConv3x3(torch.autograd.Function):
                 torch.mm(dy2.t(), cols, out=flat.view(co, 9 * ci))
                 dw = flat.view(co, 3, 3, ci).permute(0, 3, 1, 2)  # channels_last strides over (co, kh, kw, ci)
         if ctx.needs_input_grad[0]:
-            dx = torch.ops.aten.convolution_backward(dy, x, weight, None, [stride] * 2, [pad] * 2, [1, 1], False,
-                                                     [0, 0], 1, [True, False, False])[0]
+            dx = conv_backward(dy, x, weight, stride, pad, True, False)[0]
         return dx, dw, None, None
 
 

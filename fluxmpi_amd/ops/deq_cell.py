@@ -17,16 +17,9 @@ import os
 import torch
 
 from . import _ext
+from ._launch import ptr as _ptr, stream as _stream
 
 ENABLED = True  # False: the unfused 5-launch cell (A/B, scripts/diag_deq_graphs.py)
-
-
-def _ptr(t) -> int:
-    return 0 if t is None else t.data_ptr()
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _cl(t: torch.Tensor) -> bool:

@@ -32,7 +32,10 @@ import torch
 
 from . import _ext
 from . import graddst
-from .batchnorm import BNStatsLink, GradLink, SideGradLink, _dual_workspace, _link_workspace, _workspace, bn_counter  # noqa: F401 (links re-exported)
+from ._launch import conv_backward, nhwc, stream as _stream  # noqa: F401 (_stream: imported by tests)
+from .batchnorm import (BNStatsLink, GradLink, SideGradLink, _dual_workspace, _link_workspace,  # noqa: F401 (links re-exported)
+                        _workspace, bn_counter, finish_bwd, hands_masked, launch_apply, launch_bwd, launch_bwd_dual,
+                        launch_finalize)
 from . import gemm as G
 from . import gemm_nt as _NT
 from . import groupnorm as _GN
@@ -65,31 +68,15 @@ DS_WGRAD = True
 S2_FWD = True
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
-
-
 def _nhwc2d(x: torch.Tensor) -> torch.Tensor:
     """[N,C,H,W] channels_last -> [N*H*W, C] view (copy if not channels_last)."""
-    if not x.is_contiguous(memory_format=torch.channels_last):
-        x = x.contiguous(memory_format=torch.channels_last)
+    x = nhwc(x)
     n, c, h, w = x.shape
     return x.permute(0, 2, 3, 1).reshape(n * h * w, c)
 
 
 def _empty_nhwc(n, c, h, w, like):
     return torch.empty(n, h, w, c, device=like.device, dtype=like.dtype).permute(0, 3, 1, 2)
-
-
-def _grad_out(p, ch, like):
-    """fp32 [ch] output for the gradient of BatchNorm parameter ``p``: its DDP bucket slice when
-    one is attached (``graddst``, fp32 parameters), else a fresh tensor."""
-    t = graddst.take(p, (ch,), torch.float32)
-    return t if t is not None else torch.empty(ch, device=like.device, dtype=torch.float32)
 
 
 def _fwd1x1_stats(x, weight, stats):
@@ -108,20 +95,23 @@ def _fwd1x1_stats(x, weight, stats):
     return c
 
 
-def _bn_bwd(dy, x, mask, w32, b32, mean, inv, relu, has_res, stats_ready=False, params=(None, None)):
-    """Shared fused-BN backward; returns (dx, dres, dw, db) (fp32 dw/db; ``params`` = the
-    (weight, bias) leaves whose bucket slices may receive them)."""
-    C = _ext.get(required=True)
-    rows, ch = x.numel() // x.shape[1], x.shape[1]
-    dx = torch.empty_like(x)
-    dres = torch.empty_like(x) if has_res else None
-    dw = _grad_out(params[0], ch, x)
-    db = _grad_out(params[1], ch, x)
-    ws = _link_workspace(x) if stats_ready else _workspace(x)
-    C.bn_bwd(dy.data_ptr(), x.data_ptr(), 0, _p(mask), _p(w32), _p(b32), mean.data_ptr(), inv.data_ptr(),
-             dx.data_ptr(), _p(dres), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, ch, int(relu),
-             DTYPE_CODE[x.dtype], _stream(x), int(stats_ready))
-    return dx, dres, dw, db
+_bn_bwd = launch_bwd  # (dy, x, mask, w32, b32, mean, inv, relu, has_res, stats_ready, params) -> (dx, dres, dw, db)
+
+
+def _wgrad1x1_candidates(dc, x, weight, stride=1, ours=True):
+    """The weight-gradient implementations of a 1x1 convolution that ``wgrad_best`` chooses from: MIOpen;
+    with ``ours`` our split-K kernel (stride 2: B rows gathered from the even pixels) and, at stride 1
+    where it takes the shape, the 256x256-tile kernel."""
+    co, ci = weight.shape[0], weight.shape[1]
+    impls = {"miopen": lambda: conv_backward(dc, x, weight, stride, 0, False, True)[1]}
+    if ours and stride == 1:
+        impls["ours"] = lambda: G.conv1x1_wgrad_v2(_nhwc2d(dc), _nhwc2d(x), out_dtype=weight.dtype).view(co, ci, 1, 1)
+        if _w256_ok(co, ci, dc):
+            from .linear import weight_grad
+            impls["w256"] = lambda: weight_grad(_nhwc2d(dc), _nhwc2d(x), weight.dtype).view(co, ci, 1, 1)
+    elif ours and stride == 2:
+        impls["ours"] = lambda: G.conv1x1_wgrad_s2(_nhwc2d(dc), x, out_dtype=weight.dtype).view(co, ci, 1, 1)
+    return impls
 
 
 class _Conv1x1Stats(torch.autograd.Function):
@@ -129,7 +119,7 @@ class _Conv1x1Stats(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, link=None, bnlink=None):
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         ctx.link, ctx.bnlink = link, bnlink
         note_filter(weight)
         c = _fwd1x1_stats(x, weight, _workspace(x))
@@ -200,7 +190,7 @@ class _Conv1x1Hybrid(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, link=None, bnlink=None, ours_stats=False):
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         ctx.link, ctx.bnlink = link, bnlink
         note_filter(weight)
         ctx.save_for_backward(x, weight)
@@ -212,19 +202,10 @@ class _Conv1x1Hybrid(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dc):
         x, weight = ctx.saved_tensors
-        if not dc.is_contiguous(memory_format=torch.channels_last):
-            dc = dc.contiguous(memory_format=torch.channels_last)
+        dc = nhwc(dc)
         dw = None
         if ctx.needs_input_grad[1]:
-            co, ci = weight.shape[0], weight.shape[1]
-            impls = {
-                "miopen": lambda: torch.ops.aten.convolution_backward(dc, x, weight, None, [1, 1], [0, 0], [1, 1], False,
-                                                                      [0, 0], 1, [False, True, False])[1],
-                "ours": lambda: G.conv1x1_wgrad_v2(_nhwc2d(dc), _nhwc2d(x), out_dtype=weight.dtype).view(co, ci, 1, 1)}
-            if _w256_ok(co, ci, dc):
-                from .linear import weight_grad
-                impls["w256"] = lambda: weight_grad(_nhwc2d(dc), _nhwc2d(x), weight.dtype).view(co, ci, 1, 1)
-            dw = wgrad_best(("1x1", tuple(x.shape), co), impls, param=weight)
+            dw = wgrad_best(("1x1", tuple(x.shape), weight.shape[0]), _wgrad1x1_candidates(dc, x, weight), param=weight)
         dx = _dgrad_nhwc(_nhwc2d(dc), weight, x, ctx.link, ctx.bnlink) if ctx.needs_input_grad[0] else None
         return dx, dw, None, None, None
 
@@ -275,7 +256,7 @@ class _Conv1x1Downsample(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, stride, link, stats=None):
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         ctx.stride, ctx.link = stride, link
         note_filter(weight)
         ctx.save_for_backward(x, weight)
@@ -286,8 +267,7 @@ class _Conv1x1Downsample(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dc):
         x, weight = ctx.saved_tensors
-        if not dc.is_contiguous(memory_format=torch.channels_last):
-            dc = dc.contiguous(memory_format=torch.channels_last)
+        dc = nhwc(dc)
         s = ctx.stride
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
@@ -308,8 +288,7 @@ class _Conv1x1Downsample(torch.autograd.Function):
         if need_w and not (need_x and dx is None):
             dw = _ds_wgrad(dc, x, weight, s)
         elif need_w or (need_x and dx is None):
-            dx_m, dw = torch.ops.aten.convolution_backward(dc, x, weight, None, [s, s], [0, 0], [1, 1], False,
-                                                           [0, 0], 1, [need_x and dx is None, need_w, False])[:2]
+            dx_m, dw = conv_backward(dc, x, weight, s, 0, need_x and dx is None, need_w)
             dx = dx if dx is not None else dx_m
         if dx is not None and ctx.link is not None and ctx.link.offer(dx):
             dx = None  # delivered to conv1's dgrad epilogue
@@ -320,17 +299,8 @@ def _ds_wgrad(dc, x, weight, s):
     """The downsample convolution's weight gradient: the fastest (measured once per shape) of
     MIOpen and our split-K kernel (stride 2: B rows gathered from the even pixels)."""
     co, ci = weight.shape[0], weight.shape[1]
-    impls = {"miopen": lambda: torch.ops.aten.convolution_backward(
-        dc, x, weight, None, [s, s], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])[1]}
-    if DS_WGRAD and dc.dtype == torch.bfloat16 and ci % 8 == 0 and co % 8 == 0 and G.ENGINE != 1:
-        if s == 1:
-            impls["ours"] = lambda: G.conv1x1_wgrad_v2(_nhwc2d(dc), _nhwc2d(x), out_dtype=weight.dtype).view(
-                co, ci, 1, 1)
-            if _w256_ok(co, ci, dc):
-                from .linear import weight_grad
-                impls["w256"] = lambda: weight_grad(_nhwc2d(dc), _nhwc2d(x), weight.dtype).view(co, ci, 1, 1)
-        elif s == 2:
-            impls["ours"] = lambda: G.conv1x1_wgrad_s2(_nhwc2d(dc), x, out_dtype=weight.dtype).view(co, ci, 1, 1)
+    impls = _wgrad1x1_candidates(dc, x, weight, s, ours=bool(
+        DS_WGRAD and dc.dtype == torch.bfloat16 and ci % 8 == 0 and co % 8 == 0 and G.ENGINE != 1))
     if "ours" not in impls:
         return impls["miopen"]()
     return wgrad_best(("ds", tuple(x.shape), co, s), impls, param=weight)
@@ -342,6 +312,16 @@ def conv1x1_downsample(x, weight, stride, link=None, ours_stats=False):
     return _Conv1x1Downsample.apply(x, weight, stride, link, _dual_workspace(x) if ours_stats else None)
 
 
+def _bn_fwd_from_stats(x, weight, bias, residual, running_mean, running_var, momentum, eps, relu, pending, nbt):
+    """BatchNorm(+residual)(+ReLU) of a convolution's output: the finalize (``pending``: of the sums the
+    convolution's epilogue left in the workspace; else after a statistics pass) and the apply pass.
+    Returns y and (mask, w32, b32, mean, inv)."""
+    w32, b32 = weight.float(), bias.float()
+    mean, inv = launch_finalize(x, w32, b32, running_mean, running_var, momentum, eps, nbt, pending)
+    y, mask = launch_apply(x, w32, b32, mean, inv, relu, residual)
+    return y, (mask, w32, b32, mean, inv)
+
+
 class _BNFromStats(torch.autograd.Function):
     """BatchNorm(+residual)(+ReLU) whose batch statistics are already in the workspace
     (``stats_ready``) or are computed by the stats pass here."""
@@ -349,50 +329,29 @@ class _BNFromStats(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, momentum, eps, relu, stats_ready,
                 link=None, nbt=None, bnlink=None):
-        C = _ext.get(required=True)
-        ch = x.shape[1]
-        rows = x.numel() // ch
-        w32 = weight.float()
-        b32 = bias.float()
-        mean = torch.empty(ch, device=x.device, dtype=torch.float32)
-        inv = torch.empty(ch, device=x.device, dtype=torch.float32)
-        ws = _workspace(x)
-        C.bn_stats_finalize(x.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(running_mean), _p(running_var),
-                            mean.data_ptr(), inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(momentum),
-                            float(eps), int(stats_ready), DTYPE_CODE[x.dtype], _stream(x), _p(nbt))
-        res = None
-        if residual is not None:
-            res = residual if residual.is_contiguous(memory_format=torch.channels_last) else \
-                residual.contiguous(memory_format=torch.channels_last)
-        y = torch.empty_like(x)
-        mask = torch.empty(x.numel() // 8, device=x.device, dtype=torch.uint8) if (relu and res is not None) \
-            else None
-        C.bn_apply(x.data_ptr(), y.data_ptr(), _p(res), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
-                   inv.data_ptr(), rows, ch, int(relu), _p(mask), DTYPE_CODE[x.dtype], _stream(x))
+        y, saved = _bn_fwd_from_stats(x, weight, bias, residual, running_mean, running_var, momentum, eps, relu,
+                                      stats_ready, nbt)
         ctx.relu, ctx.has_res, ctx.wdtype = relu, residual is not None, weight.dtype
         ctx.params = (weight, bias)
         ctx.link = link if residual is not None else None
         ctx.bnlink = bnlink
         if bnlink is not None:
-            bnlink.bind(x, mask, w32, b32, mean, inv, relu)
-        ctx.save_for_backward(x, mask, w32, b32, mean, inv)
+            bnlink.bind(x, *saved, relu)
+        ctx.save_for_backward(x, *saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, mask, w32, b32, mean, inv = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         ready = ctx.bnlink is not None and ctx.bnlink.ready
-        # a masked GradLink takes (dy, mask) instead of dres = dy * mask (one write pass less)
-        hand_masked = ctx.link is not None and ctx.link.masked and mask is not None and ctx.relu
-        dx, dres, dw, db = _bn_bwd(dy, x, mask, w32, b32, mean, inv, ctx.relu, ctx.has_res and not hand_masked,
-                                   ready, ctx.params)
+        hand_masked = hands_masked(ctx.link, mask, ctx.relu)
+        dx, dres, dw, db = launch_bwd(dy, x, mask, w32, b32, mean, inv, ctx.relu, ctx.has_res and not hand_masked,
+                                      ready, ctx.params)
         if ctx.bnlink is not None:
             ctx.bnlink.release()
-        if ctx.link is not None:
-            ctx.link.grad, dres = ((dy, mask) if hand_masked else dres), None
-        return dx, dw.to(ctx.wdtype), db.to(ctx.wdtype), dres, None, None, None, None, None, None, None, None, None
+        dw, db, dres = finish_bwd(dw, db, ctx.wdtype, True, True, ctx.link, dy, mask, dres, hand_masked)
+        return dx, dw, db, dres, None, None, None, None, None, None, None, None, None
 
 
 class _Conv3BN3(torch.autograd.Function):
@@ -413,60 +372,53 @@ class _Conv3BN3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a2, weight, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, nbt, link,
                 ours_fwd):
-        C = _ext.get(required=True)
-        cl = torch.channels_last
-        a2 = a2 if a2.is_contiguous(memory_format=cl) else a2.contiguous(memory_format=cl)
-        res = residual if residual.is_contiguous(memory_format=cl) else residual.contiguous(memory_format=cl)
+        a2 = nhwc(a2)
         note_filter(weight)
-        ws = _workspace(a2)
         # the per-shape forward choice of conv1x1_hybrid: our GEMM with bn3's sums in its epilogue, or
         # MIOpen and the statistics pass
-        c3 = _fwd1x1_stats(a2, weight, ws) if ours_fwd else torch.nn.functional.conv2d(a2, weight)
-        ch = c3.shape[1]
-        rows = c3.numel() // ch
-        w32, b32 = bn_weight.float(), bn_bias.float()
-        mean = torch.empty(ch, device=c3.device, dtype=torch.float32)
-        inv = torch.empty_like(mean)
-        C.bn_stats_finalize(c3.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(running_mean), _p(running_var),
-                            mean.data_ptr(), inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(momentum),
-                            float(eps), int(ours_fwd), DTYPE_CODE[c3.dtype], _stream(c3), _p(nbt))
-        y = torch.empty_like(c3)
-        mask = torch.empty(c3.numel() // 8, device=c3.device, dtype=torch.uint8)
-        C.bn_apply(c3.data_ptr(), y.data_ptr(), res.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
-                   inv.data_ptr(), rows, ch, 1, mask.data_ptr(), DTYPE_CODE[c3.dtype], _stream(c3))
+        c3 = _fwd1x1_stats(a2, weight, _workspace(a2)) if ours_fwd else torch.nn.functional.conv2d(a2, weight)
+        y, saved = _bn_fwd_from_stats(c3, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, True,
+                                      ours_fwd, nbt)
         ctx.link, ctx.wdtype, ctx.params = link, bn_weight.dtype, (bn_weight, bn_bias)
-        ctx.save_for_backward(a2, weight, c3, mask, w32, b32, mean, inv)
+        ctx.save_for_backward(a2, weight, c3, *saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        C = _ext.get(required=True)
         a2, weight, c3, mask, w32, b32, mean, inv = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         n, ci, h, w = a2.shape
-        co, rows = weight.shape[0], n * h * w
-        dev, st = dy.device, _stream(dy)
-        dbw, dbb = _grad_out(ctx.params[0], co, c3), _grad_out(ctx.params[1], co, c3)
-        # reduce + finalize only (dx = dres = null): the two finished sums land in dbw / dbb
-        C.bn_bwd(dy.data_ptr(), c3.data_ptr(), 0, mask.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
-                 inv.data_ptr(), 0, 0, dbw.data_ptr(), dbb.data_ptr(), _workspace(c3).data_ptr(), rows, co, 1,
-                 DTYPE_CODE[c3.dtype], st, 0)
-        slabs = conv3bn3_slabs(rows, dev)
-        part = torch.empty(slabs, co, ci, device=dev, dtype=torch.float32)
-        d_a2 = _empty_nhwc(n, ci, h, w, a2)
-        gemm(dy, weight, d_a2, M=rows, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False, mode=4,
-             splits=slabs, a_affine=(dbb, dbw), stats=part, residual=_nhwc2d(a2),
-             bn_bwd=(c3, w32, None, mean, inv, mask, 3))
-        dw = None
-        if ctx.needs_input_grad[1]:
-            with graddst.into(weight):
-                dw = graddst.empty((co, ci), weight.dtype, dev)
-            C.gemm_splitk_reduce(part.data_ptr(), slabs, co * ci, dw.data_ptr(), DTYPE_CODE[dw.dtype], st)
-            dw = dw.view(co, ci, 1, 1)
-        if ctx.link is not None:
-            ctx.link.grad = (dy, mask)  # the residual's gradient: conv1's dgrad epilogue applies the mask
-        return (d_a2, dw, dbw.to(ctx.wdtype), dbb.to(ctx.wdtype), None, None, None, None, None, None, None, None)
+        # reduce + finalize only (no dx, no dres): the two finished sums land in dbw / dbb
+        _, _, dbw, dbb = launch_bwd(dy, c3, mask, w32, b32, mean, inv, True, params=ctx.params, want_dx=False)
+        part = torch.empty(conv3bn3_slabs(n * h * w, dy.device), weight.shape[0], ci, device=dy.device,
+                           dtype=torch.float32)
+        d_a2 = _one_pass_branch(dy, mask, c3, w32, mean, inv, (dbb, dbw), a2, weight, part, _empty_nhwc(n, ci, h, w, a2))
+        dw = _slabs_to_wgrad(part, weight) if ctx.needs_input_grad[1] else None
+        # the residual's gradient travels as (dy, mask): conv1's dgrad epilogue applies the mask
+        dbw, dbb, _ = finish_bwd(dbw, dbb, ctx.wdtype, True, True, ctx.link, dy, mask, None, True)
+        return (d_a2, dw, dbw, dbb, None, None, None, None, None, None, None, None)
+
+
+def _one_pass_branch(dy, mask, c, w32, mean, inv, sums, act, weight, part, out):
+    """One branch of the one-pass backward around a BatchNorm after a 1x1 convolution (``gemm_bf16`` mode 4,
+    csrc/kernels/conv3bn3_bwd.hip): streams (dy, c, mask, act) once, forms the BatchNorm's input gradient in
+    registers from its finished ``sums`` = (sum dy, sum dy xhat), writes ``out`` = d_act = dx . W and one fp32
+    partial of dW = dx^T . act per workgroup into the slab set ``part`` [slabs, Cout, Cin]."""
+    co, ci = weight.shape[0], weight.shape[1]
+    return gemm(dy, weight, out, M=act.numel() // ci, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False,
+                mode=4, splits=part.shape[0], a_affine=sums, stats=part, residual=_nhwc2d(act),
+                bn_bwd=(c, w32, None, mean, inv, mask, 3))
+
+
+def _slabs_to_wgrad(part, weight):
+    """The split-K reduce of the slab set ``part`` [slabs, Cout, Cin] into the 1x1 filter's gradient, in its DDP
+    bucket slice when one is attached."""
+    co, ci = weight.shape[0], weight.shape[1]
+    with graddst.into(weight):
+        dw = graddst.empty((co, ci), weight.dtype, part.device)
+    _ext.get(required=True).gemm_splitk_reduce(part.data_ptr(), part.shape[0], co * ci, dw.data_ptr(),
+                                               DTYPE_CODE[dw.dtype], _stream(part))
+    return dw.view(co, ci, 1, 1)
 
 
 # the one-pass conv3 -> bn3 backward of the stage-1 identity blocks (FLUXMPI_CONV3BN3=0: the
@@ -481,18 +433,24 @@ def conv3bn3_slabs(rows: int, device) -> int:
     return max(1, min(-(-rows // 32), 2 * cus))
 
 
+def _fused_bn_training(*bns) -> bool:
+    """Every module is a training-mode affine fused BatchNorm with running statistics (what the nodes
+    that launch its kernels themselves read from it)."""
+    from .batchnorm import FusedBatchNorm2d
+    return all(isinstance(m, FusedBatchNorm2d) and m.training and m.affine and m.track_running_stats for m in bns)
+
+
 def conv3bn3_ok(a2, conv, bn, residual, link) -> bool:
     """:func:`conv3_bn3_relu` applies: bf16 NHWC, the 64 -> 256 1x1 convolution, a training-mode
     affine fused BatchNorm, and a residual whose gradient travels as (dy, mask) through a masked
     :class:`GradLink` (or is not needed)."""
-    from .batchnorm import FusedBatchNorm2d
     wt = conv.weight
     return (CONV3BN3 and G.ENGINE != 1 and a2.is_cuda and a2.dim() == 4 and a2.dtype == torch.bfloat16
             and wt.dtype == torch.bfloat16 and tuple(wt.shape) == (256, 64, 1, 1) and wt.is_contiguous()
             and a2.shape[1] == 64 and a2.numel() // 64 < 2 ** 31 and residual is not None
             and residual.shape == (a2.shape[0], 256, a2.shape[2], a2.shape[3]) and residual.dtype == a2.dtype
             and (link.masked if link is not None else not (residual.requires_grad and torch.is_grad_enabled()))
-            and isinstance(bn, FusedBatchNorm2d) and bn.training and bn.affine and bn.track_running_stats)
+            and _fused_bn_training(bn))
 
 
 def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True):
@@ -507,32 +465,22 @@ def _dual_bn_fwd(c3, bn, stats_ready, cds, bn2, ds_ready):
     """The forward launches of relu(bn(c3) + bn2(cds)): two finalizes (a statistics pass first where the
     sums are not pending) and one dual apply. ``bn`` / ``bn2``: (weight, bias, running_mean, running_var,
     momentum, eps, num_batches_tracked). Returns y and (c3, cds, mask, w32, mean, inv, w232, mean2, inv2)."""
-    C = _ext.get(required=True)
-    cl = torch.channels_last
     w, b, rm, rv, mom, eps, nbt = bn
     w2, b2, rm2, rv2, mom2, eps2, nbt2 = bn2
-    c3 = c3 if c3.is_contiguous(memory_format=cl) else c3.contiguous(memory_format=cl)
-    cds = cds if cds.is_contiguous(memory_format=cl) else cds.contiguous(memory_format=cl)
-    ch = c3.shape[1]
-    rows = c3.numel() // ch
-    f32 = dict(device=c3.device, dtype=torch.float32)
+    c3, cds = nhwc(c3), nhwc(cds)
     w32, b32, w232, b232 = w.float(), b.float(), w2.float(), b2.float()
-    mean, inv, mean2, inv2 = (torch.empty(ch, **f32) for _ in range(4))
-    ws, code, st = _workspace(c3), DTYPE_CODE[c3.dtype], _stream(c3)
     # bn3 first: its sums may be pending in the workspace (conv3's GEMM epilogue)
-    C.bn_stats_finalize(c3.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(rm), _p(rv), mean.data_ptr(),
-                        inv.data_ptr(), 0, 0, ws.data_ptr(), rows, ch, float(mom), float(eps), int(stats_ready),
-                        code, st, _p(nbt))
+    mean, inv = launch_finalize(c3, w32, b32, rm, rv, mom, eps, nbt, stats_ready)
     # bn_ds: its sums pending in the dual workspace (the downsample GEMM's epilogue), or a stats pass
-    ws2 = _dual_workspace(c3) if ds_ready else ws
-    C.bn_stats_finalize(cds.data_ptr(), w232.data_ptr(), b232.data_ptr(), _p(rm2), _p(rv2), mean2.data_ptr(),
-                        inv2.data_ptr(), 0, 0, ws2.data_ptr(), rows, ch, float(mom2), float(eps2), int(ds_ready),
-                        code, st, _p(nbt2))
+    mean2, inv2 = launch_finalize(cds, w232, b232, rm2, rv2, mom2, eps2, nbt2, ds_ready,
+                                  ws=_dual_workspace(c3) if ds_ready else None)
+    ch = c3.shape[1]
     y = torch.empty_like(c3)
     mask = torch.empty(c3.numel() // 8, device=c3.device, dtype=torch.uint8)
-    C.bn_apply_dual(c3.data_ptr(), cds.data_ptr(), y.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(),
-                    inv.data_ptr(), w232.data_ptr(), b232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), rows, ch,
-                    mask.data_ptr(), code, st)
+    _ext.get(required=True).bn_apply_dual(
+        c3.data_ptr(), cds.data_ptr(), y.data_ptr(), w32.data_ptr(), b32.data_ptr(), mean.data_ptr(), inv.data_ptr(),
+        w232.data_ptr(), b232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), c3.numel() // ch, ch, mask.data_ptr(),
+        DTYPE_CODE[c3.dtype], _stream(c3))
     return y, (c3, cds, mask, w32, mean, inv, w232, mean2, inv2)
 
 
@@ -558,19 +506,9 @@ class _DualBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        C = _ext.get(required=True)
         c3, cds, mask, w32, mean, inv, w232, mean2, inv2 = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
-        ch = c3.shape[1]
-        rows = c3.numel() // ch
-        dx, dx2 = torch.empty_like(c3), torch.empty_like(cds)
-        dw, db, dw2, db2 = (_grad_out(p, ch, c3) for p in ctx.params)
-        C.bn_bwd_dual(dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(), mean.data_ptr(),
-                      inv.data_ptr(), w232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), dx.data_ptr(),
-                      dx2.data_ptr(), dw.data_ptr(), db.data_ptr(), dw2.data_ptr(), db2.data_ptr(),
-                      _workspace(c3).data_ptr(), _dual_workspace(c3).data_ptr(), rows, ch, DTYPE_CODE[c3.dtype],
-                      _stream(c3))
+        dx, dx2, dw, db, dw2, db2 = launch_bwd_dual(nhwc(dy), mask, c3, cds, w32, mean, inv, w232, mean2, inv2,
+                                                    ctx.params)
         t1, t2 = ctx.wdtypes
         return (dx, dw.to(t1), db.to(t1), None, None, None, None, None, None,
                 dx2, dw2.to(t2), db2.to(t2), None, None, None, None, None, None)
@@ -579,11 +517,10 @@ class _DualBN(torch.autograd.Function):
 def dual_bn_supported(c, bn, bn_ds) -> bool:
     """``dual_bn_relu`` applies: fused training-mode affine BatchNorms with running statistics,
     channels a power of two <= 2048 (C/8 divides the 256-lane workgroup)."""
-    from .batchnorm import FusedBatchNorm2d, kernel_supported
+    from .batchnorm import kernel_supported
     ch = c.shape[1]
     return (DUAL_BN and kernel_supported(c) and c.dim() == 4 and (ch & (ch - 1)) == 0
-            and all(isinstance(m, FusedBatchNorm2d) and m.training and m.affine and m.track_running_stats
-                    for m in (bn, bn_ds)))
+            and _fused_bn_training(bn, bn_ds))
 
 
 def dual_bn_relu(c3, bn, cds, bn_ds, stats_ready=False, ds_stats_ready=False):
@@ -600,11 +537,8 @@ def dual_bn_relu(c3, bn, cds, bn_ds, stats_ready=False, ds_stats_ready=False):
 def dual_bn_ok(x, ch, bn, bn_ds) -> bool:
     """:func:`dual_bn_supported` for the output (``ch`` channels, x's dtype/device) of a
     convolution of ``x``, decided before running it."""
-    from .batchnorm import FusedBatchNorm2d
     return (DUAL_BN and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16, torch.float32) and x.dim() == 4
-            and ch % 8 == 0 and 8 <= ch <= 2048 and (ch & (ch - 1)) == 0
-            and all(isinstance(m, FusedBatchNorm2d) and m.training and m.affine and m.track_running_stats
-                    for m in (bn, bn_ds)))
+            and ch % 8 == 0 and 8 <= ch <= 2048 and (ch & (ch - 1)) == 0 and _fused_bn_training(bn, bn_ds))
 
 
 class _Conv3DsBN(torch.autograd.Function):
@@ -624,9 +558,7 @@ class _Conv3DsBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a2, w3, x, wds, w, b, w2, b2, rm, rv, mom, eps, nbt, rm2, rv2, mom2, eps2, nbt2, link, ours3,
                 ours_ds, form):
-        cl = torch.channels_last
-        a2 = a2 if a2.is_contiguous(memory_format=cl) else a2.contiguous(memory_format=cl)
-        x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
+        a2, x = nhwc(a2), nhwc(x)
         note_filter(w3)
         note_filter(wds)
         c3 = _fwd1x1_stats(a2, w3, _workspace(a2)) if ours3 else torch.nn.functional.conv2d(a2, w3)
@@ -641,19 +573,14 @@ class _Conv3DsBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        C = _ext.get(required=True)
         a2, w3, x, wds, c3, cds, mask, w32, mean, inv, w232, mean2, inv2 = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         n, ci, h, w = a2.shape
         co, rows = w3.shape[0], n * h * w
-        dev, st = dy.device, _stream(dy)
-        dw, db, dw2, db2 = (_grad_out(p, co, c3) for p in ctx.params)
-        # reduce + finalize only (dx = dx2 = null): the four finished sums land in dw / db / dw2 / db2
-        C.bn_bwd_dual(dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(), mean.data_ptr(),
-                      inv.data_ptr(), w232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(), 0, 0, dw.data_ptr(),
-                      db.data_ptr(), dw2.data_ptr(), db2.data_ptr(), _workspace(c3).data_ptr(),
-                      _dual_workspace(c3).data_ptr(), rows, co, DTYPE_CODE[c3.dtype], st)
+        dev = dy.device
+        # reduce + finalize only (no dx, dx2): the four finished sums land in dw / db / dw2 / db2
+        _, _, dw, db, dw2, db2 = launch_bwd_dual(dy, mask, c3, cds, w32, mean, inv, w232, mean2, inv2, ctx.params,
+                                                 want_dx=False)
         d_a2, d_x = _empty_nhwc(n, ci, h, w, a2), _empty_nhwc(n, ci, h, w, x)
         if ctx.form == 2:
             slabs = conv3ds_slabs(rows, dev)
@@ -662,22 +589,13 @@ class _Conv3DsBN(torch.autograd.Function):
                                     mean.data_ptr(), inv.data_ptr(), db.data_ptr(), dw.data_ptr(), w232.data_ptr(),
                                     mean2.data_ptr(), inv2.data_ptr(), db2.data_ptr(), dw2.data_ptr(), a2.data_ptr(),
                                     x.data_ptr(), w3.data_ptr(), wds.data_ptr(), d_a2.data_ptr(), d_x.data_ptr(),
-                                    part[0].data_ptr(), part[1].data_ptr(), rows, slabs, st)
+                                    part[0].data_ptr(), part[1].data_ptr(), rows, slabs, _stream(dy))
         else:
-            slabs = conv3bn3_slabs(rows, dev)
-            part = torch.empty(2, slabs, co, ci, device=dev, dtype=torch.float32)
-            for i, (c, cw, cm, civ, sdy, sdx, act, wt, out) in enumerate((
-                    (c3, w32, mean, inv, db, dw, a2, w3, d_a2), (cds, w232, mean2, inv2, db2, dw2, x, wds, d_x))):
-                gemm(dy, wt, out, M=rows, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False, mode=4,
-                     splits=slabs, a_affine=(sdy, sdx), stats=part[i], residual=_nhwc2d(act),
-                     bn_bwd=(c, cw, None, cm, civ, mask, 3))
-        grads = [None, None]
-        for i, wt in enumerate((w3, wds)):
-            if ctx.needs_input_grad[1 + 2 * i]:
-                with graddst.into(wt):
-                    g = graddst.empty((co, ci), wt.dtype, dev)
-                C.gemm_splitk_reduce(part[i].data_ptr(), slabs, co * ci, g.data_ptr(), DTYPE_CODE[g.dtype], st)
-                grads[i] = g.view(co, ci, 1, 1)
+            part = torch.empty(2, conv3bn3_slabs(rows, dev), co, ci, device=dev, dtype=torch.float32)
+            _one_pass_branch(dy, mask, c3, w32, mean, inv, (db, dw), a2, w3, part[0], d_a2)
+            _one_pass_branch(dy, mask, cds, w232, mean2, inv2, (db2, dw2), x, wds, part[1], d_x)
+        grads = [_slabs_to_wgrad(part[i], wt) if ctx.needs_input_grad[1 + 2 * i] else None
+                 for i, wt in enumerate((w3, wds))]
         if ctx.link is not None and ctx.link.offer(d_x):
             d_x = None  # delivered to conv1's dgrad epilogue
         t1, t2 = ctx.wdtypes
@@ -729,25 +647,15 @@ class _BNReluConv1x1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c2, bn_weight, bn_bias, running_mean, running_var, weight, momentum, eps, nbt=None,
                 stats_ready=False):
-        C = _ext.get(required=True)
-        if not c2.is_contiguous(memory_format=torch.channels_last):
-            c2 = c2.contiguous(memory_format=torch.channels_last)
+        c2 = nhwc(c2)
         n, ch, h, w = c2.shape
-        rows = n * h * w
         w32, b32 = bn_weight.float(), bn_bias.float()
-        mean = torch.empty(ch, device=c2.device, dtype=torch.float32)
-        inv = torch.empty_like(mean)
-        scale = torch.empty_like(mean)
-        shift = torch.empty_like(mean)
-        ws = _workspace(c2)
-        C.bn_stats_finalize(c2.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(running_mean), _p(running_var),
-                            mean.data_ptr(), inv.data_ptr(), scale.data_ptr(), shift.data_ptr(), ws.data_ptr(),
-                            rows, ch, float(momentum), float(eps), int(stats_ready), DTYPE_CODE[c2.dtype], _stream(c2),
-                            _p(nbt))
+        mean, inv, scale, shift = launch_finalize(c2, w32, b32, running_mean, running_var, momentum, eps, nbt,
+                                                  stats_ready, affine=True)
         co = weight.shape[0]
         c3 = _empty_nhwc(n, co, h, w, c2)
-        gemm(_nhwc2d(c2), weight.reshape(co, ch), c3, M=rows, N=co, K=ch, lda=ch, ldb=ch, ldc=co, a_kmajor=True,
-             b_kmajor=True, mode=1, stats=ws, a_affine=(scale, shift))
+        gemm(_nhwc2d(c2), weight.reshape(co, ch), c3, M=n * h * w, N=co, K=ch, lda=ch, ldb=ch, ldc=co, a_kmajor=True,
+             b_kmajor=True, mode=1, stats=_workspace(c2), a_affine=(scale, shift))
         ctx.bn_wdtype = bn_weight.dtype
         ctx.params = (bn_weight, bn_bias)  # the leaves: their gradients' bucket slices (graddst)
         ctx.save_for_backward(c2, w32, b32, mean, inv, scale, shift, weight)
@@ -769,8 +677,7 @@ class _BNReluConv1x1(torch.autograd.Function):
         # (w4d: the LDS-DMA kernel on the cached W^T, whose epilogue has the BN-backward reductions)
         da = conv1x1_dgrad(dc3_2d, weight.reshape(co, ch), bn_bwd=(c2_2d, w32, b32, mean, inv, None, 2),
                            stats=_link_workspace(c2), w4d=weight).view(n, h, w, ch).permute(0, 3, 1, 2)
-        dc2, _, dbw, dbb = _bn_bwd(da, c2, None, w32, b32, mean, inv, True, False, stats_ready=True,
-                                   params=ctx.params)
+        dc2, _, dbw, dbb = launch_bwd(da, c2, None, w32, b32, mean, inv, True, stats_ready=True, params=ctx.params)
         return dc2, dbw.to(ctx.bn_wdtype), dbb.to(ctx.bn_wdtype), None, None, dw, None, None, None, None
 
 
@@ -781,7 +688,7 @@ class _Conv3x3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, fwd_ours, with_stats, bnlink=None, gradlink=None):
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         ctx.bnlink = bnlink
         ctx.gradlink = gradlink
         note_filter(weight)
@@ -796,16 +703,13 @@ class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         dw = None
         # (inside groupnorm.skip_param_grads — the DEQ adjoint's VJPs w.r.t. activations only — the
         # filter gradient is not wanted although needs_input_grad, fixed at forward time, says so)
         if ctx.needs_input_grad[1] and not _GN._SKIP_PARAM_GRADS:
-            impls = {
-                "miopen": lambda: torch.ops.aten.convolution_backward(dy, x, weight, None, [1, 1], [1, 1], [1, 1], False,
-                                                                      [0, 0], 1, [False, True, False])[1],
-                "ours": lambda: G.conv3x3_wgrad(dy, x)}
+            impls = {"miopen": lambda: conv_backward(dy, x, weight, 1, 1, False, True)[1],
+                     "ours": lambda: G.conv3x3_wgrad(dy, x)}
             if x.dtype == torch.bfloat16 and G.wgrad3x3n_ok(tuple(x.shape), weight.shape[0]):
                 impls["w3n"] = lambda cfg: G.conv3x3_wgrad_n(dy, x, *cfg)  # narrow channels: rows staged once
                 impls["w3n_cfgs"] = w3n_configs(x.shape[1])
@@ -823,8 +727,7 @@ class _Conv3x3(torch.autograd.Function):
             # ran first: autograd orders it by data dependency); added in the dgrad epilogue
             res = ctx.gradlink.take() if ctx.gradlink is not None else None
             if bn is None and not _dgrad_is_ours(dy, weight, x.shape):
-                dx = torch.ops.aten.convolution_backward(dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
-                                                         1, [True, False, False])[0]
+                dx = conv_backward(dy, x, weight, 1, 1, True, False)[0]
                 if res is not None:
                     dx = dx + res
             elif res is not None and bn is not None:
@@ -855,8 +758,7 @@ def _dgrad_is_ours(dy, weight, x_shape) -> bool:
         w = weight.detach()
         xe = torch.empty(x_shape, device=dy.device, dtype=dy.dtype).contiguous(memory_format=torch.channels_last)
         ours = _time_us(lambda: conv3x3_dgrad(d, w))
-        theirs = _time_us(lambda: torch.ops.aten.convolution_backward(d, xe, w, None, [1, 1], [1, 1], [1, 1], False,
-                                                                      [0, 0], 1, [True, False, False]))
+        theirs = _time_us(lambda: conv_backward(d, xe, w, 1, 1, True, False))
     _DGRAD_CHOICE[key] = ours <= theirs
     return _DGRAD_CHOICE[key]
 
@@ -870,7 +772,7 @@ class _Conv3x3S2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, with_stats=False):
-        x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         ctx.save_for_backward(x, weight)
         if G.S2_DGRAD:
             note_filter(weight)  # the input gradient reads the batched transposed-filter cache
@@ -881,29 +783,32 @@ class _Conv3x3S2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         dx = dw = None
         if ctx.needs_input_grad[1]:
             dw = wgrad_best(("3x3s2", tuple(x.shape), weight.shape[0]), {
-                "miopen": lambda: torch.ops.aten.convolution_backward(dy, x, weight, None, [2, 2], [1, 1], [1, 1], False,
-                                                                      [0, 0], 1, [False, True, False])[1],
+                "miopen": lambda: conv_backward(dy, x, weight, 2, 1, False, True)[1],
                 "ours": lambda: G.conv3x3_wgrad_s2(dy, x)}, param=weight)
         if ctx.needs_input_grad[0]:
             if G.s2_dgrad_ok(dy, weight, x.shape):
                 dx = G.conv3x3_s2_dgrad(dy, weight, x.shape)  # four parity-class implicit GEMMs
             else:
-                dx = torch.ops.aten.convolution_backward(dy, x, weight, None, [2, 2], [1, 1], [1, 1], False, [0, 0],
-                                                         1, [True, False, False])[0]
+                dx = conv_backward(dy, x, weight, 2, 1, True, False)[0]
         return dx, dw, None
 
 
-def conv3x3_s2_supported(x: torch.Tensor, conv: torch.nn.Conv2d) -> bool:
-    return (DS_WGRAD and G.ENGINE != 1 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
+def _conv3x3_geometry_ok(x: torch.Tensor, conv: torch.nn.Conv2d, stride: int) -> bool:
+    """What our 3x3 kernels of either stride take: a bf16 GPU batch, a plain 3x3 / pad 1 convolution of that
+    stride without bias, channel counts that are multiples of 8, pixels below 2^31."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+            and conv.kernel_size == (3, 3) and conv.stride == (stride, stride) and conv.padding == (1, 1)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0 and conv.weight.dtype == torch.bfloat16
             and x.numel() // x.shape[1] < 2 ** 31)
+
+
+def conv3x3_s2_supported(x: torch.Tensor, conv: torch.nn.Conv2d) -> bool:
+    return DS_WGRAD and G.ENGINE != 1 and _conv3x3_geometry_ok(x, conv, 2)
 
 
 def conv3x3_s2_forward_is_ours(x, weight) -> bool:
@@ -927,11 +832,7 @@ def conv3x3_s2(x, weight, with_stats=False):
 
 
 def conv3x3_supported(x: torch.Tensor, conv: torch.nn.Conv2d) -> bool:
-    return (CONV3X3 in ("ours", "dgrad") and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0 and conv.weight.dtype == torch.bfloat16
-            and x.numel() // x.shape[1] < 2 ** 31)
+    return CONV3X3 in ("ours", "dgrad") and _conv3x3_geometry_ok(x, conv, 1)
 
 
 def conv3x3_forward_is_ours(x, weight) -> bool:
@@ -979,7 +880,7 @@ def conv3x3(x, weight, with_stats=False, bnlink=None, gradlink=None):
 
 def conv3x3_fwd_raw(x, weight):
     """The 3x3 / s1 forward the autograd path would run (per-shape choice), without autograd."""
-    x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    x = nhwc(x)
     # a forward marks the cached transposed filter stale whichever kernel runs (as _Conv3x3 does):
     # the next input gradient re-derives it from the current weights
     note_filter(weight)
@@ -991,13 +892,11 @@ def conv3x3_fwd_raw(x, weight):
 def conv3x3_dgrad_raw(dy, weight, x_shape, residual=None):
     """The 3x3 / s1 input gradient (+ ``residual`` in the epilogue) per the per-shape choice,
     without autograd."""
-    if not dy.is_contiguous(memory_format=torch.channels_last):
-        dy = dy.contiguous(memory_format=torch.channels_last)
+    dy = nhwc(dy)
     if _dgrad_is_ours(dy, weight, x_shape):
         return conv3x3_dgrad(dy, weight, residual=residual)
     xe = torch.empty(x_shape, device=dy.device, dtype=dy.dtype).contiguous(memory_format=torch.channels_last)
-    dx = torch.ops.aten.convolution_backward(dy, xe, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                             [True, False, False])[0]
+    dx = conv_backward(dy, xe, weight, 1, 1, True, False)[0]
     return dx + residual if residual is not None else dx
 
 

@@ -18,18 +18,14 @@ import torch
 from . import _ext
 from . import gemm_nt as _NT
 from . import graddst
+from ._launch import nhwc, ptr as _ptr, stream as _stream
+from .multi_tensor import DTYPE_CODE
 
 SHARDS = 64  # == kShards in csrc/kernels/{batchnorm,gemm}.hip
 # LDS buffering of the GEMM main loop: 0 = per-shape choice in the kernel launcher, 1 or 2 forces it
 NBUF = 0
 # GEMM kernel: 0 = launcher's choice, 1 = register-staged (gemm.hip), 2 = LDS-DMA pipelined (gemm_glds.hip)
 ENGINE = int(os.environ.get("FLUXMPI_GEMM_ENGINE", "0"))
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else 0
 
 
 def gemm(a, b, c, *, M, N, K, lda, ldb, ldc, a_kmajor=True, b_kmajor=True, mode=0, splits=1, a_affine=None,
@@ -195,7 +191,7 @@ def conv3x3_fwd(x: torch.Tensor, w: torch.Tensor, in_affine=None, stats: torch.T
     """
     n, c, h, wd = x.shape
     co = w.shape[0]
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    xs = nhwc(x)
     w2 = w.permute(0, 2, 3, 1).contiguous()  # [Co][3][3][C]: K-major over (tap, channel)
     note_filter(w)
     y = out if out is not None else torch.empty(n, h, wd, co, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
@@ -217,7 +213,7 @@ def conv3x3_s2_fwd(x: torch.Tensor, w: torch.Tensor, stats: torch.Tensor | None 
     n, c, h, wd = x.shape
     co = w.shape[0]
     ho, wo = (h + 1) // 2, (wd + 1) // 2
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    xs = nhwc(x)
     w2 = w.permute(0, 2, 3, 1).contiguous()  # [Co][3][3][C]
     y = torch.empty(n, ho, wo, co, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
     gemm(xs, w2, y, M=n * ho * wo, N=co, K=9 * c, lda=c, ldb=9 * c, ldc=co, mode=1 if stats is not None else 0,
@@ -260,8 +256,7 @@ def conv3x3_s2_dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape) -> torch.Tensor
     n, co, ho, wo = dy.shape
     ci = w.shape[1]
     h, wd = x_shape[2], x_shape[3]
-    dys = dy if dy.is_contiguous(memory_format=torch.channels_last) else dy.contiguous(
-        memory_format=torch.channels_last)
+    dys = nhwc(dy)
     wt = filter_t(w)  # [ci][3][3][co] flipped: original tap (kh, kw) at column block 8 - (3 kh + kw)
     dx = torch.empty(n, h, wd, ci, device=dy.device, dtype=dy.dtype).permute(0, 3, 1, 2)
     for cls in range(4):
@@ -280,8 +275,7 @@ def conv3x3_dgrad(dy: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = 
     epilogue — the other summand of the input's gradient when the input has a second consumer."""
     n, co, h, wd = dy.shape
     ci = w.shape[1]
-    dys = dy if dy.is_contiguous(memory_format=torch.channels_last) else dy.contiguous(
-        memory_format=torch.channels_last)
+    dys = nhwc(dy)
     if ENGINE == 1:  # register-staged kernel: transpose on the spot
         wt = w.flip(2, 3).permute(1, 2, 3, 0).contiguous()  # [Ci][3][3][Co]
     else:
@@ -353,7 +347,7 @@ def conv1x1_wgrad(dy2d: torch.Tensor, x2d: torch.Tensor, in_affine=None, out: to
     ws = torch.empty(s, Co, Ci, device=dy2d.device, dtype=torch.float32)
     gemm(dy2d, x2d, ws, mode=3, splits=s, **common)
     C = _ext.get(required=True)
-    C.gemm_splitk_reduce(ws.data_ptr(), s, Co * Ci, dw.data_ptr(), 9 if dw.dtype == torch.bfloat16 else 7,
+    C.gemm_splitk_reduce(ws.data_ptr(), s, Co * Ci, dw.data_ptr(), DTYPE_CODE[dw.dtype],
                          _stream(dw))
     return dw
 
@@ -374,7 +368,7 @@ def _wgrad_splits_v2(M: int, N: int, K: int) -> int:
 
 def _wgrad_reduce(ws, splits, dw):
     C = _ext.get(required=True)
-    C.gemm_splitk_reduce(ws.data_ptr(), splits, dw.numel(), dw.data_ptr(), 9 if dw.dtype == torch.bfloat16 else 7,
+    C.gemm_splitk_reduce(ws.data_ptr(), splits, dw.numel(), dw.data_ptr(), DTYPE_CODE[dw.dtype],
                          _stream(dw))
     return dw
 
@@ -409,7 +403,7 @@ def conv1x1_wgrad_s2(dy2d: torch.Tensor, x: torch.Tensor, out_dtype=torch.bfloat
     B staging (no strided copy of X). ``dy2d`` [N*Ho*Wo, Cout], ``x`` NCHW channels_last."""
     K, Co = dy2d.shape
     n, ci, h, w = x.shape
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    xs = nhwc(x)
     assert K == n * ((h + 1) // 2) * ((w + 1) // 2)
     s = _actual_splits_v2(K, splits or _wgrad_splits_v2(Co, ci, K))
     ws = torch.empty(s, Co, ci, device=dy2d.device, dtype=torch.float32)
@@ -426,9 +420,8 @@ def conv3x3_wgrad_s2(dy: torch.Tensor, x: torch.Tensor, splits: int | None = Non
     n, co, ho, wo = dy.shape
     ci, h, wd = x.shape[1], x.shape[2], x.shape[3]
     assert ho == (h + 1) // 2 and wo == (wd + 1) // 2
-    dys = dy if dy.is_contiguous(memory_format=torch.channels_last) else dy.contiguous(
-        memory_format=torch.channels_last)
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    dys = nhwc(dy)
+    xs = nhwc(x)
     K, N = n * ho * wo, 9 * ci
     s = _actual_splits_v2(K, splits or _wgrad_splits_v2(co, N, K))
     ws = torch.empty(s, co, N, device=dy.device, dtype=torch.float32)
@@ -455,9 +448,8 @@ def conv3x3_wgrad_n(dy: torch.Tensor, x: torch.Tensor, variant: int = 1, target_
     in channels_last, like ``conv3x3_wgrad``."""
     n, co, h, wd = dy.shape
     ci = x.shape[1]
-    dys = dy if dy.is_contiguous(memory_format=torch.channels_last) else dy.contiguous(
-        memory_format=torch.channels_last)
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    dys = nhwc(dy)
+    xs = nhwc(x)
     C = _ext.get(required=True)
     groups = C.wgrad3x3n_groups(ci, co, variant)
     s = C.wgrad3x3n_splits(n, h, max(1, target_wg // groups))
@@ -474,9 +466,8 @@ def conv3x3_wgrad(dy: torch.Tensor, x: torch.Tensor, splits: int | None = None) 
     [Co, Ci, 3, 3] in channels_last (the filter parameters' layout)."""
     n, co, h, wd = dy.shape
     ci = x.shape[1]
-    dys = dy if dy.is_contiguous(memory_format=torch.channels_last) else dy.contiguous(
-        memory_format=torch.channels_last)
-    xs = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    dys = nhwc(dy)
+    xs = nhwc(x)
     K, N = n * h * wd, 9 * ci
     s = _actual_splits_v2(K, splits or _wgrad_splits_v2(co, N, K))
     ws = torch.empty(s, co, N, device=dy.device, dtype=torch.float32)

@@ -37,6 +37,7 @@ import os
 import torch
 
 from . import _ext
+from ._launch import stream as _stream
 from . import graddst
 from .multi_tensor import DTYPE_CODE
 
@@ -48,10 +49,6 @@ ENABLED = MODE != "0"
 # cut hipBLASLt to fc2 (2.75 ms), but ViT-B/16 measured -0.4 % in three interleaved pairs
 # (profiles/rd6z_vit_plain_fwd_ab.jsonl); plain forward GEMMs stay on the vendor library.
 PLAIN_FWD_MAX_K = int(os.environ.get("FLUXMPI_GEMM_NT_PLAIN_FWD_MAX_K", "0"))
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _aligned(*tensors: torch.Tensor) -> bool:

@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
+from ._launch import stream as _stream
 from . import graddst
 from .multi_tensor import DTYPE_CODE
 
@@ -87,10 +88,6 @@ def _f32(p):
     if hit is not None and hit[0] is p:
         return hit[1]
     return p.float().contiguous()
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def supported(x: torch.Tensor, groups: int) -> bool:

@@ -15,18 +15,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
+from ._launch import ptr as _p, stream as _stream
 from . import graddst
 from .multi_tensor import DTYPE_CODE
 
 _MAX_BLOCKS = 4096
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
 
 
 def supported(x: torch.Tensor) -> bool:

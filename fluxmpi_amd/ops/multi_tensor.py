@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _ext
+from ._launch import stream as _stream
 
 DTYPE_CODE = {torch.float32: 7, torch.bfloat16: 9, torch.float16: 6, torch.float64: 8}
 
@@ -30,10 +31,6 @@ def aligned_offsets(numels, dtype: torch.dtype):
         offs.append(cur)
         cur += (n + a - 1) // a * a
     return offs, cur
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _code(dt: torch.dtype) -> int:

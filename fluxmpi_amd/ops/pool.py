@@ -17,8 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _ext
-from .batchnorm import _workspace
-from .fused_block import _bn_bwd, _empty_nhwc, _p, _stream
+from ._launch import nhwc, stream
+from .batchnorm import launch_bwd, launch_finalize
+from .fused_block import _empty_nhwc
 from .multi_tensor import DTYPE_CODE
 
 
@@ -30,23 +31,17 @@ class _BNReluMaxPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, k, s, p, nbt=None):
         C = _ext.get(required=True)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
+        x = nhwc(x)
         n, ch, h, w = x.shape
-        rows = n * h * w
         w32 = weight.float() if weight is not None else torch.ones(ch, device=x.device)
         b32 = bias.float() if bias is not None else torch.zeros(ch, device=x.device)
-        mean = torch.empty(ch, device=x.device, dtype=torch.float32)
-        inv, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-        ws = _workspace(x)
-        C.bn_stats_finalize(x.data_ptr(), w32.data_ptr(), b32.data_ptr(), _p(running_mean), _p(running_var),
-                            mean.data_ptr(), inv.data_ptr(), scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), rows,
-                            ch, float(momentum), float(eps), 0, DTYPE_CODE[x.dtype], _stream(x), _p(nbt))
+        mean, inv, scale, shift = launch_finalize(x, w32, b32, running_mean, running_var, momentum, eps, nbt,
+                                                  pending=False, affine=True)
         oh, ow = _out(h, k, s, p), _out(w, k, s, p)
         y = _empty_nhwc(n, ch, oh, ow, x)
         idx = torch.empty(n * oh * ow * ch, device=x.device, dtype=torch.uint8)
         C.bn_relu_maxpool_fwd(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), idx.data_ptr(), n, h, w,
-                              ch, k, s, p, DTYPE_CODE[x.dtype], _stream(x))
+                              ch, k, s, p, DTYPE_CODE[x.dtype], stream(x))
         ctx.geo = (k, s, p)
         ctx.wdtype = weight.dtype if weight is not None else None
         ctx.has_affine = (weight is not None, bias is not None)
@@ -57,14 +52,13 @@ class _BNReluMaxPool(torch.autograd.Function):
     def backward(ctx, dy):
         C = _ext.get(required=True)
         x, idx, w32, b32, mean, inv = ctx.saved_tensors
-        if not dy.is_contiguous(memory_format=torch.channels_last):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = nhwc(dy)
         n, ch, h, w = x.shape
         k, s, p = ctx.geo
         dz = torch.empty_like(x)  # gradient of the pre-ReLU normalised activation
         C.maxpool_bwd(dy.data_ptr(), idx.data_ptr(), dz.data_ptr(), n, h, w, ch, k, s, p, DTYPE_CODE[x.dtype],
-                      _stream(x))
-        dx, _, dw, db = _bn_bwd(dz, x, None, w32, b32, mean, inv, False, False)
+                      stream(x))
+        dx, _, dw, db = launch_bwd(dz, x, None, w32, b32, mean, inv, False)
         has_w, has_b = ctx.has_affine
         return (dx, dw.to(ctx.wdtype) if has_w else None, db.to(ctx.wdtype) if has_b else None,
                 None, None, None, None, None, None, None, None)
@@ -79,7 +73,7 @@ def pad_c3_to_c4(x: torch.Tensor) -> torch.Tensor:
     if c != 3 or not xp.is_contiguous() or x.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError("pad_c3_to_c4: needs a channels_last bf16/fp16 [N, 3, H, W] tensor")
     y = torch.empty(n, h, w, 4, device=x.device, dtype=x.dtype)
-    C.pad_c3_to_c4(xp.data_ptr(), y.data_ptr(), n * h * w, DTYPE_CODE[x.dtype], _stream(x))
+    C.pad_c3_to_c4(xp.data_ptr(), y.data_ptr(), n * h * w, DTYPE_CODE[x.dtype], stream(x))
     return y.permute(0, 3, 1, 2)
 
 

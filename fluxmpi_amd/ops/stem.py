@@ -26,7 +26,8 @@ import torch
 
 from . import _ext
 from . import graddst
-from .batchnorm import _workspace
+from ._launch import stream as _stream
+from .batchnorm import _workspace, launch_finalize
 from .multi_tensor import DTYPE_CODE
 
 CO, KK = 64, 256
@@ -136,21 +137,16 @@ class _StemFn(torch.autograd.Function):
     def forward(ctx, x4, weight, bn_w, bn_b, running_mean, running_var, momentum, eps, nbt=None):
         C = _ext.get(required=True)
         n = x4.shape[0]
-        stream = torch.cuda.current_stream(x4.device).cuda_stream
+        stream = _stream(x4)
         wp = pack_filter(weight)
         c = torch.empty(n, 112, 112, CO, device=x4.device, dtype=torch.bfloat16)
         ws = _workspace(x4)
         C.stem_fwd(x4.data_ptr(), wp.data_ptr(), c.data_ptr(), ws.data_ptr(), n, stream)
         w32 = bn_w.float() if bn_w is not None else torch.ones(CO, device=x4.device)
         b32 = bn_b.float() if bn_b is not None else torch.zeros(CO, device=x4.device)
-        mean = torch.empty(CO, device=x4.device, dtype=torch.float32)
-        inv, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-        rm = running_mean.data_ptr() if running_mean is not None else 0
-        rv = running_var.data_ptr() if running_var is not None else 0
-        C.bn_stats_finalize(c.data_ptr(), w32.data_ptr(), b32.data_ptr(), rm, rv, mean.data_ptr(), inv.data_ptr(),
-                            scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), n * 112 * 112, CO, float(momentum),
-                            float(eps), 1, DTYPE_CODE[torch.bfloat16], stream,
-                            nbt.data_ptr() if nbt is not None else 0)
+        # the sums are pending in the workspace from the convolution's epilogue
+        mean, inv, scale, shift = launch_finalize(c.permute(0, 3, 1, 2), w32, b32, running_mean, running_var, momentum,
+                                                  eps, nbt, pending=True, ws=ws, affine=True)
         y = torch.empty(n, 56, 56, CO, device=x4.device, dtype=torch.bfloat16)
         idx = torch.empty(n * 56 * 56 * CO, device=x4.device, dtype=torch.uint8)
         C.bn_relu_maxpool_fwd(c.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), idx.data_ptr(), n, 112,
@@ -166,7 +162,7 @@ class _StemFn(torch.autograd.Function):
         x4, c, idx, w32, mean, inv = ctx.saved_tensors
         n = x4.shape[0]
         dev = x4.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(x4)
         dy = dy.permute(0, 2, 3, 1)
         if not dy.is_contiguous():
             dy = dy.contiguous()

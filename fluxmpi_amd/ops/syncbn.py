@@ -36,7 +36,9 @@ import torch
 import torch.nn as nn
 
 from . import _ext
-from .batchnorm import GradLink, _grad_out, _nhwc, _rows_c, bn_counter, fused_batch_norm
+from ._launch import nhwc as _nhwc, ptr as _p, stream as _stream
+from .batchnorm import (GradLink, _grad_out, _rows_c, bn_counter, finish_bwd, fused_batch_norm, hands_masked,
+                        launch_apply)
 from .multi_tensor import DTYPE_CODE
 
 COUNT_RADIX = 4096  # == kCountRadix in csrc/kernels/batchnorm.hip
@@ -73,14 +75,6 @@ def _partials(x: torch.Tensor, rows: int, ch: int) -> torch.Tensor:
         buf = torch.empty(max(need, _PART_MIN), device=x.device, dtype=torch.float32)
         _PART[key] = buf
     return buf
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
-
-
-def _stream(x):
-    return torch.cuda.current_stream(x.device).cuda_stream
 
 
 def _rows2d(x: torch.Tensor) -> torch.Tensor:
@@ -153,15 +147,9 @@ def apply_stats(x, save_mean, save_invstd, weight=None, bias=None, relu=False, r
     rows, ch = _rows_c(x)
     if kernel_covers(x):
         x = _nhwc(x)
-        y = torch.empty_like(x)
         if rows == 0:
-            return y, None
-        res = _nhwc(residual) if residual is not None else None
-        mask = torch.empty(x.numel() // 8, device=x.device, dtype=torch.uint8) if (relu and res is not None) else None
-        _ext.get(required=True).bn_apply(x.data_ptr(), y.data_ptr(), _p(res), _p(weight), _p(bias),
-                                         save_mean.data_ptr(), save_invstd.data_ptr(), rows, ch, int(relu), _p(mask),
-                                         DTYPE_CODE[x.dtype], _stream(x))
-        return y, mask
+            return torch.empty_like(x), None
+        return launch_apply(x, weight, bias, save_mean, save_invstd, relu, residual)
     scale = save_invstd if weight is None else weight.float() * save_invstd
     shift = -save_mean * scale if bias is None else bias.float() - save_mean * scale
     o = _rows2d(x).float() * scale + shift
@@ -311,21 +299,11 @@ class _SyncBN(torch.autograd.Function):
         msg, dw, db = backward_message(dy, x, mask, w32, b32, sm, si, ctx.relu, dw, db)
         if ctx.world > 1:
             _allreduce(msg)
-        # a masked GradLink takes (dy, mask) instead of dres = dy * mask: one write pass less
-        hand_masked = (ctx.link is not None and ctx.link.masked and ctx.relu and mask is not None
-                       and mask.dtype == torch.uint8)
+        hand_masked = hands_masked(ctx.link, mask, ctx.relu)  # (off the kernels the mask is a bool tensor)
         dx, dres = dx_from_message(dy, x, mask, w32, b32, sm, si, msg, count, ctx.relu,
                                    ctx.has_res and not hand_masked)
-        if w32 is None:
-            dw = None
-        elif ctx.wdtype != torch.float32:
-            dw = dw.to(ctx.wdtype)
-        if not ctx.has_bias:
-            db = None
-        elif ctx.wdtype != torch.float32:
-            db = db.to(ctx.wdtype)
-        if ctx.link is not None:
-            ctx.link.grad, dres = ((dy, mask) if hand_masked else dres), None
+        dw, db, dres = finish_bwd(dw, db, ctx.wdtype, w32 is not None, ctx.has_bias, ctx.link, dy, mask, dres,
+                                  hand_masked)
         return dx, dw, db, dres, None, None, None, None, None, None, None
 
 
