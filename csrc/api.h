@@ -403,7 +403,8 @@ void gemm_glds(const GemmProblem& g, hipStream_t stream);
 // [K/(H*W)][H][W][conv_c] with N = 9*conv_c; b_sub: row k of B = pixel (n, 2ho, 2wo) of the NHWC image
 // [.][conv_h][conv_w][ldb] for output pixel k = (n, ho, wo) of a stride-2 1x1 convolution, or with
 // conv_c > 0 the implicit im2col of a 3x3 / stride 2 / pad 1 convolution over that grid);
-// returns nothing, reduce with gemm_splitk_reduce
+// returns nothing, reduce with gemm_splitk_reduce. variant: 0/1 32-deep K-steps / 3 stages, 2 64-deep /
+// 2 stages; bit 2: plain dispatch order; bit 3: two K-groups per 8-wave workgroup (gemm_glds.hip)
 void gemm_wgrad(const void* a, const void* b, float* ws, int64_t lda, int64_t ldb, int64_t M, int64_t N, int64_t K,
                 int splits, int conv_h, int conv_w, int conv_c, hipStream_t stream, int variant = 0, int b_sub = 0);
 // out_i[ci][t][co] = in_i[co][taps-1-t][ci] (bf16) for every filter i, one launch per 40 filters:

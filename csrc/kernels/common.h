@@ -259,3 +259,18 @@ inline int resident_blocks(const void* kernel, int threads, size_t smem) {
     if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") +        \
                                                    hipGetErrorString(_e) + " at " #expr); \
   } while (0)
+
+// Raise a kernel's dynamic-LDS limit (above the 64 KiB default) once per (kernel, size, device):
+// the attribute belongs to the device's copy of the function, so a process-wide "done" flag
+// would leave the launch on a second device failing.
+inline void allow_dynamic_lds(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::map<std::tuple<const void*, int, int>, bool> done;
+  int dev = 0;
+  FLUXMPI_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  bool& d = done[std::make_tuple(kernel, bytes, dev)];
+  if (d) return;
+  FLUXMPI_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  d = true;
+}

@@ -580,7 +580,7 @@ struct TrLoader {
 
   __device__ __forceinline__ void init(const bf16* __restrict__ g, int64_t ld, int64_t cols, int64_t c0, int64_t kbeg,
                                        int H, int W, int C) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = (threadIdx.x >> 6) & 3, lane = threadIdx.x & 63;  // the wave within its group of 4
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       const int row = (wave * PPW + j) * RPP + lane / SPR;
@@ -616,7 +616,7 @@ struct TrLoader {
   // issue this wave's pieces of the current step into lds_tile, then advance one step
   __device__ __forceinline__ void issue_next(bf16* lds_tile, int kend, int64_t ld, int H, int W, int C, int dh_step,
                                              int dw_step, int dimg_step = 0) {
-    const int wave = threadIdx.x >> 6;
+    const int wave = (threadIdx.x >> 6) & 3;
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       const void* src = g_zero_line;
@@ -688,13 +688,29 @@ __device__ __forceinline__ bf16x8 read_frag_tr(const bf16* __restrict__ tile, in
   return out;
 }
 
-template <int BM, int BN, int kBK, int kStages, int BMODE>
-__global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_kernel(WgradArgs p) {
+// the rings of the K-group form (dynamic: two groups' rings exceed the static 64 KiB)
+extern __shared__ __attribute__((aligned(16))) unsigned char wgrad_kg_smem[];
+
+// KG (K-groups): one workgroup of 8 waves per CU instead of two of 4. The two 4-wave groups each
+// run the 2 x 2 wave grid over the SAME output tile and one half of the workgroup's K range
+// (split at a multiple of kBK), each through a ring of its own, so the CU keeps 2 x (kStages - 1)
+// tiles in flight; group 1 then hands its accumulators to group 0 through the idle ring and
+// group 0 stores the one slab: the on-chip half of the split-K sum, in a fixed order.
+template <int BM, int BN, int kBK, int kStages, int BMODE, bool KG = false>
+__global__ __launch_bounds__(KG ? 2 * kThreads : kThreads, KG ? 1 : 2) void gemm_wgrad_kernel(WgradArgs p) {
   constexpr bool CONVB = BMODE == 1;  // (BMODE 2 / 3: stride-2 gathers over the output grid)
   constexpr int WM = BM / 2, WN = BN / 2, FM = WM / 16, FN = WN / 16;
   constexpr int A_ELEMS = BM * kBK, B_ELEMS = BN * kBK;
   constexpr int LPT = (BM + BN) * kBK / 2048;
-  __shared__ __attribute__((aligned(16))) bf16 smem[kStages * (A_ELEMS + B_ELEMS)];
+  constexpr int kRing = kStages * (A_ELEMS + B_ELEMS);
+  const int group = KG ? static_cast<int>(threadIdx.x >> 8) : 0;
+  bf16* smem;
+  if constexpr (KG) {
+    smem = reinterpret_cast<bf16*>(wgrad_kg_smem) + group * kRing;
+  } else {
+    __shared__ __attribute__((aligned(16))) bf16 ring[kRing];
+    smem = ring;
+  }
   auto sa = [&](int s) { return smem + s * A_ELEMS; };
   auto sb = [&](int s) { return smem + kStages * A_ELEMS + s * B_ELEMS; };
   // 1-D grid over (split, tile), XCD-aware and bijective over the whole grid: each XCD gets a
@@ -710,9 +726,19 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_kernel(WgradArgs p) {
   const int split = lid / nt, bid = lid - split * nt;
   const int tm = bid / p.tiles_n, tn = bid % p.tiles_n;
   const int64_t m0 = static_cast<int64_t>(tm) * BM, n0 = static_cast<int64_t>(tn) * BN;
-  const int64_t kbeg = static_cast<int64_t>(split) * p.k_per_split;
-  const int64_t kend = kbeg + p.k_per_split < p.K ? kbeg + p.k_per_split : p.K;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int64_t kbeg = static_cast<int64_t>(split) * p.k_per_split;
+  int64_t kend = kbeg + p.k_per_split < p.K ? kbeg + p.k_per_split : p.K;
+  int nk = kend > kbeg ? static_cast<int>((kend - kbeg + kBK - 1) / kBK) : 0;
+  if (KG) {
+    // group 0: the first ceil(nk / 2) steps, group 1: the rest. Both run the same number of
+    // steps (the barriers are workgroup-wide); group 1's missing last step, or its whole range
+    // when nk == 1, lies at k >= kend, where the loaders read zeros.
+    nk = (nk + 1) / 2;
+    const int64_t kmid = kbeg + static_cast<int64_t>(nk) * kBK;
+    if (group == 0) kend = kmid < kend ? kmid : kend;
+    else kbeg = kmid;
+  }
+  const int wave = (threadIdx.x >> 6) & 3, lane = threadIdx.x & 63;
   const int wm = wave >> 1, wn = wave & 1;
   TrLoader<BM, kBK, 0> la;
   TrLoader<BN, kBK, BMODE> lb;
@@ -734,7 +760,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_kernel(WgradArgs p) {
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = kend > kbeg ? static_cast<int>((kend - kbeg + kBK - 1) / kBK) : 0;
 #pragma unroll
   for (int s = 0; s < kStages - 1; ++s)
     if (s < nk) issue(s);
@@ -759,6 +784,26 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_kernel(WgradArgs p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
     }
   }
+  if constexpr (KG) {
+    // every DMA has landed (the last step waited for vmcnt(0) before its barrier); once every wave
+    // is past its last fragment reads, group 1's accumulators go through group 0's ring, one
+    // 16-B slot per lane and fragment (lane-linear: conflict-free), and group 0 adds them
+    f32x4* xch = reinterpret_cast<f32x4*>(wgrad_kg_smem);
+    const int slot = threadIdx.x & (kThreads - 1);
+    __syncthreads();
+    if (group == 1) {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) xch[(i * FN + j) * kThreads + slot] = acc[i][j];
+    }
+    __syncthreads();
+    if (group == 1) return;
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[i][j] += xch[(i * FN + j) * kThreads + slot];
+  }
   // fp32 partial of this split: acc[i][j][r] is (row wm*WM + i*16 + 4*(lane>>4) + r, col wn*WN + j*16 + lane&15)
   float* c = p.c + static_cast<int64_t>(split) * p.M * p.N;
   const int col_in = lane & 15, rq = 4 * (lane >> 4);
@@ -773,6 +818,27 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wgrad_kernel(WgradArgs p) {
         if (m < p.M && n < p.N) c[m * p.N + n] = acc[i][j][r];
       }
     }
+}
+
+template <int BM, int BN, int BK, int ST, int BMODE, bool KG>
+void launch_wgrad(const WgradArgs& w, unsigned grid, hipStream_t s) {
+  if constexpr (KG) {
+    constexpr int kSmem = 2 * ST * (BM + BN) * BK * static_cast<int>(sizeof(bf16));  // both groups' rings
+    static_assert(kSmem <= 160 * 1024, "LDS of a CU");
+    allow_dynamic_lds(reinterpret_cast<const void*>(&gemm_wgrad_kernel<BM, BN, BK, ST, BMODE, true>), kSmem);
+    gemm_wgrad_kernel<BM, BN, BK, ST, BMODE, true><<<grid, 2 * kThreads, kSmem, s>>>(w);
+  } else {
+    gemm_wgrad_kernel<BM, BN, BK, ST, BMODE><<<grid, kThreads, 0, s>>>(w);
+  }
+}
+
+// bmode: the kernel's BMODE (0 plain, 1 implicit 3x3, 2 stride-2 1x1 gather, 3 stride-2 3x3)
+template <int BM, int BN, int BK, int ST, bool KG>
+void launch_wgrad_mode(const WgradArgs& w, unsigned grid, int bmode, hipStream_t s) {
+  if (bmode == 3) launch_wgrad<BM, BN, BK, ST, 3, KG>(w, grid, s);
+  else if (bmode == 2) launch_wgrad<BM, BN, BK, ST, 2, KG>(w, grid, s);
+  else if (bmode == 1) launch_wgrad<BM, BN, BK, ST, 1, KG>(w, grid, s);
+  else launch_wgrad<BM, BN, BK, ST, 0, KG>(w, grid, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -978,31 +1044,28 @@ void gemm_wgrad(const void* a, const void* b, float* ws, int64_t lda, int64_t ld
   w.b = static_cast<const bf16*>(b);
   w.c = ws;
   w.lda = lda; w.ldb = ldb; w.M = M; w.N = N; w.K = K;
-  // variant 0/1: 32-deep K-step, 3-stage ring; 2: 64-deep, 2 stages. Split boundaries are
-  // multiples of 64 for both (the Python side computes the same split count).
+  // variant 0/1: 32-deep K-step, 3-stage ring; 2: 64-deep, 2 stages; bit 3 (8 / 10): the K-group
+  // form of either, with 4 stages per group at 32-deep (the caller sizes splits to one workgroup
+  // per CU). Split boundaries are multiples of 64 for all (the Python side computes the same
+  // split count).
   const int64_t nk = (K + 63) / 64;
   w.k_per_split = (nk + splits - 1) / splits * 64;
   const int sp = static_cast<int>((K + w.k_per_split - 1) / w.k_per_split);
   w.conv_h = conv_h; w.conv_w = conv_w; w.conv_c = conv_c;
   w.remap = (variant & 4) ? 0 : 1;  // bit 2 of variant: plain dispatch order (A/B experiments)
+  const bool kgroups = (variant & 8) != 0;
   variant &= 3;
+  const int bmode = b_sub ? (conv_c > 0 ? 3 : 2) : (conv_h > 0 ? 1 : 0);
   const bool m128 = M > 64, n128 = N > 64;
 #define WG(BM, BN)                                                                                      \
   {                                                                                                     \
     w.tiles_m = static_cast<int>((M + BM - 1) / BM);                                                   \
     w.tiles_n = static_cast<int>((N + BN - 1) / BN);                                                   \
-    dim3 grid(w.tiles_m * w.tiles_n * sp);                                                              \
-    if (variant == 2) {                                                                                 \
-      if (b_sub && conv_c > 0) gemm_wgrad_kernel<BM, BN, 64, 2, 3><<<grid, kThreads, 0, stream>>>(w);   \
-      else if (b_sub) gemm_wgrad_kernel<BM, BN, 64, 2, 2><<<grid, kThreads, 0, stream>>>(w);            \
-      else if (conv_h > 0) gemm_wgrad_kernel<BM, BN, 64, 2, 1><<<grid, kThreads, 0, stream>>>(w);       \
-      else gemm_wgrad_kernel<BM, BN, 64, 2, 0><<<grid, kThreads, 0, stream>>>(w);                       \
-    } else {                                                                                            \
-      if (b_sub && conv_c > 0) gemm_wgrad_kernel<BM, BN, 32, 3, 3><<<grid, kThreads, 0, stream>>>(w);   \
-      else if (b_sub) gemm_wgrad_kernel<BM, BN, 32, 3, 2><<<grid, kThreads, 0, stream>>>(w);            \
-      else if (conv_h > 0) gemm_wgrad_kernel<BM, BN, 32, 3, 1><<<grid, kThreads, 0, stream>>>(w);       \
-      else gemm_wgrad_kernel<BM, BN, 32, 3, 0><<<grid, kThreads, 0, stream>>>(w);                       \
-    }                                                                                                   \
+    const unsigned grid = static_cast<unsigned>(w.tiles_m * w.tiles_n * sp);                            \
+    if (kgroups && variant == 2) launch_wgrad_mode<BM, BN, 64, 2, true>(w, grid, bmode, stream);        \
+    else if (kgroups) launch_wgrad_mode<BM, BN, 32, 4, true>(w, grid, bmode, stream);                   \
+    else if (variant == 2) launch_wgrad_mode<BM, BN, 64, 2, false>(w, grid, bmode, stream);             \
+    else launch_wgrad_mode<BM, BN, 32, 3, false>(w, grid, bmode, stream);                               \
   }
   if (m128 && n128) WG(128, 128)
   else if (m128) WG(128, 64)

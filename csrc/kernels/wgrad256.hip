@@ -508,16 +508,12 @@ void gemm_wgrad256(const void* a, const void* b, float* ws, int64_t lda, int64_t
   const int64_t grid = static_cast<int64_t>(s) * p.tiles_m * p.tiles_n;
   if (grid > 0x7fffffff) throw std::runtime_error("gemm_wgrad256: grid too large");
   constexpr int kSmem = 128 * 1024;  // both variants: 4 x 32 KiB / 2 x 64 KiB
-  static bool attr[5] = {false, false, false, false, false};
-  const void* fn = v == 1   ? reinterpret_cast<const void*>(&wgrad256_kernel<64, 2>)
+  const void* fn = v == 1   ?reinterpret_cast<const void*>(&wgrad256_kernel<64, 2>)
                    : v == 2 ? reinterpret_cast<const void*>(&wgrad256_kernel<32, 4, true>)
                    : v == 3 ? reinterpret_cast<const void*>(&wgrad256h_kernel<32, 4>)
                    : v == 4 ? reinterpret_cast<const void*>(&wgrad256pp_kernel)
                             : reinterpret_cast<const void*>(&wgrad256_kernel<32, 4>);
-  if (!attr[v]) {
-    FLUXMPI_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
-    attr[v] = true;
-  }
+  allow_dynamic_lds(fn, kSmem);
   if (v == 1) wgrad256_kernel<64, 2><<<static_cast<unsigned>(grid), kThreads, kSmem, stream>>>(p);
   else if (v == 2) wgrad256_kernel<32, 4, true><<<static_cast<unsigned>(grid), kThreads, kSmem, stream>>>(p);
   else if (v == 3) wgrad256h_kernel<32, 4><<<static_cast<unsigned>(grid), kThreads, kSmem, stream>>>(p);

@@ -34,8 +34,9 @@ from . import graddst
 WGRAD = "auto"
 # our 3x3 forward tile configurations: 0: auto (128x128 tiles); 8 / 7: 256x128 tiles, 64- / 32-deep K-steps
 FWD_ENGINES = (0, 8, 7)
-# our weight-gradient kernel configurations tried by the autotune: (variant, target workgroups); s44 sweep
-_WG_CONFIGS = ((2, 512), (2, 768), (2, 1024), (2, 384))
+# our weight-gradient kernel configurations tried by the autotune: (variant, target workgroups); s44 sweep.
+# (8, 256) / (10, 256): the K-group variants (32-deep / 4 stages, 64-deep / 2) at one workgroup per CU
+_WG_CONFIGS = ((2, 512), (2, 768), (2, 1024), (2, 384), (8, 256), (10, 256))
 # the narrow 3x3 weight-gradient kernel (wgrad3x3n.hip) configurations: (variant, target workgroups);
 # variant bit 0: 8 waves (else 4), bit 1 (4 waves only): the next two blocks in flight (else one)
 _W3N_CONFIGS = ((1, 256), (2, 256), (0, 256), (1, 512))

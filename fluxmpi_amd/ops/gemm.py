@@ -359,9 +359,11 @@ WGRAD_TARGET_WG = 768
 
 def _wgrad_splits_v2(M: int, N: int, K: int) -> int:
     """Split-K factor: ~WGRAD_TARGET_WG workgroups, >= 256 pixels per split, and at most 64 MiB
-    of fp32 partials (each is written once and read once by the reduce)."""
+    of fp32 partials (each is written once and read once by the reduce). The K-group variants
+    (``WGRAD_VARIANT & 8``: one 8-wave workgroup per CU) take the floor, at most
+    WGRAD_TARGET_WG workgroups: one round of the chip and never a partial second one."""
     tiles = max(1, -(-M // 128)) * max(1, -(-N // 128))
-    s_occ = -(-WGRAD_TARGET_WG // tiles)
+    s_occ = WGRAD_TARGET_WG // tiles if WGRAD_VARIANT & 8 else -(-WGRAD_TARGET_WG // tiles)
     s_bytes = max(1, (64 << 20) // (M * N * 4))
     return int(max(1, min(s_occ, s_bytes, K // 256)))
 
@@ -379,7 +381,9 @@ def _actual_splits_v2(K: int, splits: int) -> int:
     return -(-K // kps)
 
 
-# weight-gradient kernel variant: 1 = 32-deep K-step / 3 stages, 2 = 64-deep / 2 stages
+# weight-gradient kernel variant: 1 = 32-deep K-step / 3 stages, 2 = 64-deep / 2 stages,
+# 8 / 10 = two K-groups of 4 waves per workgroup (one workgroup per CU), 32-deep / 4 stages or
+# 64-deep / 2 stages each
 WGRAD_VARIANT = 1
 # 1 (default): XCD-aware (split, tile) block order in the weight-gradient grid; 0: dispatch order
 WGRAD_REMAP = True
