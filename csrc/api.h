@@ -176,6 +176,38 @@ void mt_ema(const std::vector<uintptr_t>& ema, const std::vector<uintptr_t>& src
 // min(decay, (1 + n) / (10 + n)) : decay, omd = 1 - d_t.
 void ema_advance(void* block, float decay, int warmup, int every, const int32_t* dev_skip, hipStream_t stream);
 
+// ---- device input pipeline (augment.hip): crop, flip, normalise, mixup / cutmix in one pass ----
+// out [B][h][w][C] (bf16 / fp16, C in {3, 4}, channel 3 = +0, 16-byte-aligned base) from the dense
+// u8 batch in [B][H][W][3] (any byte alignment). Sample b draws one Philox4x32-10 call, key (seed lo,
+// seed hi), counter (s lo, s hi, stream, step), s = sample_offset + b: ox = (w0 * rx) >> 32, oy =
+// (w1 * ry) >> 32, flip = w2 & 1, rx = W + 2 pad - w + 1, ry likewise (crop_center: ox = (rx - 1) / 2,
+// oy = (ry - 1) / 2, no draw; flip == 0: never flipped). Output pixel (i, j) reads source row
+// i + oy - pad, column (flip ? w - 1 - j : j) + ox - pad; outside the image the byte is `fill`.
+// y = float(u) * a[c] + b[c], the product and the sum rounded separately. The partner of sample b is
+// B - 1 - b, its pixel its own crop and flip at the same (i, j): mode 0 z = y; mode 1 (mixup)
+// z = y_p + lam * (y - y_p), each operation rounded; mode 2 (cutmix) z = y_p for y0 <= i < y1,
+// x0 <= j < x1, else y. The store is the round-to-nearest cast of z.
+struct AugHyper {
+  uint64_t seed;           // the Philox key
+  uint32_t stream;         // caller-chosen id below 2^30
+  uint32_t step;           // read when dev_block is null
+  int64_t sample_offset;   // index of sample 0 of this batch in the random stream (>= 0)
+  int mode;                // 0 none, 1 mixup, 2 cutmix (dev_block null)
+  int y0, x0, y1, x1;      // the cutmix box in the output (dev_block null)
+  float lam;               // mixup weight of the sample itself (dev_block null)
+  int pad, fill;           // zero-extension of the image on every side; the byte it is made of
+  int crop_center, flip;   // centre crop (no draw); flips enabled
+  float a[3], b[3];        // fp32(1 / (255 std_c)), fp32(-mean_c / std_c)
+  // optional device block, 8 words {step, mode, y0, x0, y1, x1, lam bits, 0} (aug_block_set): read
+  // wave-uniformly in place of those six, so that a captured launch follows the block
+  const uint32_t* dev_block = nullptr;
+};
+void augment_batch(const void* in, void* out, int64_t B, int H, int W, int h, int w, int C, int dtype,
+                   const AugHyper& a, hipStream_t stream);
+// One thread fills the block with plain stores.
+void aug_block_set(void* block, uint32_t step, int mode, int y0, int x0, int y1, int x1, float lam,
+                   hipStream_t stream);
+
 // ---- BatchNorm (NHWC, channels innermost) + ReLU / residual-add fusions ----------
 // Training forward: per-channel batch statistics over rows = N*H*W, then
 //   y = act(x * scale_c + shift_c [+ residual]).

@@ -181,6 +181,32 @@ PYBIND11_MODULE(_C_c3ds, m) {
         py::arg("slabs"), py::arg("stream"));
 }
 
+// The device input pipeline (augment.hip): a fifth module, loaded by fluxmpi_amd.ops._ext.aug(). The
+// arguments of AugHyper travel as keywords; `dev_block` (or 0) is the device block of aug_block_set.
+PYBIND11_MODULE(_C_aug, m) {
+  m.doc() = "fluxmpi_amd native library: crop, flip, normalise, mixup / cutmix of a uint8 batch in one pass";
+  m.def(
+      "augment_batch",
+      [](uintptr_t in, uintptr_t out, int64_t B, int H, int W, int h, int w, int C, int dtype, uint64_t seed,
+         uint32_t aug_stream, uint32_t step, int64_t sample_offset, int mode, std::array<int, 4> box, float lam, int pad,
+         int fill, int crop_center, int flip, std::array<float, 3> a, std::array<float, 3> b, uintptr_t dev_block,
+         uintptr_t stream) {
+        AugHyper hy{seed, aug_stream, step, sample_offset, mode, box[0], box[1], box[2], box[3], lam, pad, fill,
+                    crop_center, flip, {a[0], a[1], a[2]}, {b[0], b[1], b[2]}, ptr<const uint32_t*>(dev_block)};
+        augment_batch(ptr<const void*>(in), ptr<void*>(out), B, H, W, h, w, C, dtype, hy, ptr<hipStream_t>(stream));
+      },
+      py::arg("input"), py::arg("out"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("h"), py::arg("w"),
+      py::arg("C"), py::arg("dtype"), py::arg("seed"), py::arg("aug_stream"), py::arg("step"),
+      py::arg("sample_offset"), py::arg("mode"), py::arg("box"), py::arg("lam"), py::arg("pad"), py::arg("fill"),
+      py::arg("crop_center"), py::arg("flip"), py::arg("a"), py::arg("b"), py::arg("dev_block"), py::arg("stream"));
+  m.def(
+      "aug_block_set",
+      [](uintptr_t block, uint32_t step, int mode, std::array<int, 4> box, float lam, uintptr_t stream) {
+        aug_block_set(ptr<void*>(block), step, mode, box[0], box[1], box[2], box[3], lam, ptr<hipStream_t>(stream));
+      },
+      py::arg("block"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"), py::arg("stream"));
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
 

@@ -1,0 +1,83 @@
+"""Training from a uint8 image set: a rank's shard of the bytes goes through the device input pipeline
+(random crop, flip, normalise, NHWC bf16, the stem's 4-channel format, mixup with soft targets) in one
+kernel per batch, then through ResNet under the DDP engine.
+
+Run:  torchrun --nproc-per-node 8 examples/train_augment.py --model resnet50 --batch 256 --steps 100
+      python -m fluxmpi_amd.launch -n 2 examples/train_augment.py --model resnet_tiny --batch 8 --image 32 (CPU)
+
+The image set here is random bytes (what a decoded, resized data set looks like in memory); decoding
+and host loading are not this example's subject.
+"""
+import argparse
+import time
+
+import torch
+import torch.nn.functional as F
+
+import fluxmpi_amd as FluxMPI
+from fluxmpi_amd import optimisers as O
+from fluxmpi_amd.models import build_model
+from fluxmpi_amd.parallel.ddp import DDP
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--model", default="resnet50")
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--image", type=int, default=224, help="the crop fed to the model; the stored images are 8/7 of it")
+ap.add_argument("--steps", type=int, default=20)
+ap.add_argument("--items", type=int, default=None, help="images in the whole set (default: 4 batches per rank)")
+ap.add_argument("--mixup", type=float, default=0.2)
+ap.add_argument("--cutmix", type=float, default=0.0)
+ap.add_argument("--smoothing", type=float, default=0.1)
+args = ap.parse_args()
+
+FluxMPI.Init()
+dev = FluxMPI.device()
+classes = 10 if args.model == "resnet_tiny" else 1000
+kw = {"norm": "fused"} if args.model.startswith("resnet") and dev.type == "cuda" else {}
+model = build_model(args.model, **kw).to(dev)
+if dev.type == "cuda":
+    model = model.to(memory_format=torch.channels_last)
+    for m in model.modules():
+        if not isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            for p in m.parameters(recurse=False):
+                p.data = p.data.bfloat16()
+ddp = DDP(model, O.AdamW(1e-3, decay=1e-4), average=True)
+
+# the whole set, the same on every rank; each rank keeps its contiguous shard of images and labels
+stored = args.image * 8 // 7
+items = args.items or 4 * args.batch * FluxMPI.total_workers()
+g = torch.Generator().manual_seed(0)
+images = torch.randint(0, 256, (items, stored, stored, 3), dtype=torch.uint8, generator=g)
+labels = torch.randint(0, classes, (items,), generator=g)
+shard_x = FluxMPI.DistributedDataContainer(images)
+shard_y = FluxMPI.DistributedDataContainer(labels)
+per_epoch = max(1, len(shard_x) // args.batch)
+
+# channels=4: the ResNet stem's own input format, so the stem runs no pad pass; every rank draws
+# different crops from the one seed (sample_offset = local_rank * batch)
+aug = FluxMPI.DeviceAugment(args.image, channels=4 if dev.type == "cuda" else 3,
+                            dtype=torch.bfloat16, seed=0, mixup_alpha=args.mixup, cutmix_alpha=args.cutmix,
+                            label_smoothing=args.smoothing, num_classes=classes)
+
+t0 = time.time()
+for step in range(args.steps):
+    lo = (step % per_epoch) * args.batch
+    u8 = shard_x[lo:lo + args.batch].to(dev, non_blocking=True)  # the bytes: 1/4 of the bf16 batch
+    y = shard_y[lo:lo + args.batch].to(dev, non_blocking=True)
+    x, soft = aug(u8, y)  # [B, C, h, w] channels_last, [B, classes] fp32
+    if dev.type != "cuda":
+        x = x.float()
+    loss = F.cross_entropy(ddp(x).float(), soft)
+    loss.backward()
+    ddp.step()
+    if step % 10 == 0:
+        FluxMPI.fluxmpi_println(f"step {step} loss {loss.item():.4f} (mix {aug.draw(step)})")
+
+model.eval()
+with torch.no_grad():  # evaluation: the centre crop, no flip, no mix
+    x, y = aug.eval()(shard_x[0:args.batch].to(dev), shard_y[0:args.batch].to(dev))
+    acc = (ddp(x if dev.type == "cuda" else x.float()).argmax(1) == y).float().mean().item()
+FluxMPI.fluxmpi_println(f"centre-crop accuracy on a training batch {acc:.3f}")
+if FluxMPI.local_rank() == 0:
+    print(f"{args.steps * args.batch * FluxMPI.total_workers() / (time.time() - t0):.1f} samples/s")
+FluxMPI.Finalize()

@@ -31,6 +31,7 @@ from .parallel import (COMM_WORLD, Barrier, DistributedDataContainer, Distribute
                        synchronize, total_workers)
 from .parallel.ddp import EMA, LossScale  # noqa: F401
 from .ops.syncbn import SyncBatchNorm2d, convert_sync_batchnorm, sync_batch_norm  # noqa: F401
+from .ops.augment import DeviceAugment  # noqa: F401
 from .utils.config import disable_cudampi_support  # noqa: F401
 from .utils.errors import FluxMPINotInitializedError  # noqa: F401
 
@@ -58,5 +59,5 @@ __all__ = [
     "FluxMPIFluxModel", "FlatParams", "allreduce", "bcast", "reduce", "Iallreduce", "Ibcast", "Wait", "Waitall",
     "allgather", "reduce_scatter", "COMM_WORLD", "ReduceOp", "disable_cudampi_support",
     "FluxMPINotInitializedError", "optimisers", "build", "barrier", "Barrier", "device", "backend_name",
-    "SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm", "LossScale", "EMA",
+    "SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm", "LossScale", "EMA", "DeviceAugment",
 ]

@@ -233,6 +233,12 @@ class Bottleneck(nn.Module):
         return F.relu(out + identity)
 
 
+def _rgb(x, w):
+    """The first three channels of a 4-channel batch (the stem's padded input format) for a path that
+    runs the 3-channel filter ``w``; any other input as it is."""
+    return x[:, :3] if x.dim() == 4 and x.shape[1] == 4 and w.shape[1] == 3 else x
+
+
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, conv_impl="gemm", norm="torch", zero_init_residual=False):
         super().__init__()
@@ -264,13 +270,17 @@ class ResNet(nn.Module):
         """7x7/2 stem. On the GPU the 3 input channels are zero-padded to 4 (image and
         filter; same math, and the filter's gradient is the slice of the padded one):
         MIOpen's NHWC kernels for C=4 run the forward 1.3x and the weight gradient 1.4x
-        faster than for C=3 on MI355X (scripts/bench_stem.py), for one ~30 us pad pass."""
+        faster than for C=3 on MI355X (scripts/bench_stem.py), for one ~30 us pad pass. A batch that
+        already has the zero fourth channel (ops.augment, channels=4) needs no pad pass; where the
+        3-channel filter runs, its first three channels are taken."""
         w = self.conv1.weight
-        if not (x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and w.shape[1] == 3
+        if not (x.is_cuda and x.dim() == 4 and x.shape[1] in (3, 4) and w.shape[1] == 3
                 and self.conv_impl in ("hybrid", "fused")):
-            return self.conv1(x)
+            return self.conv1(_rgb(x, w))
         w4 = F.pad(w, (0, 0, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last)
-        if (not x.requires_grad and x.dtype in (torch.bfloat16, torch.float16)
+        if x.shape[1] == 4:
+            x4 = x
+        elif (not x.requires_grad and x.dtype in (torch.bfloat16, torch.float16)
                 and x.permute(0, 2, 3, 1).is_contiguous() and x.data_ptr() % 16 == 0):
             from ..ops.pool import pad_c3_to_c4
             x4 = pad_c3_to_c4(x)  # one HIP pass (6 B read, 8 B written per pixel)
@@ -313,9 +323,9 @@ class ResNet(nn.Module):
                 x = self.maxpool(self.bn1(c, relu=True))
         elif self.norm_kind == "sync":
             # the fused stem / pool kernels carry statistics of their own (local to the rank)
-            x = self.maxpool(self.bn1(self.conv1(x), relu=True))
+            x = self.maxpool(self.bn1(self.conv1(_rgb(x, self.conv1.weight)), relu=True))
         else:
-            x = self.maxpool(F.relu(self.bn1(self.conv1(x))))
+            x = self.maxpool(F.relu(self.bn1(self.conv1(_rgb(x, self.conv1.weight)))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(global_avg_pool(x))
 

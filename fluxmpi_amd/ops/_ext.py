@@ -121,6 +121,12 @@ def c3ds():
     return _extra("_C_c3ds", "the downsample-block backward entry")
 
 
+def aug():
+    """The ``_C_aug`` module: ``augment_batch`` and ``aug_block_set`` (the device input pipeline,
+    ``csrc/kernels/augment.hip``)."""
+    return _extra("_C_aug", "the input-pipeline entries")
+
+
 def require_for(t: torch.Tensor):
     """The extension if ``t`` lives on the GPU (mandatory there), else ``None``."""
     if t.is_cuda:

@@ -3,7 +3,8 @@
 ``stem(x, conv_weight, bn)`` == ``max_pool2d(relu(bn(conv2d(x, w, stride=2, padding=3))), 3, 2, 1)``
 for 224x224 bf16 NHWC images in training mode (``csrc/kernels/stem.hip``):
 
-* forward: the input channels are zero-padded 3 -> 4 (one pass), the convolution runs as an
+* forward: the input channels are zero-padded 3 -> 4 (one pass; none when the batch already has the
+  zero fourth channel, as ``ops.augment`` writes it), the convolution runs as an
   implicit GEMM over LDS image halos (no im2col) with the BatchNorm statistics reduced in its
   epilogue, then the fused BN + ReLU + max-pool of :mod:`.pool`;
 * backward: ONE pass computes the pool-gradient gather, the BatchNorm backward sums and the
@@ -125,7 +126,7 @@ def emulate_conv(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 def supported(x: torch.Tensor, weight: torch.Tensor, conv, bn) -> bool:
     return (x.is_cuda and not x.requires_grad and x.dtype == torch.bfloat16 and x.dim() == 4
-            and tuple(x.shape[1:]) == (3, 224, 224) and x.permute(0, 2, 3, 1).is_contiguous()
+            and tuple(x.shape[1:]) in ((3, 224, 224), (4, 224, 224)) and x.permute(0, 2, 3, 1).is_contiguous()
             and x.data_ptr() % 16 == 0 and tuple(weight.shape) == (CO, 3, 7, 7)
             and tuple(conv.stride) == (2, 2) and tuple(conv.padding) == (3, 3) and conv.bias is None
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and bn.training
@@ -192,11 +193,13 @@ class _StemFn(torch.autograd.Function):
 
 
 def stem(x: torch.Tensor, conv, bn) -> torch.Tensor:
-    """``max_pool2d(relu(bn(conv(x))), 3, 2, 1)`` on the stem kernels (see :func:`supported`)."""
+    """``max_pool2d(relu(bn(conv(x))), 3, 2, 1)`` on the stem kernels (see :func:`supported`). A
+    4-channel ``x`` (channel 3 zero: what ``ops.augment`` writes with ``channels=4``) is the kernels'
+    own input format and skips the pad pass."""
     from .batchnorm import bn_counter
     from .pool import pad_c3_to_c4
     mom, nbt = bn_counter(bn)
-    x4 = pad_c3_to_c4(x).permute(0, 2, 3, 1)
+    x4 = (x if x.shape[1] == 4 else pad_c3_to_c4(x)).permute(0, 2, 3, 1)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
     return _StemFn.apply(x4, conv.weight, bn.weight, bn.bias, rm, rv, mom, bn.eps, nbt)
