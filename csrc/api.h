@@ -426,6 +426,16 @@ void conv3ds_bwd(const void* dy, const uint8_t* relu_mask, const void* c3, const
                  const float* w2, const float* save_mean2, const float* save_invstd2, const float* sum_dy2,
                  const float* sum_dy_xhat2, const void* a2, const void* x, const void* wt3, const void* wtds,
                  void* d_a2, void* d_xside, float* ws3, float* wsds, int64_t P, int slabs, hipStream_t stream);
+// bn_relu_conv1x1_fwd.hip: bn2 apply + ReLU + the 1x1 expansion convolution of a bottleneck in one
+// streaming kernel, (Cin, Cout) = (64, 256) or (128, 512), bf16 NHWC. Reads c2 [P][Cin] once, writes
+// a2 = relu(fmaf(c2, scale, shift)) [P][Cin] (bit for bit what bn_apply stores from the same
+// statistics; scale / shift [Cin] fp32 as bn_stats_finalize produces them) and c3 = a2 . W^T
+// [P][Cout] (wt = the filter [Cout][Cin] as stored), and adds the per-channel sum and sum of squares
+// of the rounded c3 into stats [64][2][Cout] (one atomic per column, moment and workgroup). Every
+// pointer 16-byte aligned; the grid is one resident round, at most one workgroup per 32-pixel tile.
+bool bn_relu_conv1x1_fwd_supported(int Cin, int Cout);
+void bn_relu_conv1x1_fwd(const void* c2, const float* scale, const float* shift, const void* wt, void* a2, void* c3,
+                         float* stats, int64_t P, int Cin, int Cout, hipStream_t stream);
 // the LDS-DMA pipelined kernel: K-major A (or implicit conv) and B, modes 0/1, optional residual,
 // no prologue affine / split-K / BN-backward epilogue
 bool gemm_glds_supported(const GemmProblem& g);

@@ -181,6 +181,16 @@ PYBIND11_MODULE(_C_c3ds, m) {
         py::arg("slabs"), py::arg("stream"));
 }
 
+// bn2 apply + ReLU + conv3 forward in one kernel (bn_relu_conv1x1_fwd.hip): a module of its own, loaded by
+// fluxmpi_amd.ops._ext.bn2c3().
+PYBIND11_MODULE(_C_bn2c3, m) {
+  m.doc() = "fluxmpi_amd native library: BatchNorm apply + ReLU + 1x1 expansion convolution forward";
+  m.def("bn_relu_conv1x1_fwd_supported", &bn_relu_conv1x1_fwd_supported, py::arg("Cin"), py::arg("Cout"));
+  m.def("bn_relu_conv1x1_fwd", raw(&bn_relu_conv1x1_fwd), py::arg("c2"), py::arg("scale"), py::arg("shift"),
+        py::arg("wt"), py::arg("a2"), py::arg("c3"), py::arg("stats"), py::arg("P"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("stream"));
+}
+
 // The device input pipeline (augment.hip): a fifth module, loaded by fluxmpi_amd.ops._ext.aug(). The
 // arguments of AugHyper travel as keywords; `dev_block` (or 0) is the device block of aug_block_set.
 PYBIND11_MODULE(_C_aug, m) {

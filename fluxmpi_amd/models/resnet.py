@@ -184,29 +184,35 @@ class Bottleneck(nn.Module):
                 else:
                     identity = self.downsample(x)
                 if self.hybrid:
+                    c2 = None
                     if fb.conv3x3_supported(a1, self.conv2):
                         # implicit-GEMM conv2 (input gradient always; forward where measured faster,
                         # then bn2's statistics come from its epilogue)
                         ours = fb.conv3x3_forward_is_ours(a1, self.conv2.weight)
                         c2 = fb.conv3x3(a1, self.conv2.weight, with_stats=True)
-                        a2 = fb.bn_from_stats(c2, self.bn2, relu=True, stats_ready=ours)
                     elif fb.conv3x3_s2_supported(a1, self.conv2):
                         # stride-2 conv2: forward where measured faster on our implicit GEMM (+ bn2's
                         # sums from its epilogue), weight gradient autotuned (fused_block._Conv3x3S2)
                         ours = fb.conv3x3_s2_forward_is_ours(a1, self.conv2.weight)
                         c2 = fb.conv3x3_s2(a1, self.conv2.weight, with_stats=ours)
-                        a2 = fb.bn_from_stats(c2, self.bn2, relu=True, stats_ready=ours)
-                    else:
+                    c3 = None
+                    if c2 is None:
                         a2 = self.bn2(self.conv2(a1), relu=True)
-                    o3 = fb.conv1x1_forward_is_ours(a2, self.conv3.weight)
+                    elif fb.bn2conv3_ok(c2, self.bn2, self.conv3):
+                        # stages 1 and 2: bn2's apply pass and conv3's forward as one streaming kernel; the
+                        # nodes below take c3 as computed and skip their forward GEMM
+                        a2, c3 = fb.bn_relu_conv3(c2, self.bn2, self.conv3, stats_ready=ours)
+                    else:
+                        a2 = fb.bn_from_stats(c2, self.bn2, relu=True, stats_ready=ours)
+                    o3 = c3 is not None or fb.conv1x1_forward_is_ours(a2, self.conv3.weight)
                     if self.downsample is None and fb.conv3bn3_ok(a2, self.conv3, self.bn3, identity, link):
                         # stage-1 identity block: conv3 -> bn3 as one node, whose backward forms bn3's
                         # input gradient in registers (one pass instead of dx + dgrad + wgrad)
-                        return fb.conv3_bn3_relu(a2, self.conv3, self.bn3, identity, link, ours_fwd=o3)
+                        return fb.conv3_bn3_relu(a2, self.conv3, self.bn3, identity, link, ours_fwd=o3, c3=c3)
                     if c3ds:
                         return fb.conv3ds_bn_relu(a2, self.conv3, self.bn3, x, ds[0], ds[1], link, ours3=o3,
-                                                  ours_ds=ds_stats)
-                    c3 = fb.conv1x1_hybrid(a2, self.conv3.weight, None, ours_stats=o3)
+                                                  ours_ds=ds_stats, c3=c3)
+                    c3 = fb.conv1x1_hybrid(a2, self.conv3.weight, None, ours_stats=o3, c=c3)
                 else:
                     c2 = fb.conv3x3(a1, self.conv2.weight) if fb.conv3x3_supported(a1, self.conv2) else self.conv2(a1)
                     c3 = fb.bn_relu_conv1x1(c2, self.bn2, self.conv3.weight)  # bn2+relu fused into the A load

@@ -121,6 +121,12 @@ def c3ds():
     return _extra("_C_c3ds", "the downsample-block backward entry")
 
 
+def bn2c3():
+    """The ``_C_bn2c3`` module: ``bn_relu_conv1x1_fwd`` (bn2 apply + ReLU + conv3 forward of a bottleneck in
+    one kernel, ``csrc/kernels/bn_relu_conv1x1_fwd.hip``)."""
+    return _extra("_C_bn2c3", "the bn2 + conv3 forward entry")
+
+
 def aug():
     """The ``_C_aug`` module: ``augment_batch`` and ``aug_block_set`` (the device input pipeline,
     ``csrc/kernels/augment.hip``)."""

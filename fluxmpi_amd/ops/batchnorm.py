@@ -228,6 +228,21 @@ def launch_apply(x, w32, b32, mean, inv, relu, residual=None):
     return y, mask
 
 
+def launch_apply_conv1x1(x, scale, shift, weight, ws=None):
+    """``(y, c)``: y = relu(x * scale + shift) (bit for bit :func:`launch_apply`'s from the same statistics;
+    ``scale`` / ``shift``: :func:`launch_finalize` with ``affine``) and c = conv1x1(y, weight), from one read
+    of ``x`` (``csrc/kernels/bn_relu_conv1x1_fwd.hip``: bf16 NHWC, 64 -> 256 or 128 -> 512 channels). The
+    per-channel sums of c are left pending in ``ws`` (default :func:`_workspace`) for the next BatchNorm."""
+    n, ch, h, w = x.shape
+    co = weight.shape[0]
+    y = torch.empty_like(x)
+    c = torch.empty(n, h, w, co, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
+    ws = _workspace(x) if ws is None else ws
+    _ext.bn2c3().bn_relu_conv1x1_fwd(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), weight.data_ptr(), y.data_ptr(),
+                                     c.data_ptr(), ws.data_ptr(), n * h * w, ch, co, stream(x))
+    return y, c
+
+
 def launch_bwd(dy, x, mask, w32, b32, mean, inv, relu, want_dres=False, stats_ready=False, params=(None, None),
                want_dx=True):
     """The fused-BN backward; returns ``(dx, dres, dw, db)``, dw / db fp32: in the bucket slices of

@@ -34,8 +34,8 @@ from . import _ext
 from . import graddst
 from ._launch import conv_backward, nhwc, stream as _stream  # noqa: F401 (_stream: imported by tests)
 from .batchnorm import (BNStatsLink, GradLink, SideGradLink, _dual_workspace, _link_workspace,  # noqa: F401 (links re-exported)
-                        _workspace, bn_counter, finish_bwd, hands_masked, launch_apply, launch_bwd, launch_bwd_dual,
-                        launch_finalize)
+                        _workspace, bn_counter, finish_bwd, hands_masked, launch_apply, launch_apply_conv1x1, launch_bwd,
+                        launch_bwd_dual, launch_finalize)
 from . import gemm as G
 from . import gemm_nt as _NT
 from . import groupnorm as _GN
@@ -189,11 +189,14 @@ class _Conv1x1Hybrid(torch.autograd.Function):
     with the block's residual gradient added in its epilogue (``link``)."""
 
     @staticmethod
-    def forward(ctx, x, weight, link=None, bnlink=None, ours_stats=False):
+    def forward(ctx, x, weight, link=None, bnlink=None, ours_stats=False, c=None):
         x = nhwc(x)
         ctx.link, ctx.bnlink = link, bnlink
         note_filter(weight)
         ctx.save_for_backward(x, weight)
+        if c is not None:
+            # already computed, its BatchNorm's sums pending in the workspace (bn_relu_conv3)
+            return c
         if ours_stats:
             # our GEMM, the next BatchNorm's statistics accumulated in its epilogue
             return _fwd1x1_stats(x, weight, _workspace(x))
@@ -207,7 +210,7 @@ class _Conv1x1Hybrid(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = wgrad_best(("1x1", tuple(x.shape), weight.shape[0]), _wgrad1x1_candidates(dc, x, weight), param=weight)
         dx = _dgrad_nhwc(_nhwc2d(dc), weight, x, ctx.link, ctx.bnlink) if ctx.needs_input_grad[0] else None
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 def _ds_fwd_ours(x, weight, stride, stats):
@@ -354,6 +357,67 @@ class _BNFromStats(torch.autograd.Function):
         return dx, dw, db, dres, None, None, None, None, None, None, None, None, None
 
 
+class _BN2Conv3(torch.autograd.Function):
+    """(a2, c3) = (relu(bn2(c2)), conv3(a2)) of a bottleneck from one read of c2: bn2's finalize, then one
+    streaming kernel (csrc/kernels/bn_relu_conv1x1_fwd.hip) instead of the apply pass and the expansion GEMM;
+    bn3's sums are left pending in the workspace as the GEMM's epilogue leaves them. a2 is bit for bit the apply
+    pass's. c3 is not differentiable here: the node that consumes it (``conv1x1_hybrid``, ``_Conv3BN3``,
+    ``_Conv3DsBN`` with ``c3`` given) skips its forward GEMM and owns conv3's backward through a2. The
+    backward is ``_BNFromStats``'s for a ReLU without residual (the mask recomputed from c2)."""
+
+    @staticmethod
+    def forward(ctx, c2, weight, bias, running_mean, running_var, momentum, eps, stats_ready, nbt, conv_weight):
+        c2 = nhwc(c2)
+        w32, b32 = weight.float(), bias.float()
+        mean, inv, scale, shift = launch_finalize(c2, w32, b32, running_mean, running_var, momentum, eps, nbt,
+                                                  stats_ready, affine=True)
+        a2, c3 = launch_apply_conv1x1(c2, scale, shift, conv_weight)
+        ctx.wdtype, ctx.params = weight.dtype, (weight, bias)
+        ctx.save_for_backward(c2, w32, b32, mean, inv)
+        ctx.mark_non_differentiable(c3)
+        # (materialised, the gradient of c3 that nobody computes is a zero fill of c3's size per backward)
+        ctx.set_materialize_grads(False)
+        return a2, c3
+
+    @staticmethod
+    def backward(ctx, dy, _):
+        if dy is None:  # a2 took no part in what is differentiated
+            return (None,) * 10
+        c2, w32, b32, mean, inv = ctx.saved_tensors
+        dx, _, dw, db = launch_bwd(nhwc(dy), c2, None, w32, b32, mean, inv, True, params=ctx.params)
+        dw, db, _ = finish_bwd(dw, db, ctx.wdtype, True, True, None, None, None, None, False)
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+# bn2's apply pass and conv3's forward GEMM as one kernel in stages 1 and 2 (FLUXMPI_BN2CONV3=0: the two
+# launches; profiles/bn2c3_bn2conv3.md)
+BN2CONV3 = os.environ.get("FLUXMPI_BN2CONV3", "1") != "0"
+
+
+def bn2conv3_ok(c2, bn, conv) -> bool:
+    """:func:`bn_relu_conv3` applies: gradients recorded, bf16 NHWC, a training-mode affine fused BatchNorm, the
+    1x1 expansion 64 -> 256 or 128 -> 512 where :func:`conv1x1_forward_is_ours` holds for the shape, and at
+    least one 32-pixel tile per workgroup of the fullest grid measured (two per compute unit): below that
+    the persistent kernel cannot fill the device and nobody has timed it against the two launches."""
+    wt = conv.weight
+    if not (BN2CONV3 and G.ENGINE != 1 and torch.is_grad_enabled() and c2.is_cuda and c2.dim() == 4
+            and c2.dtype == torch.bfloat16 and c2.is_contiguous(memory_format=torch.channels_last)
+            and wt.dtype == torch.bfloat16 and wt.is_contiguous()
+            and (c2.shape[1], tuple(wt.shape)) in ((64, (256, 64, 1, 1)), (128, (512, 128, 1, 1)))
+            and _fused_bn_training(bn)):
+        return False
+    cus = torch.cuda.get_device_properties(c2.device).multi_processor_count
+    return c2.numel() // c2.shape[1] >= 32 * 2 * cus and conv1x1_forward_is_ours(c2, wt)
+
+
+def bn_relu_conv3(c2, bn, conv, stats_ready=True):
+    """(relu(bn(c2)), conv(relu(bn(c2)))) from one read of c2 (check :func:`bn2conv3_ok`); ``stats_ready`` as for
+    :func:`bn_from_stats`. The second result goes to its consumer as ``c3=`` / ``c=``."""
+    mom, nbt = bn_counter(bn)
+    return _BN2Conv3.apply(c2, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, stats_ready, nbt,
+                           conv.weight)
+
+
 class _Conv3BN3(torch.autograd.Function):
     """out = relu(bn3(conv3(a2)) + residual) of a stage-1 identity block (1x1, 64 -> 256), whose
     backward never materialises bn3's input gradient dx3. Forward: exactly the launches of
@@ -371,12 +435,14 @@ class _Conv3BN3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a2, weight, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, nbt, link,
-                ours_fwd):
+                ours_fwd, c3=None):
         a2 = nhwc(a2)
         note_filter(weight)
         # the per-shape forward choice of conv1x1_hybrid: our GEMM with bn3's sums in its epilogue, or
-        # MIOpen and the statistics pass
-        c3 = _fwd1x1_stats(a2, weight, _workspace(a2)) if ours_fwd else torch.nn.functional.conv2d(a2, weight)
+        # MIOpen and the statistics pass; or c3 already computed, the sums pending (bn_relu_conv3)
+        ours_fwd = ours_fwd or c3 is not None
+        if c3 is None:
+            c3 = _fwd1x1_stats(a2, weight, _workspace(a2)) if ours_fwd else torch.nn.functional.conv2d(a2, weight)
         y, saved = _bn_fwd_from_stats(c3, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, True,
                                       ours_fwd, nbt)
         ctx.link, ctx.wdtype, ctx.params = link, bn_weight.dtype, (bn_weight, bn_bias)
@@ -396,7 +462,7 @@ class _Conv3BN3(torch.autograd.Function):
         dw = _slabs_to_wgrad(part, weight) if ctx.needs_input_grad[1] else None
         # the residual's gradient travels as (dy, mask): conv1's dgrad epilogue applies the mask
         dbw, dbb, _ = finish_bwd(dbw, dbb, ctx.wdtype, True, True, ctx.link, dy, mask, None, True)
-        return (d_a2, dw, dbw, dbb, None, None, None, None, None, None, None, None)
+        return (d_a2, dw, dbw, dbb, None, None, None, None, None, None, None, None, None)
 
 
 def _one_pass_branch(dy, mask, c, w32, mean, inv, sums, act, weight, part, out):
@@ -453,12 +519,13 @@ def conv3bn3_ok(a2, conv, bn, residual, link) -> bool:
             and _fused_bn_training(bn))
 
 
-def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True):
+def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True, c3=None):
     """relu(bn(conv(a2)) + residual) with the one-pass backward (check :func:`conv3bn3_ok`);
-    ``ours_fwd``: :func:`conv1x1_forward_is_ours` for this shape."""
+    ``ours_fwd``: :func:`conv1x1_forward_is_ours` for this shape; ``c3``: conv(a2) already computed, bn's sums
+    pending in the workspace (:func:`bn_relu_conv3`)."""
     mom, nbt = bn_counter(bn)
     return _Conv3BN3.apply(a2, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, mom,
-                           bn.eps, nbt, link, bool(ours_fwd))
+                           bn.eps, nbt, link, bool(ours_fwd), c3)
 
 
 def _dual_bn_fwd(c3, bn, stats_ready, cds, bn2, ds_ready):
@@ -557,11 +624,13 @@ class _Conv3DsBN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a2, w3, x, wds, w, b, w2, b2, rm, rv, mom, eps, nbt, rm2, rv2, mom2, eps2, nbt2, link, ours3,
-                ours_ds, form):
+                ours_ds, form, c3=None):
         a2, x = nhwc(a2), nhwc(x)
         note_filter(w3)
         note_filter(wds)
-        c3 = _fwd1x1_stats(a2, w3, _workspace(a2)) if ours3 else torch.nn.functional.conv2d(a2, w3)
+        ours3 = ours3 or c3 is not None  # already computed, bn3's sums pending (bn_relu_conv3)
+        if c3 is None:
+            c3 = _fwd1x1_stats(a2, w3, _workspace(a2)) if ours3 else torch.nn.functional.conv2d(a2, w3)
         cds = _ds_fwd_ours(x, wds, 1, _dual_workspace(x)) if ours_ds else torch.nn.functional.conv2d(x, wds)
         y, saved = _dual_bn_fwd(c3, (w, b, rm, rv, mom, eps, nbt), ours3, cds, (w2, b2, rm2, rv2, mom2, eps2, nbt2),
                                 ours_ds)
@@ -599,7 +668,7 @@ class _Conv3DsBN(torch.autograd.Function):
         if ctx.link is not None and ctx.link.offer(d_x):
             d_x = None  # delivered to conv1's dgrad epilogue
         t1, t2 = ctx.wdtypes
-        return (d_a2, grads[0], d_x, grads[1], dw.to(t1), db.to(t1), dw2.to(t2), db2.to(t2)) + (None,) * 14
+        return (d_a2, grads[0], d_x, grads[1], dw.to(t1), db.to(t1), dw2.to(t2), db2.to(t2)) + (None,) * 15
 
 
 # the one-pass backward around the dual BatchNorm of the stage-1 downsample block (FLUXMPI_CONV3DS=0:
@@ -630,14 +699,15 @@ def conv3ds_ok(x, conv2, conv3, bn, ds_conv, bn_ds) -> bool:
             and dual_bn_ok(x, 256, bn, bn_ds))
 
 
-def conv3ds_bn_relu(a2, conv3, bn, x, ds_conv, bn_ds, link=None, ours3=True, ours_ds=True):
+def conv3ds_bn_relu(a2, conv3, bn, x, ds_conv, bn_ds, link=None, ours3=True, ours_ds=True, c3=None):
     """relu(bn(conv3(a2)) + bn_ds(ds_conv(x))) with the one-pass backward (check :func:`conv3ds_ok`);
-    ``ours3`` / ``ours_ds``: :func:`conv1x1_forward_is_ours` / :func:`ds_forward_is_ours` for the shapes."""
+    ``ours3`` / ``ours_ds``: :func:`conv1x1_forward_is_ours` / :func:`ds_forward_is_ours` for the shapes;
+    ``c3``: conv3(a2) already computed, bn's sums pending in the workspace (:func:`bn_relu_conv3`)."""
     mom, nbt = bn_counter(bn)
     mom2, nbt2 = bn_counter(bn_ds)
     return _Conv3DsBN.apply(a2, conv3.weight, x, ds_conv.weight, bn.weight, bn.bias, bn_ds.weight, bn_ds.bias,
                             bn.running_mean, bn.running_var, mom, bn.eps, nbt, bn_ds.running_mean, bn_ds.running_var,
-                            mom2, bn_ds.eps, nbt2, link, bool(ours3), bool(ours_ds), CONV3DS)
+                            mom2, bn_ds.eps, nbt2, link, bool(ours3), bool(ours_ds), CONV3DS, c3)
 
 
 class _BNReluConv1x1(torch.autograd.Function):
@@ -924,10 +994,11 @@ def conv1x1_forward_is_ours(x, weight) -> bool:
     return stats_choice(_FWD1_CHOICE, (tuple(x.shape), weight.shape[0]), make)
 
 
-def conv1x1_hybrid(x, weight, link=None, bnlink=None, ours_stats=False):
+def conv1x1_hybrid(x, weight, link=None, bnlink=None, ours_stats=False, c=None):
     """``ours_stats``: forward on our GEMM with the next BatchNorm's statistics left pending in
-    the workspace (``bn_from_stats(..., stats_ready=True)``); else MIOpen's forward."""
-    return _Conv1x1Hybrid.apply(x, weight, link, bnlink, ours_stats)
+    the workspace (``bn_from_stats(..., stats_ready=True)``); else MIOpen's forward. ``c``: the output already
+    computed, the statistics pending (:func:`bn_relu_conv3`): no forward launch, the backward as ever."""
+    return _Conv1x1Hybrid.apply(x, weight, link, bnlink, ours_stats, c)
 
 
 def bn_from_stats(x, bn, relu=False, residual=None, stats_ready=True, link=None, bnlink=None):
