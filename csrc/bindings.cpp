@@ -5,6 +5,8 @@
 // ATen C++ ABI and lets it launch on any stream, including during HIP-graph
 // capture.
 #include <array>
+#include <optional>
+#include <tuple>
 #include <type_traits>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -36,129 +38,92 @@ template <typename R, typename... A> auto raw(R (*fn)(A...)) {
 using Ptrs = const std::vector<uintptr_t>&;
 using Ptrs3 = std::array<uintptr_t, 3>;
 
-// ---- the fused optimisers' entries, bound twice --------------------------------------------------
-// `_C` keeps the surface tests/golden/c_api_surface.json records. The loss-scaling arguments (the
-// skip predicate of the update kernels, the non-finite flag and the inverse scale of the norm pass)
-// and entries live in `_C_scale`, a second module of this shared object, with `dev_skip` as a
-// trailing keyword argument. One body serves both: it takes dev_skip FIRST, no_skip binds it to
-// null and skip_last moves it behind the other parameters. In front of dev_skip a body takes the
-// stochastic-rounding arguments (null in `_C` and `_C_scale`); with_sr, for `_C_sr`, builds them from
-// five more trailing keyword arguments.
-template <typename R, typename... A> auto no_skip(R (*fn)(const SrHyper*, uintptr_t, A...)) {
-  return [fn](A... a) -> R { return fn(nullptr, 0, a...); };
-}
-template <typename R, typename... A> auto skip_last(R (*fn)(const SrHyper*, uintptr_t, A...)) {
-  return [fn](A... a, uintptr_t dev_skip) -> R { return fn(nullptr, dev_skip, a...); };
-}
+// ---- the fused optimisers' entries ----------------------------------------------------------------
+// Behind the parameters `_C` has always had, the update entries take two trailing keywords, both off
+// by default: `dev_skip` (loss scaling: the device predicate that calls the launch off) and `sr`
+// (stochastic rounding). `sr` is ONE optional keyword, None or the tuple (seed, sr_stream, step,
+// dev_step, offsets), because seed = 0, step = 0 is a valid generator state: "on" cannot be read off
+// the values. A call that passes neither reaches the kernels with SrHyper* null and dev_skip null.
 static SrHyper sr_hyper(uint64_t seed, uint32_t sr_stream, uint32_t step, uintptr_t dev_step,
                         const std::vector<int64_t>& offsets) {
   return SrHyper{seed, sr_stream, step, ptr<const uint32_t*>(dev_step), offsets.empty() ? nullptr : offsets.data(),
                  offsets.size()};
 }
-template <typename R, typename... A> auto with_sr(R (*fn)(const SrHyper*, uintptr_t, A...)) {
-  return [fn](A... a, uintptr_t dev_skip, uint64_t seed, uint32_t sr_stream, uint32_t step, uintptr_t dev_step,
-              const std::vector<int64_t>& offsets) -> R {
-    const SrHyper sr = sr_hyper(seed, sr_stream, step, dev_step, offsets);
-    return fn(&sr, dev_skip, a...);
-  };
+using SrArg = const std::optional<std::tuple<uint64_t, uint32_t, uint32_t, uintptr_t, std::vector<int64_t>>>&;
+// *sr as an SrHyper in `h` (which points into sr's offsets), or null
+static const SrHyper* sr_or_null(SrArg sr, SrHyper& h) {
+  if (!sr) return nullptr;
+  h = std::apply(sr_hyper, *sr);
+  return &h;
 }
 
-static void py_mt_adam(const SrHyper* sr, uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
+static void py_mt_adam(Ptrs p, Ptrs g, Ptrs mm, Ptrs vv, Ptrs master,
                        const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
                        double beta2, double eps, double bc1, double bc2, double weight_decay, float grad_scale,
-                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale, float clip_delta) {
+                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t stream, uintptr_t tscale, float clip_delta,
+                       uintptr_t dev_skip, SrArg sr) {
+  SrHyper s;
   AdamHyper h{lr, beta1, beta2, eps, bc1, bc2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
               ptr<const float*>(dev_gscale)};
   h.tscale = ptr<const void*>(tscale);
   h.clip_delta = clip_delta;
   h.dev_skip = ptr<const int32_t*>(dev_skip);
-  mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
+  mt_adam(p, g, mm, vv, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr_or_null(sr, s));
 }
 
-static void py_mt_sgd(const SrHyper* sr, uintptr_t dev_skip, Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel,
-                      int p_dtype, int g_dtype, int s_dtype, double lr, double momentum, double weight_decay,
+static void py_mt_sgd(Ptrs p, Ptrs g, Ptrs buf, Ptrs master, const std::vector<int64_t>& numel, int p_dtype,
+                      int g_dtype, int s_dtype, double lr, double momentum, double weight_decay,
                       float grad_scale, int nesterov, uintptr_t dev_lr, uintptr_t stream, uintptr_t dev_gscale,
-                      uintptr_t tscale, float clip_delta) {
+                      uintptr_t tscale, float clip_delta, uintptr_t dev_skip, SrArg sr) {
+  SrHyper s;
   SgdHyper h{lr, momentum, weight_decay, grad_scale, nesterov, ptr<const float*>(dev_lr)};
   h.dev_gscale = ptr<const float*>(dev_gscale);
   h.tscale = ptr<const void*>(tscale);
   h.clip_delta = clip_delta;
   h.dev_skip = ptr<const int32_t*>(dev_skip);
-  mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
+  mt_sgd(p, g, buf, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr_or_null(sr, s));
 }
 
-static void py_mt_rule(const SrHyper* sr, uintptr_t dev_skip, int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master,
+static void py_mt_rule(int kind, Ptrs p, Ptrs g, Ptrs s1, Ptrs s2, Ptrs s3, Ptrs master,
                        const std::vector<int64_t>& numel, int p_dtype, int g_dtype, int s_dtype, double lr, double beta1,
                        double beta2, double eps, double bt1, double bt2, double weight_decay, float grad_scale,
-                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta, uintptr_t stream) {
+                       uintptr_t dev_hyper, uintptr_t dev_gscale, uintptr_t tscale, float clip_delta, uintptr_t stream,
+                       uintptr_t dev_skip, SrArg sr) {
+  SrHyper s;
   RuleHyper h{kind, lr, beta1, beta2, eps, bt1, bt2, weight_decay, grad_scale, ptr<const float*>(dev_hyper),
               ptr<const float*>(dev_gscale), ptr<const void*>(tscale), clip_delta, ptr<const int32_t*>(dev_skip)};
-  mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr);
+  mt_rule(p, g, s1, s2, s3, master, numel, p_dtype, g_dtype, s_dtype, h, ptr<hipStream_t>(stream), sr_or_null(sr, s));
 }
 
-#define ADAM_ARGS                                                                                                  \
-  py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("master"), py::arg("numel"),             \
-      py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("beta1"),                \
-      py::arg("beta2"), py::arg("eps"), py::arg("bc1"), py::arg("bc2"), py::arg("weight_decay"),                  \
-      py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"),                      \
-      py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f
-#define SGD_ARGS                                                                                                   \
-  py::arg("param"), py::arg("grad"), py::arg("buf"), py::arg("master"), py::arg("numel"), py::arg("p_dtype"),     \
-      py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),        \
-      py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"), py::arg("stream"),                           \
-      py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f
-#define RULE_ARGS                                                                                                  \
-  py::arg("kind"), py::arg("param"), py::arg("grad"), py::arg("s1"), py::arg("s2"), py::arg("s3"),                \
-      py::arg("master"), py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"),            \
-      py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("bt1"), py::arg("bt2"),          \
-      py::arg("weight_decay"), py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"),                \
-      py::arg("tscale"), py::arg("clip_delta"), py::arg("stream")
-#define SUMSQ_ARGS                                                                                                 \
-  py::arg("grad"), py::arg("numel"), py::arg("g_dtype"), py::arg("partials"), py::arg("sumsq"), py::arg("scale"), \
-      py::arg("omega"), py::arg("grad_scale"), py::arg("stream")
-#define TOTAL_ARGS                                                                                                 \
-  py::arg("sumsq"), py::arg("n"), py::arg("acc_dtype"), py::arg("slot"), py::arg("accumulate"), py::arg("omega"), \
-      py::arg("grad_scale"), py::arg("stream")
-#define NO_SKIP py::arg("dev_skip") = uintptr_t(0)
+// the two trailing keywords of the update entries (above)
+#define SKIP_SR_ARGS py::arg("dev_skip") = uintptr_t(0), py::arg("sr") = py::none()
 
-// The loss-scaling surface (DDP(loss_scale=...)): fluxmpi_amd.ops._ext.scale() loads it from _C's file.
-PYBIND11_MODULE(_C_scale, m) {
-  m.doc() = "fluxmpi_amd native library: the fused optimisers' entries with the loss-scaling arguments";
-  m.def("mt_adam", skip_last(&py_mt_adam), ADAM_ARGS, NO_SKIP);
-  m.def("mt_sgd", skip_last(&py_mt_sgd), SGD_ARGS, NO_SKIP);
-  m.def("mt_rule", skip_last(&py_mt_rule), RULE_ARGS, NO_SKIP);
+PYBIND11_MODULE(_C, m) {
+  m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
+
+  m.def("mt_copy", raw(&mt_copy), py::arg("src"), py::arg("dst"), py::arg("numel"), py::arg("in_dtype"),
+        py::arg("out_dtype"), py::arg("scale"), py::arg("stream"));
+  m.def("mt_fill", raw(&mt_fill));
+  m.def("mt_sumsq", raw(&mt_sumsq));
+
+  m.def("mt_adam", &py_mt_adam, py::arg("param"), py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("master"),
+        py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("bc1"), py::arg("bc2"), py::arg("weight_decay"),
+        py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"), py::arg("stream"),
+        py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f, SKIP_SR_ARGS);
   m.def("adam_advance", raw(&adam_advance), py::arg("dev"), py::arg("beta1"), py::arg("beta2"), py::arg("stream"),
-        NO_SKIP);
-  m.def("mt_leaf_sumsq", raw(&mt_leaf_sumsq), SUMSQ_ARGS, py::arg("nonfinite_flag") = uintptr_t(0),
-        py::arg("dev_pre") = uintptr_t(0));
-  m.def("clip_total", raw(&clip_total), TOTAL_ARGS, py::arg("dev_pre") = uintptr_t(0));
-  m.def("mt_check_finite", raw(&mt_check_finite), py::arg("grad"), py::arg("numel"), py::arg("g_dtype"),
-        py::arg("flag"), py::arg("stream"));
-  m.def("loss_scale_update", raw(&loss_scale_update), py::arg("block"), py::arg("growth"), py::arg("backoff"),
-        py::arg("interval"), py::arg("min_scale"), py::arg("max_scale"), py::arg("stream"));
-}
-
-// The weight-EMA surface (DDP(ema=...), optimisers.ema_update): a third module of this shared object,
-// loaded by fluxmpi_amd.ops._ext.ema(), so that `_C` and `_C_scale` keep the entries they have.
-PYBIND11_MODULE(_C_ema, m) {
-  m.doc() = "fluxmpi_amd native library: exponential moving average of the weights";
-  m.def("mt_ema", raw(&mt_ema), py::arg("ema"), py::arg("src"), py::arg("numel"), py::arg("src_dtype"),
-        py::arg("omd"), py::arg("dev_block"), py::arg("dev_skip"), py::arg("stream"));
-  m.def("ema_advance", raw(&ema_advance), py::arg("block"), py::arg("decay"), py::arg("warmup"), py::arg("every"),
-        py::arg("dev_skip"), py::arg("stream"));
-}
-
-// The stochastic-rounding surface (DDP(stochastic_rounding=...), ops.optim's sr=): a further module,
-// loaded by fluxmpi_amd.ops._ext.sr(). The update entries take the loss-scaling dev_skip and the
-// generator's arguments as trailing keywords; the step comes from `step`, or from the device block
-// `dev_step` when that is given.
-#define SR_ARGS                                                                                        \
-  py::arg("seed"), py::arg("sr_stream"), py::arg("step"), py::arg("dev_step"), py::arg("offsets")
-PYBIND11_MODULE(_C_sr, m) {
-  m.doc() = "fluxmpi_amd native library: stochastic rounding of the fused optimisers' bf16 stores";
-  m.def("mt_adam", with_sr(&py_mt_adam), ADAM_ARGS, NO_SKIP, SR_ARGS);
-  m.def("mt_sgd", with_sr(&py_mt_sgd), SGD_ARGS, NO_SKIP, SR_ARGS);
-  m.def("mt_rule", with_sr(&py_mt_rule), RULE_ARGS, NO_SKIP, SR_ARGS);
+        py::arg("dev_skip") = uintptr_t(0));
+  m.def("mt_sgd", &py_mt_sgd, py::arg("param"), py::arg("grad"), py::arg("buf"), py::arg("master"), py::arg("numel"),
+        py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("dev_lr"), py::arg("stream"),
+        py::arg("dev_gscale") = uintptr_t(0), py::arg("tscale") = uintptr_t(0), py::arg("clip_delta") = 0.f,
+        SKIP_SR_ARGS);
+  m.def("mt_rule", &py_mt_rule, py::arg("kind"), py::arg("param"), py::arg("grad"), py::arg("s1"), py::arg("s2"),
+        py::arg("s3"), py::arg("master"), py::arg("numel"), py::arg("p_dtype"), py::arg("g_dtype"), py::arg("s_dtype"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("bt1"), py::arg("bt2"),
+        py::arg("weight_decay"), py::arg("grad_scale"), py::arg("dev_hyper"), py::arg("dev_gscale"),
+        py::arg("tscale"), py::arg("clip_delta"), py::arg("stream"), SKIP_SR_ARGS);
+  // stochastic rounding as a stand-alone cast; sr_advance steps the device block `dev_step` points at
   m.def(
       "mt_stochastic_round",
       [](Ptrs dst, Ptrs src, const std::vector<int64_t>& numel, uintptr_t dev_skip, uintptr_t stream, uint64_t seed,
@@ -166,35 +131,31 @@ PYBIND11_MODULE(_C_sr, m) {
         mt_stochastic_round(dst, src, numel, sr_hyper(seed, sr_stream, step, dev_step, offsets),
                             ptr<const int32_t*>(dev_skip), ptr<hipStream_t>(stream));
       },
-      py::arg("dst"), py::arg("src"), py::arg("numel"), py::arg("dev_skip"), py::arg("stream"), SR_ARGS);
+      py::arg("dst"), py::arg("src"), py::arg("numel"), py::arg("dev_skip"), py::arg("stream"), py::arg("seed"),
+      py::arg("sr_stream"), py::arg("step"), py::arg("dev_step"), py::arg("offsets"));
   m.def("sr_advance", raw(&sr_advance), py::arg("block"), py::arg("dev_skip"), py::arg("stream"));
-}
 
-// The one-pass backward of the stage-1 downsample block (conv3ds_bwd.hip): a fourth module, loaded by
-// fluxmpi_amd.ops._ext.c3ds().
-PYBIND11_MODULE(_C_c3ds, m) {
-  m.doc() = "fluxmpi_amd native library: one-pass backward around the dual BatchNorm of a downsample block";
-  m.def("conv3ds_bwd", raw(&conv3ds_bwd), py::arg("dy"), py::arg("mask"), py::arg("c3"), py::arg("cds"), py::arg("w"),
-        py::arg("mean"), py::arg("inv"), py::arg("sum_dy"), py::arg("sum_dy_xhat"), py::arg("w2"), py::arg("mean2"),
-        py::arg("inv2"), py::arg("sum_dy2"), py::arg("sum_dy_xhat2"), py::arg("a2"), py::arg("x"), py::arg("wt3"),
-        py::arg("wtds"), py::arg("d_a2"), py::arg("d_xside"), py::arg("ws3"), py::arg("wsds"), py::arg("P"),
-        py::arg("slabs"), py::arg("stream"));
-}
+  // ---- gradient clipping, loss scaling (nonfinite_flag, dev_pre: the scaler's, null without) ----
+  m.def("sumsq_partials", &sumsq_partials, py::arg("numel"));
+  m.def("mt_leaf_sumsq", raw(&mt_leaf_sumsq), py::arg("grad"), py::arg("numel"), py::arg("g_dtype"),
+        py::arg("partials"), py::arg("sumsq"), py::arg("scale"), py::arg("omega"), py::arg("grad_scale"),
+        py::arg("stream"), py::arg("nonfinite_flag") = uintptr_t(0), py::arg("dev_pre") = uintptr_t(0));
+  m.def("clip_total", raw(&clip_total), py::arg("sumsq"), py::arg("n"), py::arg("acc_dtype"), py::arg("slot"),
+        py::arg("accumulate"), py::arg("omega"), py::arg("grad_scale"), py::arg("stream"),
+        py::arg("dev_pre") = uintptr_t(0));
+  m.def("mt_check_finite", raw(&mt_check_finite), py::arg("grad"), py::arg("numel"), py::arg("g_dtype"),
+        py::arg("flag"), py::arg("stream"));
+  m.def("loss_scale_update", raw(&loss_scale_update), py::arg("block"), py::arg("growth"), py::arg("backoff"),
+        py::arg("interval"), py::arg("min_scale"), py::arg("max_scale"), py::arg("stream"));
 
-// bn2 apply + ReLU + conv3 forward in one kernel (bn_relu_conv1x1_fwd.hip): a module of its own, loaded by
-// fluxmpi_amd.ops._ext.bn2c3().
-PYBIND11_MODULE(_C_bn2c3, m) {
-  m.doc() = "fluxmpi_amd native library: BatchNorm apply + ReLU + 1x1 expansion convolution forward";
-  m.def("bn_relu_conv1x1_fwd_supported", &bn_relu_conv1x1_fwd_supported, py::arg("Cin"), py::arg("Cout"));
-  m.def("bn_relu_conv1x1_fwd", raw(&bn_relu_conv1x1_fwd), py::arg("c2"), py::arg("scale"), py::arg("shift"),
-        py::arg("wt"), py::arg("a2"), py::arg("c3"), py::arg("stats"), py::arg("P"), py::arg("Cin"), py::arg("Cout"),
-        py::arg("stream"));
-}
+  // ---- exponential moving average of the weights ------------------------------------
+  m.def("mt_ema", raw(&mt_ema), py::arg("ema"), py::arg("src"), py::arg("numel"), py::arg("src_dtype"),
+        py::arg("omd"), py::arg("dev_block"), py::arg("dev_skip"), py::arg("stream"));
+  m.def("ema_advance", raw(&ema_advance), py::arg("block"), py::arg("decay"), py::arg("warmup"), py::arg("every"),
+        py::arg("dev_skip"), py::arg("stream"));
 
-// The device input pipeline (augment.hip): a fifth module, loaded by fluxmpi_amd.ops._ext.aug(). The
-// arguments of AugHyper travel as keywords; `dev_block` (or 0) is the device block of aug_block_set.
-PYBIND11_MODULE(_C_aug, m) {
-  m.doc() = "fluxmpi_amd native library: crop, flip, normalise, mixup / cutmix of a uint8 batch in one pass";
+  // ---- the device input pipeline (augment.hip): AugHyper's arguments travel as keywords; `dev_block`
+  // (or 0) is the device block of aug_block_set ----
   m.def(
       "augment_batch",
       [](uintptr_t in, uintptr_t out, int64_t B, int H, int W, int h, int w, int C, int dtype, uint64_t seed,
@@ -215,33 +176,18 @@ PYBIND11_MODULE(_C_aug, m) {
         aug_block_set(ptr<void*>(block), step, mode, box[0], box[1], box[2], box[3], lam, ptr<hipStream_t>(stream));
       },
       py::arg("block"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"), py::arg("stream"));
-}
 
-PYBIND11_MODULE(_C, m) {
-  m.doc() = "fluxmpi_amd native library: gfx950 HIP kernels + RCCL communicator";
-
-  m.def("mt_copy", raw(&mt_copy), py::arg("src"), py::arg("dst"), py::arg("numel"), py::arg("in_dtype"),
-        py::arg("out_dtype"), py::arg("scale"), py::arg("stream"));
-  m.def("mt_fill", raw(&mt_fill));
-  m.def("mt_sumsq", raw(&mt_sumsq));
-
-  m.def("mt_adam", no_skip(&py_mt_adam), ADAM_ARGS);
-  m.def("adam_advance", [](uintptr_t dev, float beta1, float beta2, uintptr_t stream) {
-    adam_advance(ptr<float*>(dev), beta1, beta2, ptr<hipStream_t>(stream));
-  });
-  m.def("mt_sgd", no_skip(&py_mt_sgd), SGD_ARGS);
-  m.def("mt_rule", no_skip(&py_mt_rule), RULE_ARGS);
-  m.def("sumsq_partials", &sumsq_partials, py::arg("numel"));
-  m.def("mt_leaf_sumsq",
-        [](Ptrs grad, const std::vector<int64_t>& numel, int g_dtype, uintptr_t partials, uintptr_t sumsq,
-           uintptr_t scale, float omega, float grad_scale, uintptr_t stream) {
-          raw(&mt_leaf_sumsq)(grad, numel, g_dtype, partials, sumsq, scale, omega, grad_scale, stream, 0, 0);
-        },
-        SUMSQ_ARGS);
-  m.def("clip_total",
-        [](uintptr_t sumsq, int64_t n, int acc_dtype, uintptr_t slot, int accumulate, float omega, float grad_scale,
-           uintptr_t stream) { raw(&clip_total)(sumsq, n, acc_dtype, slot, accumulate, omega, grad_scale, stream, 0); },
-        TOTAL_ARGS);
+  // ---- ResNet one-pass nodes: the backward around the dual BatchNorm of a stage-1 downsample block
+  // (conv3ds_bwd.hip); bn2 apply + ReLU + conv3 forward (bn_relu_conv1x1_fwd.hip) ----
+  m.def("conv3ds_bwd", raw(&conv3ds_bwd), py::arg("dy"), py::arg("mask"), py::arg("c3"), py::arg("cds"), py::arg("w"),
+        py::arg("mean"), py::arg("inv"), py::arg("sum_dy"), py::arg("sum_dy_xhat"), py::arg("w2"), py::arg("mean2"),
+        py::arg("inv2"), py::arg("sum_dy2"), py::arg("sum_dy_xhat2"), py::arg("a2"), py::arg("x"), py::arg("wt3"),
+        py::arg("wtds"), py::arg("d_a2"), py::arg("d_xside"), py::arg("ws3"), py::arg("wsds"), py::arg("P"),
+        py::arg("slabs"), py::arg("stream"));
+  m.def("bn_relu_conv1x1_fwd_supported", &bn_relu_conv1x1_fwd_supported, py::arg("Cin"), py::arg("Cout"));
+  m.def("bn_relu_conv1x1_fwd", raw(&bn_relu_conv1x1_fwd), py::arg("c2"), py::arg("scale"), py::arg("shift"),
+        py::arg("wt"), py::arg("a2"), py::arg("c3"), py::arg("stats"), py::arg("P"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("stream"));
 
   // ---- fused NHWC BatchNorm ------------------------------------------------
   m.def("bn_fwd_train", raw(&bn_fwd_train));

@@ -1243,13 +1243,7 @@ void attn_bwd(const void* q, const void* k, const void* v, const void* o, const 
   const unsigned grid = static_cast<unsigned>(total), threads = static_cast<unsigned>(plan.bwd_waves) * 64;
   if (plan.bwd == BwdKind::kFused13) {
     a.colpart = colpart;  // [B * 13][3 * H * 64] (attn_bwd_colpart_rows), or nullptr
-    static const bool attr = [] {
-      FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<13>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            static_cast<int>(fused_lds(13))));
-      return true;
-    }();
-    (void)attr;
+    allow_dynamic_lds(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<13>), static_cast<int>(fused_lds(13)));
     attn_bwd_fused_kernel<13><<<grid, threads, fused_lds(13), s>>>(a);
     FLUXMPI_HIP_CHECK(hipGetLastError());
     return;

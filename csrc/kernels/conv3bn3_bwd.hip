@@ -27,10 +27,8 @@
 // A workgroup stores its dW partial as one fp32 slab ws[blockIdx.x][256][64] (plain stores; a
 // workgroup without tiles stores zeros) and gemm_splitk_reduce sums the slabs: no float atomics,
 // no grid barrier. Rows past P are zero in both tiles, so the partial last tile adds nothing.
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "../api.h"
 #include "bn_dx.h"
@@ -246,20 +244,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv3bn3_bwd_kernel(C3Args p) {
         slab[static_cast<unsigned>((wave * 64 + 16 * i + 4 * (lane >> 4) + r) * kCi + 16 * j + (lane & 15))] = acc[i][j][r];
 }
 
-// the kernel needs more dynamic LDS than the default limit: raise it once per device
-void allow_lds() {
-  static std::mutex mu;
-  static std::vector<char> done;
-  int dev = 0;
-  FLUXMPI_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  if (static_cast<size_t>(dev) >= done.size()) done.resize(dev + 1, 0);
-  if (done[dev]) return;
-  FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3bn3_bwd_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
-  done[dev] = 1;
-}
-
 }  // namespace
 
 void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream) {
@@ -283,7 +267,7 @@ void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream) {
   // (more workgroups than tiles is allowed: the extra ones store zero slabs)
   if (g.splits < 1 || g.splits > 65535)
     throw std::runtime_error("gemm_bf16 mode 4: splits (the slab count = workgroups) must be in [1, 65535]");
-  allow_lds();
+  allow_dynamic_lds(reinterpret_cast<const void*>(&conv3bn3_bwd_kernel), kSmem);
   C3Args p{static_cast<const bf16*>(g.a), static_cast<const bf16*>(g.bnb_x), g.bnb_mask, g.bnb_w, g.bnb_mean,
            g.bnb_inv, g.a_scale, g.a_shift, static_cast<const bf16*>(g.res), static_cast<const bf16*>(g.b),
            static_cast<bf16*>(g.c), g.stats, g.M};

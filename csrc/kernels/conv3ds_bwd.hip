@@ -22,10 +22,8 @@
 // ws3[blockIdx.x][256][64] and wsds[blockIdx.x][256][64] (plain stores; a workgroup without tiles
 // stores zeros) and gemm_splitk_reduce sums each set: no float atomics, no grid barrier. Rows past P
 // are zero in every tile, so the partial last tile adds nothing.
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "../api.h"
 #include "bn_dx.h"
@@ -250,20 +248,6 @@ __global__ __launch_bounds__(kThreads) void conv3ds_bwd_kernel(DsArgs p) {
         slab[static_cast<unsigned>((wv * 64 + 16 * i + 4 * (lane >> 4) + r) * kCi + 16 * j + (lane & 15))] = acc[i][j][r];
 }
 
-// the kernel needs more dynamic LDS than the default limit: raise it once per device
-void allow_lds() {
-  static std::mutex mu;
-  static std::vector<char> done;
-  int dev = 0;
-  FLUXMPI_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  if (static_cast<size_t>(dev) >= done.size()) done.resize(dev + 1, 0);
-  if (done[dev]) return;
-  FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3ds_bwd_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
-  done[dev] = 1;
-}
-
 }  // namespace
 
 void conv3ds_bwd(const void* dy, const uint8_t* mask, const void* c3, const void* cds, const float* w,
@@ -290,7 +274,7 @@ void conv3ds_bwd(const void* dy, const uint8_t* mask, const void* c3, const void
   // (more workgroups than tiles is allowed: the extra ones store zero slabs)
   if (slabs < 1 || slabs > 65535)
     throw std::runtime_error("conv3ds_bwd: slabs (the slab count = workgroups) must be in [1, 65535]");
-  allow_lds();
+  allow_dynamic_lds(reinterpret_cast<const void*>(&conv3ds_bwd_kernel), kSmem);
   DsArgs p{static_cast<const bf16*>(dy), mask,
            {Branch{static_cast<const bf16*>(c3), w, mean, inv, sum_dy, sum_dy_xhat, static_cast<const bf16*>(a2),
                    static_cast<const bf16*>(wt3), static_cast<bf16*>(d_a2), ws3},

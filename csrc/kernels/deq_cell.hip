@@ -620,13 +620,6 @@ void check_disjoint(const void* out, size_t out_bytes, const void* p, size_t byt
     throw std::runtime_error("deq_cell_vjp: out must not alias u, grad or the state");
 }
 
-template <typename K>
-void set_lds(K kernel, size_t lds) {
-  if (lds > 160 * 1024) throw std::runtime_error("deq_cell: sample does not fit in LDS");
-  FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-}
-
 }  // namespace
 
 bool deq_cell_supported(int64_t H, int64_t W, int64_t C, int64_t G) {
@@ -655,11 +648,7 @@ void deq_cell_fwd(const void* z, const void* x, const void* w1, const void* w2, 
     a.st.mean[i] = mean[i];
     a.st.rstd[i] = rstd[i];
   }
-  static bool attr = false;
-  if (!attr) {
-    set_lds(deq_cell_fwd_kernel, 160 * 1024);
-    attr = true;
-  }
+  allow_dynamic_lds(reinterpret_cast<const void*>(&deq_cell_fwd_kernel), 160 * 1024);
   deq_cell_fwd_kernel<<<s.N, kThreads, lds, stream>>>(a, s);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
@@ -698,11 +687,7 @@ void deq_cell_vjp(const void* u, const void* const* h, const void* w2t, const vo
     a.mean[i] = mean[i];
     a.rstd[i] = rstd[i];
   }
-  static bool attr = false;
-  if (!attr) {
-    set_lds(deq_cell_vjp_kernel, 160 * 1024);
-    attr = true;
-  }
+  allow_dynamic_lds(reinterpret_cast<const void*>(&deq_cell_vjp_kernel), 160 * 1024);
   deq_cell_vjp_kernel<<<s.N, kThreads, lds, stream>>>(a, s);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }

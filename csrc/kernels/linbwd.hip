@@ -332,12 +332,7 @@ void linear_bwd(const void* dy, const void* x, const void* w, void* dx, float* w
   p.dg_first = dg_first;
   const int64_t grid = static_cast<int64_t>(p.wg_jobs) + p.dg_tiles;
   if (grid == 0) return;
-  static bool attr = false;
-  if (!attr) {
-    FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&linbwd_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
-    attr = true;
-  }
+  allow_dynamic_lds(reinterpret_cast<const void*>(&linbwd_kernel), kSmem);
   linbwd_kernel<<<static_cast<unsigned>(grid), kThreads, kSmem, stream>>>(p);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }

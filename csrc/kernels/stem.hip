@@ -604,22 +604,9 @@ void check_ptr(const void* ptr, const char* what) {
 
 }  // namespace
 
-namespace {
-void set_lds_attrs() {
-  static bool done = false;
-  if (done) return;
-  FLUXMPI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kFSmem));
-  for (const void* k : {reinterpret_cast<const void*>(&stem_bwd_kernel<0>), reinterpret_cast<const void*>(&stem_bwd_kernel<1>),
-                        reinterpret_cast<const void*>(&stem_bwd_kernel<2>), reinterpret_cast<const void*>(&stem_bwd_kernel<3>)})
-    FLUXMPI_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kBSmem));
-  done = true;
-}
-}  // namespace
-
 int stem_bwd_blocks(int64_t n) {
   static int b = [] {
-    set_lds_attrs();
+    allow_dynamic_lds(reinterpret_cast<const void*>(&stem_bwd_kernel<0>), kBSmem);
     const int r = resident_blocks(reinterpret_cast<const void*>(&stem_bwd_kernel<0>), kBT, kBSmem);
     return r > 0 ? r : 512;
   }();
@@ -636,7 +623,7 @@ void stem_fwd(const void* x, const void* wp, void* y, float* stats, int64_t n, h
   check_ptr(stats, "stats");
   if (n < 1 || n * kOH * kOW * kCo >= (int64_t(1) << 40)) throw std::runtime_error("stem_fwd: bad batch");
   if (max_blocks < 0) throw std::runtime_error("stem_fwd: max_blocks must be >= 0 (0: the resident workgroups)");
-  set_lds_attrs();
+  allow_dynamic_lds(reinterpret_cast<const void*>(&stem_fwd_kernel), kFSmem);
   const int groups = static_cast<int>(n * (kOH / kFRows));
   static int resident = [] { return resident_blocks(reinterpret_cast<const void*>(&stem_fwd_kernel), kFT, kFSmem); }();
   const int cap = max_blocks > 0 && max_blocks < resident ? max_blocks : resident;  // a test's grid: longer walks
@@ -656,7 +643,6 @@ void stem_bwd(const void* x, const void* c, const void* dp, const uint8_t* idx, 
   check_ptr(idx, "pool index");
   check_ptr(part, "partials");
   if (n < 1 || blocks < 1 || blocks > stem_bwd_blocks(n)) throw std::runtime_error("stem_bwd: bad batch / grid");
-  set_lds_attrs();
   // FLUXMPI_STEM_BWD_DIAG=1/2/3: the MODE builds (time split of the phases; results are wrong)
   static const int mode = [] {
     const char* e = std::getenv("FLUXMPI_STEM_BWD_DIAG");
@@ -667,6 +653,7 @@ void stem_bwd(const void* x, const void* c, const void* dp, const uint8_t* idx, 
   StemBwdArgs a{static_cast<const bf16*>(x), static_cast<const bf16*>(c), static_cast<const bf16*>(dp), idx, mean, inv,
                 part, stats, (total + blocks - 1) / blocks, total};
   auto kern = mode == 1 ? stem_bwd_kernel<1> : mode == 2 ? stem_bwd_kernel<2> : mode == 3 ? stem_bwd_kernel<3> : stem_bwd_kernel<0>;
+  allow_dynamic_lds(reinterpret_cast<const void*>(kern), kBSmem);
   kern<<<static_cast<unsigned>(blocks), kBT, kBSmem, s>>>(a);
   FLUXMPI_HIP_CHECK(hipGetLastError());
   bn_finalize_bwd(stats, kCo, dw_bn, db_bn, s);

@@ -1,11 +1,15 @@
 """Loader for the in-tree native extension ``fluxmpi_amd._C``.
 
-``_C`` is one shared object, built by ``fluxmpi_amd/_build.py`` with hipcc for
-gfx950, that contains
+``_C`` is one shared object and one Python module (``csrc/bindings.cpp``), built by
+``fluxmpi_amd/_build.py`` with hipcc for gfx950, that contains
 
-* the CDNA4 HIP kernels (multi-tensor pack/unpack/scale, fused Adam/SGD
-  families, fused BatchNorm(+ReLU) for NHWC), and
+* the CDNA4 HIP kernels: the multi-tensor copies and fused optimisers (with gradient clipping, loss
+  scaling, weight EMA and stochastic rounding), the normalisation, attention, GEMM and convolution
+  kernels, the ResNet one-pass nodes, the DEQ cell and solver, the device input pipeline, and
 * the native RCCL communicator (``csrc/comm/rccl_comm.cpp``).
+
+Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
+(``tests/test_bindings_surface.py`` says what may change in its surface).
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -21,7 +25,6 @@ and as the numerics oracle in tests.
 from __future__ import annotations
 
 import importlib
-import importlib.util
 import os
 
 import torch
@@ -72,65 +75,6 @@ def get(required: bool = True):
             f"{_ERR!r}. Run `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`."
         )
     return mod
-
-
-_EXTRA: dict = {}
-
-
-def _extra(name: str, what: str):
-    """A further pybind11 module ``fluxmpi_amd.<name>`` of the shared object ``_C`` was loaded from (its
-    ``PyInit_<name>``): new entries get a module of their own, so ``_C`` itself keeps the surface
-    ``tests/golden/c_api_surface.json`` records. Missing: an error, as for ``_C``."""
-    if name not in _EXTRA:
-        C = get(required=True)
-        if C is None:
-            raise NativeExtensionError(f"fluxmpi_amd.{name} needs the native extension fluxmpi_amd._C")
-        spec = importlib.util.spec_from_file_location(f"fluxmpi_amd.{name}", C.__file__)
-        try:
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-        except Exception as e:
-            raise NativeExtensionError(
-                f"fluxmpi_amd.{name} ({what} of {C.__file__}) failed to load: {e!r}. "
-                "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
-        _EXTRA[name] = mod
-    return _EXTRA[name]
-
-
-def scale():
-    """The ``_C_scale`` module: the fused optimisers' entries with the loss-scaling arguments
-    (``dev_skip``, ``nonfinite_flag``, ``dev_pre``), ``mt_check_finite`` and ``loss_scale_update``."""
-    return _extra("_C_scale", "the loss-scaling entries")
-
-
-def ema():
-    """The ``_C_ema`` module: ``mt_ema`` and ``ema_advance`` (the exponential moving average of the
-    weights, ``csrc/kernels/optim_ema.hip``)."""
-    return _extra("_C_ema", "the weight-EMA entries")
-
-
-def sr():
-    """The ``_C_sr`` module: the fused optimisers' entries with the stochastic-rounding arguments,
-    ``mt_stochastic_round`` and ``sr_advance`` (``csrc/kernels/optim_sr.h``, ``optim_sr.hip``)."""
-    return _extra("_C_sr", "the stochastic-rounding entries")
-
-
-def c3ds():
-    """The ``_C_c3ds`` module: ``conv3ds_bwd`` (the one-pass backward around the dual BatchNorm of a
-    stage-1 downsample block, ``csrc/kernels/conv3ds_bwd.hip``)."""
-    return _extra("_C_c3ds", "the downsample-block backward entry")
-
-
-def bn2c3():
-    """The ``_C_bn2c3`` module: ``bn_relu_conv1x1_fwd`` (bn2 apply + ReLU + conv3 forward of a bottleneck in
-    one kernel, ``csrc/kernels/bn_relu_conv1x1_fwd.hip``)."""
-    return _extra("_C_bn2c3", "the bn2 + conv3 forward entry")
-
-
-def aug():
-    """The ``_C_aug`` module: ``augment_batch`` and ``aug_block_set`` (the device input pipeline,
-    ``csrc/kernels/augment.hip``)."""
-    return _extra("_C_aug", "the input-pipeline entries")
 
 
 def require_for(t: torch.Tensor):

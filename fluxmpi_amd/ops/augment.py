@@ -240,7 +240,7 @@ def augment_batch(u8: torch.Tensor, *, size, pad=0, fill=0, crop="random", flip=
             return z.permute(0, 3, 1, 2)
         (out if out.shape == z.shape else out.permute(0, 2, 3, 1)).copy_(z)
         return out if tuple(out.shape) == (c.B, channels, c.h, c.w) else out.permute(0, 3, 1, 2)
-    A = _ext.aug()
+    A = _ext.get(required=True)
     buf = out if out is not None else torch.empty(c.B, c.h, c.w, channels, device=u8.device, dtype=dtype)
     A.augment_batch(u8.data_ptr(), buf.data_ptr(), c.B, c.H, c.W, c.h, c.w, channels, DTYPE_CODE[dtype], int(seed),
                     int(stream), int(step), int(sample_offset), c.mix.mode, list(c.mix.box), c.mix.lam, pad, fill,
@@ -255,8 +255,8 @@ def block_set(block: torch.Tensor, step: int, mix: MixDraw | None = None) -> Non
     _check_ids("aug_block_set", 0, 0, step)
     if not (block.is_cuda and block.dtype == torch.int32 and block.numel() >= BLOCK_WORDS and block.is_contiguous()):
         raise ValueError(f"aug_block_set: the block is a dense int32 GPU tensor of {BLOCK_WORDS} words")
-    _ext.aug().aug_block_set(block.data_ptr(), int(step), int(mix.mode), [int(v) for v in mix.box], float(mix.lam),
-                             _stream(block))
+    _ext.get(required=True).aug_block_set(block.data_ptr(), int(step), int(mix.mode), [int(v) for v in mix.box],
+                                          float(mix.lam), _stream(block))
 
 
 def block_lam(block: torch.Tensor) -> torch.Tensor:

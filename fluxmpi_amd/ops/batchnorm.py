@@ -238,8 +238,8 @@ def launch_apply_conv1x1(x, scale, shift, weight, ws=None):
     y = torch.empty_like(x)
     c = torch.empty(n, h, w, co, device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
     ws = _workspace(x) if ws is None else ws
-    _ext.bn2c3().bn_relu_conv1x1_fwd(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), weight.data_ptr(), y.data_ptr(),
-                                     c.data_ptr(), ws.data_ptr(), n * h * w, ch, co, stream(x))
+    _ext.get(required=True).bn_relu_conv1x1_fwd(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), weight.data_ptr(),
+                                                y.data_ptr(), c.data_ptr(), ws.data_ptr(), n * h * w, ch, co, stream(x))
     return y, c
 
 

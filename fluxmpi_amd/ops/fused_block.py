@@ -654,11 +654,11 @@ class _Conv3DsBN(torch.autograd.Function):
         if ctx.form == 2:
             slabs = conv3ds_slabs(rows, dev)
             part = torch.empty(2, slabs, co, ci, device=dev, dtype=torch.float32)
-            _ext.c3ds().conv3ds_bwd(dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(),
-                                    mean.data_ptr(), inv.data_ptr(), db.data_ptr(), dw.data_ptr(), w232.data_ptr(),
-                                    mean2.data_ptr(), inv2.data_ptr(), db2.data_ptr(), dw2.data_ptr(), a2.data_ptr(),
-                                    x.data_ptr(), w3.data_ptr(), wds.data_ptr(), d_a2.data_ptr(), d_x.data_ptr(),
-                                    part[0].data_ptr(), part[1].data_ptr(), rows, slabs, _stream(dy))
+            _ext.get(required=True).conv3ds_bwd(
+                dy.data_ptr(), mask.data_ptr(), c3.data_ptr(), cds.data_ptr(), w32.data_ptr(), mean.data_ptr(),
+                inv.data_ptr(), db.data_ptr(), dw.data_ptr(), w232.data_ptr(), mean2.data_ptr(), inv2.data_ptr(),
+                db2.data_ptr(), dw2.data_ptr(), a2.data_ptr(), x.data_ptr(), w3.data_ptr(), wds.data_ptr(),
+                d_a2.data_ptr(), d_x.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), rows, slabs, _stream(dy))
         else:
             part = torch.empty(2, conv3bn3_slabs(rows, dev), co, ci, device=dev, dtype=torch.float32)
             _one_pass_branch(dy, mask, c3, w32, mean, inv, (db, dw), a2, w3, part[0], d_a2)

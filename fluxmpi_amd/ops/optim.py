@@ -71,18 +71,14 @@ def _ptr(t: torch.Tensor | None) -> int:
     return t.data_ptr() if t is not None else 0
 
 
-def _call(C, name: str, *args, _scaling: dict, _sr: dict | None = None, **kw):
-    """Call the native entry ``name``: ``_C``'s, or, when one of the loss-scaling arguments
-    ``_scaling`` (device addresses; 0: not given) is there, ``_C_scale``'s with those arguments.
-    ``_C`` keeps its recorded surface; the loss-scaling surface is a second module of the same
-    library (``ops._ext.scale``). With ``_sr`` (the generator's arguments, :meth:`SR._native`):
-    ``_C_sr``'s entry, which takes both."""
-    if _sr is not None:
-        return getattr(_ext.sr(), name)(*args, **kw, **_scaling, **_sr)
+def _call(C, name: str, *args, _scaling: dict, _sr: tuple | None = None, **kw):
+    """Call ``_C``'s entry ``name`` with, as trailing keywords, those of the loss-scaling arguments
+    ``_scaling`` (device addresses; 0: not given) that are given and, with ``_sr`` (the generator's
+    arguments, :meth:`SR._native`), ``sr``. Without either the call is the entry's plain one."""
     given = {k: v for k, v in _scaling.items() if v}
-    if given:
-        return getattr(_ext.scale(), name)(*args, **kw, **given)
-    return getattr(C, name)(*args, **kw)
+    if _sr is not None:
+        given["sr"] = _sr
+    return getattr(C, name)(*args, **kw, **given)
 
 
 def _skip_ptr(dev_skip) -> int:
@@ -147,10 +143,11 @@ class SR:
     def _offset(self, i: int) -> int:
         return 0 if self.offsets is None else self.offsets[i]
 
-    def _native(self, idx, n: int) -> dict:
+    def _native(self, idx, n: int) -> tuple:
+        """``(seed, sr_stream, step, dev_step, offsets)``: the update entries' ``sr`` keyword, and under
+        those names the keywords of ``mt_stochastic_round``."""
         off = self._offsets(n)
-        return {"seed": self.seed, "sr_stream": self.stream, "step": self.step, "dev_step": _ptr(self.dev_block),
-                "offsets": [off[i] for i in idx]}
+        return self.seed, self.stream, self.step, _ptr(self.dev_block), [off[i] for i in idx]
 
     def _host_step(self) -> int:
         """The step as the reference path reads it (a host read of the block: CPU tensors)."""
@@ -197,7 +194,8 @@ def sr_advance_(block: torch.Tensor, *, dev_skip: torch.Tensor | None = None) ->
     launches; not when ``dev_skip`` is non-zero: a skipped step does not count. Graph-capturable."""
     _sr_block_ok(block, "sr_advance_")
     if block.is_cuda:
-        _ext.sr().sr_advance(block.data_ptr(), _skip_ptr(dev_skip), torch.cuda.current_stream(block.device).cuda_stream)
+        _ext.get(required=True).sr_advance(block.data_ptr(), _skip_ptr(dev_skip),
+                                           torch.cuda.current_stream(block.device).cuda_stream)
     elif not _skipped(dev_skip):
         nxt = ((int(block[0]) & 0xFFFFFFFF) + 1) & 0xFFFFFFFF
         block[0] = nxt - (1 << 32) if nxt >= 1 << 31 else nxt
@@ -228,10 +226,11 @@ def stochastic_round_(dsts, srcs, sr: "SR", *, dev_skip: torch.Tensor | None = N
     if not dsts[0].is_cuda:
         stochastic_round_reference_(dsts, srcs, sr, dev_skip=dev_skip)
         return
-    _ext.sr().mt_stochastic_round([d.data_ptr() for d in dsts], [x.data_ptr() for x in srcs],
-                                  [d.numel() for d in dsts], _skip_ptr(dev_skip),
-                                  torch.cuda.current_stream(dsts[0].device).cuda_stream,
-                                  **sr._native(range(len(dsts)), len(dsts)))
+    _ext.get(required=True).mt_stochastic_round([d.data_ptr() for d in dsts], [x.data_ptr() for x in srcs],
+                                                [d.numel() for d in dsts], _skip_ptr(dev_skip),
+                                                torch.cuda.current_stream(dsts[0].device).cuda_stream,
+                                                **dict(zip(("seed", "sr_stream", "step", "dev_step", "offsets"),
+                                                           sr._native(range(len(dsts)), len(dsts)))))
 
 
 def stochastic_round_reference_(dsts, srcs, sr: "SR", *, dev_skip: torch.Tensor | None = None) -> None:
@@ -830,7 +829,7 @@ def check_finite_(grads, flag: torch.Tensor) -> None:
     if not grads[0].is_cuda:
         check_finite_reference_(grads, flag)
         return
-    S = _ext.scale()
+    S = _ext.get(required=True)
     stream = torch.cuda.current_stream(grads[0].device).cuda_stream
     by_dtype: dict = {}
     for g in grads:
@@ -872,8 +871,9 @@ def loss_scale_update_(block: torch.Tensor, *, growth: float, backoff: float, in
     if block.dtype != torch.int32 or block.numel() < LS_WORDS or not block.is_contiguous():
         raise TypeError(f"loss_scale_update_: block is a contiguous int32 tensor of {LS_WORDS} entries")
     if block.is_cuda:
-        _ext.scale().loss_scale_update(block.data_ptr(), float(growth), float(backoff), int(interval), float(min_scale),
-                            float(max_scale), torch.cuda.current_stream(block.device).cuda_stream)
+        _ext.get(required=True).loss_scale_update(block.data_ptr(), float(growth), float(backoff), int(interval),
+                                                  float(min_scale), float(max_scale),
+                                                  torch.cuda.current_stream(block.device).cuda_stream)
         return
     loss_scale_update_reference_(block, growth=growth, backoff=backoff, interval=interval, min_scale=min_scale,
                                  max_scale=max_scale)
@@ -985,7 +985,7 @@ def ema_(emas, srcs, *, decay: float | None = None, dev_block: torch.Tensor | No
     if not emas[0].is_cuda:
         ema_reference_(emas, srcs, decay=decay, dev_block=dev_block, dev_skip=dev_skip)
         return
-    E = _ext.ema()
+    E = _ext.get(required=True)
     stream = torch.cuda.current_stream(emas[0].device).cuda_stream
     omd = 1.0 - float(decay) if decay is not None else 0.0
     groups: dict = {}
@@ -1029,8 +1029,8 @@ def ema_advance_(block: torch.Tensor, *, decay: float, warmup: bool, every: int,
     if int(every) < 1:
         raise ValueError(f"ema_advance_: every must be >= 1, got {every}")
     if block.is_cuda:
-        _ext.ema().ema_advance(block.data_ptr(), float(decay), int(bool(warmup)), int(every), _skip_ptr(dev_skip),
-                               torch.cuda.current_stream(block.device).cuda_stream)
+        _ext.get(required=True).ema_advance(block.data_ptr(), float(decay), int(bool(warmup)), int(every),
+                                            _skip_ptr(dev_skip), torch.cuda.current_stream(block.device).cuda_stream)
         return
     ema_advance_reference_(block, decay=decay, warmup=warmup, every=every, dev_skip=dev_skip)
 

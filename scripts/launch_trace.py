@@ -5,8 +5,8 @@ change of host code changed nothing; the launches can: which entries of the exte
 what order, with which scalars, null pointers and dataflow links is fully determined by the host code.
 (The same kind of check as ``scripts/isa_equal.py`` for device code and ``scripts/optim_digest.py``.)
 
-:func:`recording` puts a stand-in in place of ``_ext.get()`` / ``_ext.c3ds()`` that forwards every call
-and logs ``entry(arguments)``; the vendor calls (``F.conv2d``, ``aten.convolution_backward``) are logged
+:func:`recording` puts a stand-in in place of ``_ext.get()``, the one way into the extension, that forwards
+every call and logs ``entry(arguments)``; the vendor calls (``F.conv2d``, ``aten.convolution_backward``) are logged
 the same way, tensors as ``shape@address``. An integer >= 2^40 is a device address and is written as
 ``a<k>``, k the order of first appearance in the case, so the trace does not depend on where the
 allocator put things; 0 stays 0, lists go element by element, everything else is written verbatim.
@@ -73,17 +73,17 @@ class Recorder:
 class _Proxy:
     """Forwards every attribute of the extension module; calls are logged first."""
 
-    def __init__(self, mod, rec, tag=""):
-        self.__dict__.update(_mod=mod, _rec=rec, _tag=tag)
+    def __init__(self, mod, rec):
+        self.__dict__.update(_mod=mod, _rec=rec)
 
     def __getattr__(self, name):
         v = getattr(self._mod, name)
         if not callable(v):
             return v
-        rec, full = self._rec, self._tag + name
+        rec = self._rec
 
         def call(*args, **kwargs):
-            rec.add(full, args, kwargs, sys._getframe(1))
+            rec.add(name, args, kwargs, sys._getframe(1))
             return v(*args, **kwargs)
         return call
 
@@ -126,21 +126,18 @@ class _Vendor:
 
 @contextlib.contextmanager
 def recording(rec: Recorder, ext=None, vendor: bool = True):
-    """Log into ``rec`` every call made through ``ext.get()`` / ``ext.c3ds()`` (default: ``ops._ext``) and,
+    """Log into ``rec`` every call made through ``ext.get()`` (default: ``ops._ext``) and,
     with ``vendor``, through ``F.conv2d`` / ``aten.convolution_backward``; the originals are put back on exit."""
     if ext is None:
         from fluxmpi_amd.ops import _ext as ext
-    get, c3ds = ext.get, ext.c3ds
+    get = ext.get
 
     def rec_get(*a, **k):
         mod = get(*a, **k)
         return None if mod is None else _Proxy(mod, rec)
 
-    def rec_c3ds():
-        return _Proxy(c3ds(), rec, "c3ds.")
-
-    undo = [(ext, "get", get), (ext, "c3ds", c3ds)]
-    ext.get, ext.c3ds = rec_get, rec_c3ds
+    undo = [(ext, "get", get)]
+    ext.get = rec_get
     try:
         if vendor:
             import torch

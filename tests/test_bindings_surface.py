@@ -3,9 +3,13 @@
 For every attribute of the module and every method of ``RcclComm``: name, number of parameters,
 parameter names (``None`` where the binding names none), default values, and whether it returns
 ``None``, all parsed from the signature line pybind11 writes into the docstring (types are not
-compared, so a change of pybind's wording does not matter). ``tests/golden/c_api_surface.json`` was
-recorded from the hand-written bindings that preceded the ``raw()`` adaptor;
+compared, so a change of pybind's wording does not matter).
 ``python -m tests.test_bindings_surface`` prints the surface of the built library in that format.
+
+The rule: add entries, or trailing parameters with defaults, freely and re-record
+``tests/golden/c_api_surface.json``. Never edit ``c_api_surface_base.json``: anything
+``test_golden_extends_base`` rejects (a name gone, a parameter renamed, reordered or without its
+default, a new parameter a caller has to pass) breaks callers and needs its own justification.
 """
 import json
 import os
@@ -14,6 +18,12 @@ import re
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "c_api_surface.json")
+BASE = os.path.join(os.path.dirname(GOLDEN), "c_api_surface_base.json")
+# entries that began in modules of their own beside ``_C``
+MOVED_IN = ("mt_check_finite", "loss_scale_update", "mt_ema", "ema_advance", "mt_stochastic_round", "sr_advance",
+            "conv3ds_bwd", "bn_relu_conv1x1_fwd_supported", "bn_relu_conv1x1_fwd", "augment_batch", "aug_block_set")
+# base functions that have grown trailing defaulted parameters (loss scaling, stochastic rounding)
+EXTENDED = ("adam_advance", "clip_total", "mt_adam", "mt_leaf_sumsq", "mt_rule", "mt_sgd")
 
 
 def _split_top(s: str) -> list[str]:
@@ -83,6 +93,33 @@ def test_bindings_surface_matches_golden():
     assert sorted(got) == sorted(golden), (sorted(set(got) ^ set(golden)))
     for name in golden:
         assert got[name] == golden[name], name
+
+
+def test_golden_extends_base():
+    """The recorded surface is a compatible superset of the base: every call the base allowed still binds."""
+    with open(GOLDEN) as f:
+        new = json.load(f)
+    with open(BASE) as f:
+        base = json.load(f)
+    assert len(base) == 90 and len(new) == 101
+    assert not set(MOVED_IN) - set(new), sorted(set(MOVED_IN) - set(new))
+    differ = []
+    for name, old in base.items():
+        assert name in new, name
+        got = new[name]
+        if old["kind"] != "function":  # a class, or "other"
+            assert got == old, name
+            continue
+        assert got["kind"] == "function" and got["returns_none"] == old["returns_none"], name
+        assert got["nparams"] >= old["nparams"] == len(old["params"]) and got["nparams"] == len(got["params"]), name
+        for i, (po, pn) in enumerate(zip(old["params"], got["params"])):
+            assert pn["default"] == po["default"], (name, i)
+            assert po["name"] is None or pn["name"] == po["name"], (name, i)
+        for i, pn in enumerate(got["params"][old["nparams"]:], old["nparams"]):
+            assert pn["default"] is not None, (name, i)
+        if got != old:
+            differ.append(name)
+    assert sorted(differ) == sorted(EXTENDED)
 
 
 if __name__ == "__main__":

@@ -47,7 +47,7 @@ def _st():
 
 def _entry():
     from fluxmpi_amd.ops import _ext
-    return _ext.bn2c3()
+    return _ext.get(required=True)
 
 
 def _inputs(family, P, ci, co, seed):

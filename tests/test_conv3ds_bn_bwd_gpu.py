@@ -41,7 +41,7 @@ def _st():
 
 def _X():
     from fluxmpi_amd.ops import _ext
-    return _ext.c3ds()
+    return _ext.get(required=True)
 
 
 def _branch(family, P, seed, flip):

@@ -19,8 +19,8 @@ def lt():
 def _fake():
     calls = []
     mod = types.SimpleNamespace(launch=lambda *a, **k: calls.append(("launch", a, k)) or 7, version="1.0")
-    extra = types.SimpleNamespace(conv3ds_bwd=lambda *a: calls.append(("c3ds", a, {})))
-    ext = types.SimpleNamespace(get=lambda required=True: mod, c3ds=lambda: extra)
+    mod.conv3ds_bwd = lambda *a: calls.append(("c3ds", a, {}))
+    ext = types.SimpleNamespace(get=lambda required=True: mod)
     return ext, mod, calls
 
 
@@ -32,11 +32,11 @@ def test_addresses_are_numbered_by_first_appearance(lt):
         C = ext.get(required=True)
         assert C.launch(b, a, 0, 392, 1e-5, True, None, (1 << 40) - 1) == 7  # forwarded, result handed back
         C.launch(a, c, b, flag=a)
-        ext.c3ds().conv3ds_bwd(c, 13)
+        ext.get().conv3ds_bwd(c, 13)
         assert C.version == "1.0" and not hasattr(C, "missing")  # non-callables and hasattr pass through
     assert rec.records == ["launch(a0,a1,0,392,1e-05,True,None,%d)" % ((1 << 40) - 1),
                            "launch(a1,a2,a0,flag=a1)",
-                           "c3ds.conv3ds_bwd(a2,13)"]
+                           "conv3ds_bwd(a2,13)"]
     assert [c[0] for c in calls] == ["launch", "launch", "c3ds"] and calls[0][1][0] == b
     assert all(c.startswith("test_launch_trace.py:") for c in rec.callers)
 
@@ -52,12 +52,12 @@ def test_lists_go_element_by_element(lt):
 
 def test_originals_are_restored(lt):
     ext, mod, _ = _fake()
-    get, c3ds = ext.get, ext.c3ds
+    get = ext.get
     with pytest.raises(ZeroDivisionError):
         with lt.recording(lt.Recorder(), ext, vendor=False):
             assert ext.get is not get and ext.get() is not mod
             1 / 0
-    assert ext.get is get and ext.c3ds is c3ds and ext.get() is mod
+    assert ext.get is get and ext.get() is mod
 
 
 def test_vendor_calls_are_restored(lt):
