@@ -606,4 +606,26 @@ void gelu_set_form(int tanh_form);
 void gelu_fwd(const void* h, void* g, int64_t n, int dtype, hipStream_t stream);
 int gelu_form();
 
+// ---- fused softmax cross-entropy (csrc/kernels/xent.hip) --------------------------------------
+// Logits x [B, C] contiguous (dtype bf16 / fp16 / fp32), arithmetic fp32. mode 0 hard labels, 1 mixed
+// labels (partner row B - 1 - b; lam by value, or read from dev_lam when not null), 2 dense targets
+// [B, C] (target_dtype fp32 / bf16 / fp16). labels: int32 / int64 (label_dtype), compared and never
+// used as an address; in mode 2 they are optional and serve the rank only. eps: label smoothing in
+// [0, 1). None of the three allocates, copies or synchronises.
+// forward: loss_row, m (row max), s (sum of exp(x - m)) per row in fp32; rank (optional, needs
+// labels): the number of classes that beat the row's label, ties broken towards the lower index.
+void xent_fwd(const void* x, const void* labels, const void* target, float* loss_row, float* m, float* s,
+              int32_t* rank, int64_t B, int64_t C, int dtype, int label_dtype, int target_dtype, int mode, float eps,
+              float lam, const float* dev_lam, hipStream_t stream);
+// One workgroup: loss[0] = sum_b loss_row[b] in a fixed order (reduction 1), times fl32(1/B)
+// (reduction 0); loss may be null. meter (optional, needs rank): 8 words {fp64 sum of the row
+// losses, int64 rows, int64 #(rank < k0), int64 #(rank < k1)}, the batch added by one thread.
+void xent_finish(const float* loss_row, const int32_t* rank, float* loss, void* meter, int64_t B, int reduction,
+                 int k0, int k1, hipStream_t stream);
+// backward: dx = (softmax(x) W - t) gs in x's dtype, one rounding; gs = g[0] fl32(1/B) (reduction 0),
+// g[0] (1) or g[row] (2), g read on the device.
+void xent_bwd(const void* x, const void* labels, const void* target, const float* m, const float* s, const float* g,
+              void* dx, int64_t B, int64_t C, int dtype, int label_dtype, int target_dtype, int mode, int reduction,
+              float eps, float lam, const float* dev_lam, hipStream_t stream);
+
 }  // namespace fluxmpi

@@ -376,3 +376,19 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("size", &RcclComm::size)
       .def_property_readonly("device", &RcclComm::device);
 }
+
+// A second module of the same shared object (loaded from _C.__file__ by ops/_ext.py: xent()): the
+// fused softmax cross-entropy entries, beside `_C` so that its recorded surface stays as it is.
+PYBIND11_MODULE(_C_xent, m) {
+  m.doc() = "fluxmpi_amd native library: the fused softmax cross-entropy entries (csrc/kernels/xent.hip)";
+  m.def("xent_fwd", raw(&xent_fwd), py::arg("x"), py::arg("labels"), py::arg("target"), py::arg("loss_row"),
+        py::arg("m"), py::arg("s"), py::arg("rank"), py::arg("B"), py::arg("C"), py::arg("dtype"),
+        py::arg("label_dtype"), py::arg("target_dtype"), py::arg("mode"), py::arg("eps"), py::arg("lam"),
+        py::arg("dev_lam"), py::arg("stream"));
+  m.def("xent_finish", raw(&xent_finish), py::arg("loss_row"), py::arg("rank"), py::arg("loss"), py::arg("meter"),
+        py::arg("B"), py::arg("reduction"), py::arg("k0"), py::arg("k1"), py::arg("stream"));
+  m.def("xent_bwd", raw(&xent_bwd), py::arg("x"), py::arg("labels"), py::arg("target"), py::arg("m"), py::arg("s"),
+        py::arg("g"), py::arg("dx"), py::arg("B"), py::arg("C"), py::arg("dtype"), py::arg("label_dtype"),
+        py::arg("target_dtype"), py::arg("mode"), py::arg("reduction"), py::arg("eps"), py::arg("lam"),
+        py::arg("dev_lam"), py::arg("stream"));
+}

@@ -1,6 +1,7 @@
 """Training from a uint8 image set: a rank's shard of the bytes goes through the device input pipeline
-(random crop, flip, normalise, NHWC bf16, the stem's 4-channel format, mixup with soft targets) in one
-kernel per batch, then through ResNet under the DDP engine.
+(random crop, flip, normalise, NHWC bf16, the stem's 4-channel format, mixup) in one kernel per batch, then
+through ResNet under the DDP engine. The mixed labels go to the fused loss as two integer labels and lam
+(no dense target); the running loss and top-1 / top-5 counts stay on the device and are read every 10 steps.
 
 Run:  torchrun --nproc-per-node 8 examples/train_augment.py --model resnet50 --batch 256 --steps 100
       python -m fluxmpi_amd.launch -n 2 examples/train_augment.py --model resnet_tiny --batch 8 --image 32 (CPU)
@@ -12,7 +13,6 @@ import argparse
 import time
 
 import torch
-import torch.nn.functional as F
 
 import fluxmpi_amd as FluxMPI
 from fluxmpi_amd import optimisers as O
@@ -57,27 +57,34 @@ per_epoch = max(1, len(shard_x) // args.batch)
 # different crops from the one seed (sample_offset = local_rank * batch)
 aug = FluxMPI.DeviceAugment(args.image, channels=4 if dev.type == "cuda" else 3,
                             dtype=torch.bfloat16, seed=0, mixup_alpha=args.mixup, cutmix_alpha=args.cutmix,
-                            label_smoothing=args.smoothing, num_classes=classes)
+                            label_smoothing=args.smoothing, num_classes=classes, targets="labels")
+meter = FluxMPI.ClassificationMeter(topk=(1, 5))
 
 t0 = time.time()
 for step in range(args.steps):
     lo = (step % per_epoch) * args.batch
     u8 = shard_x[lo:lo + args.batch].to(dev, non_blocking=True)  # the bytes: 1/4 of the bf16 batch
     y = shard_y[lo:lo + args.batch].to(dev, non_blocking=True)
-    x, soft = aug(u8, y)  # [B, C, h, w] channels_last, [B, classes] fp32
+    x, target = aug(u8, y)  # [B, C, h, w] channels_last; MixedLabels(labels, lam, smoothing)
     if dev.type != "cuda":
         x = x.float()
-    loss = F.cross_entropy(ddp(x).float(), soft)
+    loss = FluxMPI.softmax_cross_entropy(ddp(x), target, meter=meter)  # the meter takes the batch in on the device
     loss.backward()
     ddp.step()
-    if step % 10 == 0:
-        FluxMPI.fluxmpi_println(f"step {step} loss {loss.item():.4f} (mix {aug.draw(step)})")
+    if step % 10 == 9 or step == args.steps - 1:  # the only host read of the loop
+        r = meter.read()
+        FluxMPI.fluxmpi_println(f"step {step} loss {r['loss']:.4f} top1 {r['top1']:.3f} top5 {r['top5']:.3f} "
+                                f"over {r['rows']} samples (mix {aug.draw(step)})")
+        meter.reset()
 
 model.eval()
 with torch.no_grad():  # evaluation: the centre crop, no flip, no mix
     x, y = aug.eval()(shard_x[0:args.batch].to(dev), shard_y[0:args.batch].to(dev))
-    acc = (ddp(x if dev.type == "cuda" else x.float()).argmax(1) == y).float().mean().item()
-FluxMPI.fluxmpi_println(f"centre-crop accuracy on a training batch {acc:.3f}")
+    meter.reset()
+    FluxMPI.softmax_cross_entropy(ddp(x if dev.type == "cuda" else x.float()), y, meter=meter)
+    r = meter.read(reduce=True)  # summed over the ranks
+FluxMPI.fluxmpi_println(f"centre-crop on a training batch: loss {r['loss']:.4f} top1 {r['top1']:.3f} "
+                        f"top5 {r['top5']:.3f} over {r['rows']} samples")
 if FluxMPI.local_rank() == 0:
     print(f"{args.steps * args.batch * FluxMPI.total_workers() / (time.time() - t0):.1f} samples/s")
 FluxMPI.Finalize()

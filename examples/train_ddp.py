@@ -7,7 +7,6 @@ import argparse
 import time
 
 import torch
-import torch.nn.functional as F
 
 import fluxmpi_amd as FluxMPI
 from fluxmpi_amd import optimisers as O
@@ -53,7 +52,7 @@ timer = StepTimer(dev)
 t0 = time.time()
 for step in range(args.steps):
     with timer.phase("forward"):
-        loss = F.cross_entropy(ddp(x).float(), y)
+        loss = FluxMPI.softmax_cross_entropy(ddp(x), y)  # bf16 logits as they are, fp32 loss
     with timer.phase("backward"):
         loss.backward()
     with timer.phase("optimizer"):
@@ -68,9 +67,9 @@ if args.ema is not None:
     # afterwards the training weights are back bit for bit (ddp.ema_state_dict() is what to checkpoint)
     model.eval()
     with torch.no_grad():
-        live = F.cross_entropy(ddp(x).float(), y).item()
+        live = FluxMPI.softmax_cross_entropy(ddp(x), y).item()
         with ddp.ema_weights():
-            avg = F.cross_entropy(ddp(x).float(), y).item()
+            avg = FluxMPI.softmax_cross_entropy(ddp(x), y).item()
     model.train()
     FluxMPI.fluxmpi_println(f"eval loss {live:.4f}, with the averaged weights {avg:.4f} "
                             f"({int(ddp.ema_updates())} EMA updates, decay now {float(ddp.ema_decay()):.4f})")

@@ -32,6 +32,8 @@ from .parallel import (COMM_WORLD, Barrier, DistributedDataContainer, Distribute
 from .parallel.ddp import EMA, LossScale  # noqa: F401
 from .ops.syncbn import SyncBatchNorm2d, convert_sync_batchnorm, sync_batch_norm  # noqa: F401
 from .ops.augment import DeviceAugment  # noqa: F401
+from .ops.xent import (ClassificationMeter, MixedLabels, SoftmaxCrossEntropy, softmax_cross_entropy,  # noqa: F401
+                       xent_reference)
 from .utils.config import disable_cudampi_support  # noqa: F401
 from .utils.errors import FluxMPINotInitializedError  # noqa: F401
 
@@ -60,4 +62,5 @@ __all__ = [
     "allgather", "reduce_scatter", "COMM_WORLD", "ReduceOp", "disable_cudampi_support",
     "FluxMPINotInitializedError", "optimisers", "build", "barrier", "Barrier", "device", "backend_name",
     "SyncBatchNorm2d", "convert_sync_batchnorm", "sync_batch_norm", "LossScale", "EMA", "DeviceAugment",
+    "softmax_cross_entropy", "xent_reference", "SoftmaxCrossEntropy", "ClassificationMeter", "MixedLabels",
 ]

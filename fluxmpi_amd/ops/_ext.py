@@ -9,7 +9,9 @@
 * the native RCCL communicator (``csrc/comm/rccl_comm.cpp``).
 
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
-(``tests/test_bindings_surface.py`` says what may change in its surface).
+(``tests/test_bindings_surface.py`` says what may change in its surface). The one exception is
+:func:`xent`: the fused softmax cross-entropy entries are a second pybind11 module of the same
+shared object, ``_C_xent``, until ``_C``'s recorded surface is next re-recorded.
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -25,6 +27,7 @@ and as the numerics oracle in tests.
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import os
 
 import torch
@@ -75,6 +78,29 @@ def get(required: bool = True):
             f"{_ERR!r}. Run `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`."
         )
     return mod
+
+
+_XENT = None
+
+
+def xent():
+    """The ``_C_xent`` module (``xent_fwd``, ``xent_finish``, ``xent_bwd``; ``csrc/kernels/xent.hip``):
+    the ``PyInit__C_xent`` of the shared object ``_C`` was loaded from. Missing: an error, as for ``_C``."""
+    global _XENT
+    if _XENT is None:
+        C = get(required=True)
+        if C is None:
+            raise NativeExtensionError("fluxmpi_amd._C_xent needs the native extension fluxmpi_amd._C")
+        spec = importlib.util.spec_from_file_location("fluxmpi_amd._C_xent", C.__file__)
+        try:
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        except Exception as e:
+            raise NativeExtensionError(
+                f"fluxmpi_amd._C_xent (the cross-entropy entries of {C.__file__}) failed to load: {e!r}. "
+                "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
+        _XENT = mod
+    return _XENT
 
 
 def require_for(t: torch.Tensor):

@@ -42,6 +42,7 @@ from ._launch import ptr as _ptr
 from ._launch import stream as _stream
 from .multi_tensor import DTYPE_CODE
 from .philox import philox4x32
+from .xent import MixedLabels
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -340,7 +341,10 @@ class DeviceAugment:
     ``images``: ``uint8 [B, H, W, 3]``; ``x``: the ``[B, channels, h, w]`` channels_last batch of
     :func:`augment_batch` (random crop of ``size`` from the image zero-extended by ``pad``, flip,
     normalise, and the batch's mixup / cutmix). ``y``: ``labels`` untouched when nothing mixes and
-    ``label_smoothing == 0``, else the soft targets ``[B, num_classes]`` of :func:`mix_targets`.
+    ``label_smoothing == 0``, else the soft targets ``[B, num_classes]`` of :func:`mix_targets`
+    (``targets="dense"``, the default) or, with ``targets="labels"``, ``MixedLabels(labels, lam,
+    label_smoothing)`` for :func:`..xent.softmax_cross_entropy`: ``lam`` the float of the draw, or the
+    block's device word under ``use_block=True``; no dense matrix is built.
 
     ``step`` defaults to an internal counter that advances once per call; ``sample_offset`` defaults
     to ``local_rank() * B`` once ``Init()`` ran (ranks draw different crops from one seed), else 0.
@@ -355,7 +359,10 @@ class DeviceAugment:
 
     def __init__(self, size, *, pad=0, fill=0, flip=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, channels=3,
                  dtype=torch.bfloat16, seed=0, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5,
-                 label_smoothing=0.0, num_classes=None):
+                 label_smoothing=0.0, num_classes=None, targets="dense"):
+        if targets not in ("dense", "labels"):
+            raise ValueError(f"DeviceAugment: targets is 'dense' or 'labels', got {targets!r}")
+        self.targets = targets
         self.size = (int(size), int(size)) if isinstance(size, int) else tuple(int(v) for v in size)
         if len(self.size) != 2 or min(self.size) < 1:
             raise ValueError(f"DeviceAugment: size is a positive int or (h, w), got {size!r}")
@@ -368,7 +375,7 @@ class DeviceAugment:
         if not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"DeviceAugment: label_smoothing must lie in [0, 1), got {label_smoothing}")
         self.mixes = mixup_alpha > 0 or cutmix_alpha > 0
-        if (self.mixes or label_smoothing > 0) and num_classes is None:
+        if (self.mixes or label_smoothing > 0) and num_classes is None and targets == "dense":
             raise ValueError("DeviceAugment: mixup / cutmix / label smoothing form soft targets: give num_classes")
         _check_ids("DeviceAugment", seed, 0, 0)
         norm_constants(mean, std)
@@ -442,6 +449,8 @@ class DeviceAugment:
             return None
         if not self.mixes and self.label_smoothing == 0:
             return labels
+        if self.targets == "labels":
+            return MixedLabels(labels, lam, self.label_smoothing)
         return mix_targets(labels, self.num_classes, lam, self.label_smoothing)
 
     def __call__(self, images, labels=None, step=None, *, sample_offset=None, use_block=False, out=None):
