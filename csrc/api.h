@@ -410,6 +410,9 @@ void gemm_bf16(const GemmProblem& g, hipStream_t stream);
 // xhat ([256] fp32, bn_bwd's dbias / dweight); b = W [256][64] as stored (N-major, ldb = 64);
 // res = a2 [M][64] (ldr = 64); ldc = 64. splits = the slab count = the workgroups launched, the
 // caller's choice: min(ceil(M / 64), 2 x compute units) fills the device with one round.
+// The same with N = 128, K = 512 (a stage-2 identity block's 128 -> 512; every 64 / 256 above doubled)
+// runs conv3bn3_s2_bwd.hip: one workgroup per compute unit, so splits = min(ceil(M / 32), compute units).
+// Any other (N, K) throws.
 void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream);
 // conv3ds_bwd.hip: the same around the dual BatchNorm of a stage-1 downsample block,
 // out = relu(bn3(conv3(a2)) + bn_ds(conv_ds(x))), both convolutions 1x1, 64 -> 256, stride 1. One pass

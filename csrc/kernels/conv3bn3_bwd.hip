@@ -27,6 +27,8 @@
 // A workgroup stores its dW partial as one fp32 slab ws[blockIdx.x][256][64] (plain stores; a
 // workgroup without tiles stores zeros) and gemm_splitk_reduce sums the slabs: no float atomics,
 // no grid barrier. Rows past P are zero in both tiles, so the partial last tile adds nothing.
+// The stage-2 form (128 -> 512, one workgroup per CU) is conv3bn3_s2_bwd.hip; conv3bn3_bwd below checks
+// the problem for both and launches the one that (N, K) names.
 #include <stdexcept>
 #include <string>
 
@@ -55,22 +57,6 @@ static_assert(kThreads == kCo, "one lane per channel computes the coefficients")
 constexpr int kRpi = kThreads / (kCo / 8);  // rows of a tile the workgroup covers at once (8)
 constexpr int kRows = kTP / kRpi;           // rows of a tile per lane (4)
 constexpr int kAv = kTP * (kCi / 8) / kThreads;  // a2 vectors of a tile per lane (1)
-
-struct C3Args {
-  const bf16* dy;       // [P][256]
-  const bf16* x3;       // [P][256]
-  const uint8_t* mask;  // [P * 256 / 8]
-  const float* w;       // bn3 weight (nullable: 1)
-  const float* mean;
-  const float* inv;
-  const float* sum_dy;       // [256] = dbias
-  const float* sum_dy_xhat;  // [256] = dweight
-  const bf16* a2;            // [P][64]
-  const bf16* wt;            // conv3 filter [256][64]
-  bf16* d_a2;                // [P][64]
-  float* ws;                 // [gridDim.x][256][64]
-  int64_t P;
-};
 
 __device__ __forceinline__ void ld4(const float* __restrict__ p, float* v) {
   const float4 a = *reinterpret_cast<const float4*>(p);
@@ -247,11 +233,13 @@ __global__ __launch_bounds__(kThreads, 2) void conv3bn3_bwd_kernel(C3Args p) {
 }  // namespace
 
 void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream) {
-  if (g.N != kCi || g.K != kCo || g.M < 1 || g.lda != kCo || g.ldb != kCi || g.ldc != kCi || g.ldr != kCi ||
+  // (N, K) = (Cin, Cout): (64, 256) here, (128, 512) in conv3bn3_s2_bwd.hip
+  const bool s2 = g.N == 128 && g.K == 512;
+  if (!((g.N == kCi && g.K == kCo) || s2) || g.M < 1 || g.lda != g.K || g.ldb != g.N || g.ldc != g.N || g.ldr != g.N ||
       !g.a_kmajor || g.b_kmajor || g.bnb_rm != 3)
-    throw std::runtime_error("gemm_bf16 mode 4: needs N = 64, K = 256, dense operands (lda = 256, ldb = ldc = ldr = 64), "
-                             "K-major A, N-major B and the 1-bit ReLU mask (bnb_rm = 3); got M=" + std::to_string(g.M) +
-                             ", N=" + std::to_string(g.N) + ", K=" + std::to_string(g.K));
+    throw std::runtime_error("gemm_bf16 mode 4: needs (N, K) = (64, 256) or (128, 512), dense operands (lda = K, ldb = "
+                             "ldc = ldr = N), K-major A, N-major B and the 1-bit ReLU mask (bnb_rm = 3); got M=" +
+                             std::to_string(g.M) + ", N=" + std::to_string(g.N) + ", K=" + std::to_string(g.K));
   if (g.a == nullptr || g.b == nullptr || g.c == nullptr || g.res == nullptr || g.bnb_x == nullptr ||
       g.bnb_mask == nullptr || g.bnb_mean == nullptr || g.bnb_inv == nullptr || g.a_scale == nullptr ||
       g.a_shift == nullptr || g.stats == nullptr)
@@ -267,10 +255,11 @@ void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream) {
   // (more workgroups than tiles is allowed: the extra ones store zero slabs)
   if (g.splits < 1 || g.splits > 65535)
     throw std::runtime_error("gemm_bf16 mode 4: splits (the slab count = workgroups) must be in [1, 65535]");
-  allow_dynamic_lds(reinterpret_cast<const void*>(&conv3bn3_bwd_kernel), kSmem);
   C3Args p{static_cast<const bf16*>(g.a), static_cast<const bf16*>(g.bnb_x), g.bnb_mask, g.bnb_w, g.bnb_mean,
            g.bnb_inv, g.a_scale, g.a_shift, static_cast<const bf16*>(g.res), static_cast<const bf16*>(g.b),
            static_cast<bf16*>(g.c), g.stats, g.M};
+  if (s2) return conv3bn3_s2_launch(p, g.splits, stream);
+  allow_dynamic_lds(reinterpret_cast<const void*>(&conv3bn3_bwd_kernel), kSmem);
   conv3bn3_bwd_kernel<<<static_cast<unsigned>(g.splits), kThreads, kSmem, stream>>>(p);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }

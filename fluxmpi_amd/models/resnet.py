@@ -206,7 +206,7 @@ class Bottleneck(nn.Module):
                         a2 = fb.bn_from_stats(c2, self.bn2, relu=True, stats_ready=ours)
                     o3 = c3 is not None or fb.conv1x1_forward_is_ours(a2, self.conv3.weight)
                     if self.downsample is None and fb.conv3bn3_ok(a2, self.conv3, self.bn3, identity, link):
-                        # stage-1 identity block: conv3 -> bn3 as one node, whose backward forms bn3's
+                        # stage-1 / stage-2 identity block: conv3 -> bn3 as one node, whose backward forms bn3's
                         # input gradient in registers (one pass instead of dx + dgrad + wgrad)
                         return fb.conv3_bn3_relu(a2, self.conv3, self.bn3, identity, link, ours_fwd=o3, c3=c3)
                     if c3ds:

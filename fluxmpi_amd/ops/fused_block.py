@@ -419,19 +419,20 @@ def bn_relu_conv3(c2, bn, conv, stats_ready=True):
 
 
 class _Conv3BN3(torch.autograd.Function):
-    """out = relu(bn3(conv3(a2)) + residual) of a stage-1 identity block (1x1, 64 -> 256), whose
-    backward never materialises bn3's input gradient dx3. Forward: exactly the launches of
-    ``conv1x1_hybrid(ours_stats=True)`` + ``bn_from_stats``. Backward: bn3's reduce + finalize
-    (``bn_bwd`` without a dx), then one kernel (``gemm_bf16`` mode 4, csrc/kernels/conv3bn3_bwd.hip)
-    that streams (dy, c3, mask, a2) once, forms dx3 in registers and produces d_a2 = dx3 . W and
-    the per-workgroup partials of dW = dx3^T . a2, then the split-K reduce into the filter's
-    gradient. Unfused, dx3 (the network's largest activation size) is written once and read twice.
+    """out = relu(bn3(conv3(a2)) + residual) of a stage-1 or stage-2 identity block (1x1, 64 -> 256 or
+    128 -> 512: the shape is the filter's), whose backward never materialises bn3's input gradient dx3.
+    Forward: exactly the launches of ``conv1x1_hybrid(ours_stats=True)`` + ``bn_from_stats``. Backward: bn3's
+    reduce + finalize (``bn_bwd`` without a dx), then one kernel (``gemm_bf16`` mode 4,
+    csrc/kernels/conv3bn3_bwd.hip or conv3bn3_s2_bwd.hip) that streams (dy, c3, mask, a2) once, forms dx3
+    in registers and produces d_a2 = dx3 . W and the per-workgroup partials of dW = dx3^T . a2, then the
+    split-K reduce into the filter's gradient. Unfused, dx3 (the network's largest activation size) is
+    written once and read twice.
 
     The filter gradient always comes from the one-pass kernel: there is no per-shape choice as
-    ``wgrad_best`` makes for the unfused path. That is measured at ResNet-50's 56 x 56, batch 256 only
-    (``profiles/c3b3_conv3bn3.md``); :func:`conv3bn3_ok` admits any N, H, W, and at few pixels the kernel
-    runs few workgroups, each loading the 32 KiB filter first, which nobody has timed against the
-    unfused kernels."""
+    ``wgrad_best`` makes for the unfused path. That is measured at ResNet-50's 56 x 56 and 28 x 28, batch 256
+    only (``profiles/c3b3_conv3bn3.md``, ``profiles/c3b3s2_conv3bn3_s2.md``); for 64 -> 256
+    :func:`conv3bn3_ok` admits any N, H, W, and at few pixels the kernel runs few workgroups, each loading
+    the 32 KiB filter first, which nobody has timed against the unfused kernels (128 -> 512 is gated)."""
 
     @staticmethod
     def forward(ctx, a2, weight, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, nbt, link,
@@ -456,8 +457,8 @@ class _Conv3BN3(torch.autograd.Function):
         n, ci, h, w = a2.shape
         # reduce + finalize only (no dx, no dres): the two finished sums land in dbw / dbb
         _, _, dbw, dbb = launch_bwd(dy, c3, mask, w32, b32, mean, inv, True, params=ctx.params, want_dx=False)
-        part = torch.empty(conv3bn3_slabs(n * h * w, dy.device), weight.shape[0], ci, device=dy.device,
-                           dtype=torch.float32)
+        part = torch.empty(conv3bn3_slabs(n * h * w, dy.device, weight.shape[0]), weight.shape[0], ci,
+                           device=dy.device, dtype=torch.float32)
         d_a2 = _one_pass_branch(dy, mask, c3, w32, mean, inv, (dbb, dbw), a2, weight, part, _empty_nhwc(n, ci, h, w, a2))
         dw = _slabs_to_wgrad(part, weight) if ctx.needs_input_grad[1] else None
         # the residual's gradient travels as (dy, mask): conv1's dgrad epilogue applies the mask
@@ -467,8 +468,8 @@ class _Conv3BN3(torch.autograd.Function):
 
 def _one_pass_branch(dy, mask, c, w32, mean, inv, sums, act, weight, part, out):
     """One branch of the one-pass backward around a BatchNorm after a 1x1 convolution (``gemm_bf16`` mode 4,
-    csrc/kernels/conv3bn3_bwd.hip): streams (dy, c, mask, act) once, forms the BatchNorm's input gradient in
-    registers from its finished ``sums`` = (sum dy, sum dy xhat), writes ``out`` = d_act = dx . W and one fp32
+    csrc/kernels/conv3bn3_bwd.hip for 64 -> 256, conv3bn3_s2_bwd.hip for 128 -> 512): streams (dy, c, mask, act)
+    once, forms the BatchNorm's input gradient in registers from its finished ``sums`` = (sum dy, sum dy xhat), writes ``out`` = d_act = dx . W and one fp32
     partial of dW = dx^T . act per workgroup into the slab set ``part`` [slabs, Cout, Cin]."""
     co, ci = weight.shape[0], weight.shape[1]
     return gemm(dy, weight, out, M=act.numel() // ci, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False,
@@ -487,16 +488,18 @@ def _slabs_to_wgrad(part, weight):
     return dw.view(co, ci, 1, 1)
 
 
-# the one-pass conv3 -> bn3 backward of the stage-1 identity blocks (FLUXMPI_CONV3BN3=0: the
-# separate dx pass + input-gradient GEMM + weight-gradient kernel)
-CONV3BN3 = os.environ.get("FLUXMPI_CONV3BN3", "1") != "0"
+# the one-pass conv3 -> bn3 backward of the identity blocks (FLUXMPI_CONV3BN3=0: the separate dx pass +
+# input-gradient GEMM + weight-gradient kernel everywhere; 1: one pass in stage 1 (64 -> 256) only; 2, the
+# default: in stage 2 (128 -> 512) as well, profiles/c3b3s2_conv3bn3_s2.md)
+CONV3BN3 = int(os.environ.get("FLUXMPI_CONV3BN3", "2"))
 
 
-def conv3bn3_slabs(rows: int, device) -> int:
-    """Workgroups (= fp32 partial slabs) of the mode-4 kernel: one resident round, two
-    workgroups per compute unit, never more than the 32-pixel tiles there are."""
+def conv3bn3_slabs(rows: int, device, cout: int = 256) -> int:
+    """Workgroups (= fp32 partial slabs) of the mode-4 kernel: one resident round, never more than the
+    32-pixel tiles there are. 64 -> 256: two workgroups per compute unit; 128 -> 512 (``cout`` 512): one, its
+    filter-gradient accumulator being half of a compute unit's registers."""
     cus = torch.cuda.get_device_properties(device).multi_processor_count
-    return max(1, min(-(-rows // 32), 2 * cus))
+    return max(1, min(-(-rows // 32), cus if cout == 512 else 2 * cus))
 
 
 def _fused_bn_training(*bns) -> bool:
@@ -506,17 +509,35 @@ def _fused_bn_training(*bns) -> bool:
     return all(isinstance(m, FusedBatchNorm2d) and m.training and m.affine and m.track_running_stats for m in bns)
 
 
+def conv3bn3_admits(filter_shape, pixels: int, cus: int) -> bool:
+    """The shape part of :func:`conv3bn3_ok` under the ``CONV3BN3`` switch: the (256, 64, 1, 1) filter at any
+    pixel count from switch value 1; the (512, 128, 1, 1) filter from value 2, and only with at least 64
+    pixels per compute unit (``cus``)."""
+    if tuple(filter_shape) == (256, 64, 1, 1):
+        return CONV3BN3 >= 1
+    if tuple(filter_shape) == (512, 128, 1, 1):
+        return CONV3BN3 >= 2 and pixels >= 32 * 2 * cus
+    return False
+
+
 def conv3bn3_ok(a2, conv, bn, residual, link) -> bool:
-    """:func:`conv3_bn3_relu` applies: bf16 NHWC, the 64 -> 256 1x1 convolution, a training-mode
-    affine fused BatchNorm, and a residual whose gradient travels as (dy, mask) through a masked
-    :class:`GradLink` (or is not needed)."""
+    """:func:`conv3_bn3_relu` applies: bf16 NHWC, the 64 -> 256 1x1 convolution (``CONV3BN3`` >= 1) or the
+    128 -> 512 one (``CONV3BN3`` >= 2), a training-mode affine fused BatchNorm, and a residual whose gradient
+    travels as (dy, mask) through a masked :class:`GradLink` (or is not needed). 128 -> 512 also needs at least
+    64 pixels per compute unit (the gate of :func:`bn2conv3_ok`): its kernel is one workgroup per compute unit,
+    each forming the 128 KiB filter's fragments first, and nobody has timed that against the unfused kernels
+    at fewer pixels."""
     wt = conv.weight
-    return (CONV3BN3 and G.ENGINE != 1 and a2.is_cuda and a2.dim() == 4 and a2.dtype == torch.bfloat16
-            and wt.dtype == torch.bfloat16 and tuple(wt.shape) == (256, 64, 1, 1) and wt.is_contiguous()
-            and a2.shape[1] == 64 and a2.numel() // 64 < 2 ** 31 and residual is not None
-            and residual.shape == (a2.shape[0], 256, a2.shape[2], a2.shape[3]) and residual.dtype == a2.dtype
+    co, ci = wt.shape[0], wt.shape[1]
+    if not (G.ENGINE != 1 and a2.is_cuda and a2.dim() == 4 and a2.dtype == torch.bfloat16
+            and wt.dtype == torch.bfloat16 and wt.is_contiguous()
+            and a2.shape[1] == ci and a2.numel() // ci < 2 ** 31 and residual is not None
+            and residual.shape == (a2.shape[0], co, a2.shape[2], a2.shape[3]) and residual.dtype == a2.dtype
             and (link.masked if link is not None else not (residual.requires_grad and torch.is_grad_enabled()))
-            and _fused_bn_training(bn))
+            and _fused_bn_training(bn)):
+        return False
+    return conv3bn3_admits(tuple(wt.shape), a2.numel() // ci,
+                           torch.cuda.get_device_properties(a2.device).multi_processor_count)
 
 
 def conv3_bn3_relu(a2, conv, bn, residual, link=None, ours_fwd=True, c3=None):
