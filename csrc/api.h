@@ -208,6 +208,19 @@ void augment_batch(const void* in, void* out, int64_t B, int H, int W, int h, in
 void aug_block_set(void* block, uint32_t step, int mode, int y0, int x0, int y1, int x1, float lam,
                    hipStream_t stream);
 
+// ---- device input pipeline, resampling form (resize_crop.hip): per-sample box -> bilinear resize ----
+// As augment_batch, with the crop given per sample: boxes int32 [B][5] = (top, left, bh, bw, flip) on
+// the device, a box inside the image (it is clamped to it before use: top into [0, H - 1], bh into
+// [1, H - top], columns likewise, flip & 1). Sides H, W, h, w <= 16384. Output column j, j' = w - 1 - j
+// under a flip: num = (2 j' + 1) bw - w, den = 2 w; num < 0: x0 = 0, fx = 0; else x0 = num / den, fx =
+// ((num % den) * 2048 + w) / den; x1 = min(x0 + 1, bw - 1). Rows likewise with (i, bh, h), no flip.
+// Per channel, from the four bytes at rows top + y0 / y1, columns left + x0 / x1: t0 = p00 (2048 - fx)
+// + p01 fx, t1 likewise, v = (t0 (2048 - fy) + t1 fy + 2^21) >> 22 (half-pixel centres, no antialias,
+// 11-bit weights). From the byte v on: augment_batch's arithmetic, the partner B - 1 - b with its own
+// box. Of AugHyper the mixing fields, a, b and dev_block apply; pad and fill must be 0.
+void resized_crop_batch(const void* in, void* out, const int32_t* boxes, int64_t B, int H, int W, int h, int w, int C,
+                        int dtype, const AugHyper& a, hipStream_t stream);
+
 // ---- BatchNorm (NHWC, channels innermost) + ReLU / residual-add fusions ----------
 // Training forward: per-channel batch statistics over rows = N*H*W, then
 //   y = act(x * scale_c + shift_c [+ residual]).

@@ -392,3 +392,25 @@ PYBIND11_MODULE(_C_xent, m) {
         py::arg("target_dtype"), py::arg("mode"), py::arg("reduction"), py::arg("eps"), py::arg("lam"),
         py::arg("dev_lam"), py::arg("stream"));
 }
+
+// A third module of the same shared object, loaded the same way: the resampling form of the device
+// input pipeline (csrc/kernels/resize_crop.hip). `mode`, `box`, `lam`, `a`, `b` and `dev_block` are
+// AugHyper's; `boxes` is the device table int32 [B][5].
+PYBIND11_MODULE(_C_rrc, m) {
+  m.doc() = "fluxmpi_amd native library: the resized-crop entry (csrc/kernels/resize_crop.hip)";
+  m.def(
+      "resized_crop_batch",
+      [](uintptr_t in, uintptr_t out, uintptr_t boxes, int64_t B, int H, int W, int h, int w, int C, int dtype,
+         uint32_t step, int mode, std::array<int, 4> box, float lam, std::array<float, 3> a, std::array<float, 3> b,
+         uintptr_t dev_block, uintptr_t stream) {
+        AugHyper hy{};
+        hy.step = step, hy.mode = mode, hy.y0 = box[0], hy.x0 = box[1], hy.y1 = box[2], hy.x1 = box[3], hy.lam = lam;
+        for (int c = 0; c < 3; ++c) hy.a[c] = a[c], hy.b[c] = b[c];
+        hy.dev_block = ptr<const uint32_t*>(dev_block);
+        resized_crop_batch(ptr<const void*>(in), ptr<void*>(out), ptr<const int32_t*>(boxes), B, H, W, h, w, C, dtype,
+                           hy, ptr<hipStream_t>(stream));
+      },
+      py::arg("input"), py::arg("out"), py::arg("boxes"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("h"),
+      py::arg("w"), py::arg("C"), py::arg("dtype"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"),
+      py::arg("a"), py::arg("b"), py::arg("dev_block"), py::arg("stream"));
+}

@@ -25,14 +25,13 @@
 #include "augment_host.h"
 #include "common.h"
 #include "optim_sr.h"
+// last: it turns contraction off for what follows
+#include "augment_device.h"
 
 #pragma clang fp contract(off)
 
 namespace fluxmpi {
 namespace {
-
-// words of the device block (api.h: aug_block_set)
-constexpr int kAugStep = 0, kAugMode = 1, kAugY0 = 2, kAugX0 = 3, kAugY1 = 4, kAugX1 = 5, kAugLam = 6;
 
 struct AugArgs {
   const uint8_t* in;
@@ -49,21 +48,6 @@ struct AugArgs {
   float a[3], b[3];
   int rows, row_blocks, row_bytes, chunks, sets, stage_shift, item_shift;
 };
-
-// what a launch mixes with, wave-uniform
-struct Mix {
-  uint32_t step;
-  int mode, y0, x0, y1, x1;
-  float lam;
-};
-
-__device__ __forceinline__ Mix mix_of(const AugArgs& k) {
-  const uint32_t* __restrict__ blk = k.dev_block;
-  if (blk == nullptr) return {k.step, k.mode, k.y0, k.x0, k.y1, k.x1, k.lam};
-  return {blk[kAugStep], static_cast<int>(blk[kAugMode]), static_cast<int>(blk[kAugY0]),
-          static_cast<int>(blk[kAugX0]), static_cast<int>(blk[kAugY1]), static_cast<int>(blk[kAugX1]),
-          __builtin_bit_cast(float, blk[kAugLam])};
-}
 
 // a sample's draws: source pixel of output (i, j) = (i + oy, (flip ? w - 1 - j : j) + ox)
 struct Sample {
@@ -113,20 +97,6 @@ __device__ __forceinline__ RowSrc row_src(const AugArgs& k, const Sample& s, int
   return r;
 }
 
-// one aligned 16-byte chunk of the batch; the bytes of it that lie outside the tensor read as 0
-// (they are never picked) and are not loaded
-__device__ __forceinline__ uint4 load_chunk(const AugArgs& k, const uint8_t* p) {
-  const uint8_t* end = k.in + k.in_bytes;
-  if (p >= k.in && p + 16 <= end) return *reinterpret_cast<const uint4*>(p);
-  uint32_t v[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int t = 0; t < 16; ++t) {
-    const uint8_t* q = p + t;
-    if (q >= k.in && q < end) v[t >> 2] |= static_cast<uint32_t>(*q) << (8 * (t & 3));
-  }
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
 __device__ __forceinline__ void stage_row(const AugArgs& k, const RowSrc& r, uint8_t* lrow, int ck) {
   if (r.ok && ck < r.nch) *reinterpret_cast<uint4*>(lrow + 16 * ck) = load_chunk(k, r.ga + 16 * ck);
 }
@@ -168,34 +138,6 @@ __device__ __forceinline__ void group_bytes(const AugArgs& k, const Sample& s, c
 #pragma unroll
     for (int t = 0; t < 8; ++t) px[t] = pixel_bytes(k, s, r, lrow, j0 + t);
   }
-}
-
-__device__ __forceinline__ float normalise(const AugArgs& k, uint32_t px, int c) {
-  const float u = static_cast<float>((px >> (8 * c)) & 0xffu);
-  const float m = u * k.a[c];  // rounded on its own: contraction is off
-  return m + k.b[c];
-}
-
-// one output pixel's C stores from its packed bytes and its partner's
-template <typename T, int C>
-__device__ __forceinline__ void pixel_out(const AugArgs& k, const Mix& m, uint32_t px, uint32_t pp, bool use_p,
-                                          bool inbox, T* o) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float z = normalise(k, px, c);
-    if (use_p) {
-      const float yp = normalise(k, pp, c);
-      if (m.mode == 1) {
-        const float d = z - yp;
-        const float t = m.lam * d;
-        z = yp + t;
-      } else if (inbox) {
-        z = yp;
-      }
-    }
-    o[c] = static_cast<T>(z);
-  }
-  if constexpr (C == 4) o[3] = static_cast<T>(0.f);
 }
 
 template <typename T, int C, bool MIX>

@@ -28,6 +28,9 @@ ap.add_argument("--items", type=int, default=None, help="images in the whole set
 ap.add_argument("--mixup", type=float, default=0.2)
 ap.add_argument("--cutmix", type=float, default=0.0)
 ap.add_argument("--smoothing", type=float, default=0.1)
+ap.add_argument("--crop", choices=("pad", "resized"), default="pad",
+                help="pad: a crop of the stored image by translation; resized: RandomResizedCrop(scale=(0.08, 1), "
+                     "ratio=(3/4, 4/3)) resampled bilinearly, the ImageNet recipe (evaluation: Resize + CenterCrop)")
 args = ap.parse_args()
 
 FluxMPI.Init()
@@ -57,7 +60,7 @@ per_epoch = max(1, len(shard_x) // args.batch)
 # different crops from the one seed (sample_offset = local_rank * batch)
 aug = FluxMPI.DeviceAugment(args.image, channels=4 if dev.type == "cuda" else 3,
                             dtype=torch.bfloat16, seed=0, mixup_alpha=args.mixup, cutmix_alpha=args.cutmix,
-                            label_smoothing=args.smoothing, num_classes=classes, targets="labels")
+                            label_smoothing=args.smoothing, num_classes=classes, targets="labels", crop=args.crop)
 meter = FluxMPI.ClassificationMeter(topk=(1, 5))
 
 t0 = time.time()

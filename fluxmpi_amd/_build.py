@@ -78,7 +78,8 @@ EXTRA_FLAGS = {f: _NO_SLP for f in ("gemm_nt.hip", "attention.hip", "gemm_glds.h
 
 # kernels tuned to sit just under the 256-VGPR limit: a compiler that starts to spill them must show
 # at build time, not as a slow step (the resource remarks of their compile are checked for scratch)
-NO_SCRATCH = ("conv3bn3_bwd.hip", "conv3ds_bwd.hip", "bn_relu_conv1x1_fwd.hip", "xent.hip", "conv3bn3_s2_bwd.hip")
+NO_SCRATCH = ("conv3bn3_bwd.hip", "conv3ds_bwd.hip", "bn_relu_conv1x1_fwd.hip", "xent.hip", "conv3bn3_s2_bwd.hip",
+              "resize_crop.hip")
 
 
 def _check_no_scratch(src: str, remarks: str) -> None:

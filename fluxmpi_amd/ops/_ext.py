@@ -9,9 +9,10 @@
 * the native RCCL communicator (``csrc/comm/rccl_comm.cpp``).
 
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
-(``tests/test_bindings_surface.py`` says what may change in its surface). The one exception is
-:func:`xent`: the fused softmax cross-entropy entries are a second pybind11 module of the same
-shared object, ``_C_xent``, until ``_C``'s recorded surface is next re-recorded.
+(``tests/test_bindings_surface.py`` says what may change in its surface). The exceptions go through
+:func:`submodule`: the fused softmax cross-entropy entries (:func:`xent`, ``_C_xent``) and the
+resized-crop entry (:func:`rrc`, ``_C_rrc``) are further pybind11 modules of the same shared object,
+until ``_C``'s recorded surface is next re-recorded.
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -80,27 +81,37 @@ def get(required: bool = True):
     return mod
 
 
-_XENT = None
+_SUB: dict = {}
 
 
-def xent():
-    """The ``_C_xent`` module (``xent_fwd``, ``xent_finish``, ``xent_bwd``; ``csrc/kernels/xent.hip``):
-    the ``PyInit__C_xent`` of the shared object ``_C`` was loaded from. Missing: an error, as for ``_C``."""
-    global _XENT
-    if _XENT is None:
+def submodule(name: str, what: str):
+    """A further pybind11 module ``fluxmpi_amd.<name>`` of the shared object ``_C`` was loaded from (its
+    ``PyInit_<name>``); ``what`` names its entries in the error. Missing: an error, as for ``_C``."""
+    mod = _SUB.get(name)
+    if mod is None:
         C = get(required=True)
         if C is None:
-            raise NativeExtensionError("fluxmpi_amd._C_xent needs the native extension fluxmpi_amd._C")
-        spec = importlib.util.spec_from_file_location("fluxmpi_amd._C_xent", C.__file__)
+            raise NativeExtensionError(f"fluxmpi_amd.{name} needs the native extension fluxmpi_amd._C")
+        spec = importlib.util.spec_from_file_location(f"fluxmpi_amd.{name}", C.__file__)
         try:
             mod = importlib.util.module_from_spec(spec)
             spec.loader.exec_module(mod)
         except Exception as e:
             raise NativeExtensionError(
-                f"fluxmpi_amd._C_xent (the cross-entropy entries of {C.__file__}) failed to load: {e!r}. "
+                f"fluxmpi_amd.{name} ({what} of {C.__file__}) failed to load: {e!r}. "
                 "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
-        _XENT = mod
-    return _XENT
+        _SUB[name] = mod
+    return mod
+
+
+def xent():
+    """The ``_C_xent`` module (``xent_fwd``, ``xent_finish``, ``xent_bwd``; ``csrc/kernels/xent.hip``)."""
+    return submodule("_C_xent", "the cross-entropy entries")
+
+
+def rrc():
+    """The ``_C_rrc`` module (``resized_crop_batch``; ``csrc/kernels/resize_crop.hip``)."""
+    return submodule("_C_rrc", "the resized-crop entry")
 
 
 def require_for(t: torch.Tensor):
