@@ -644,4 +644,23 @@ void xent_bwd(const void* x, const void* labels, const void* target, const float
               void* dx, int64_t B, int64_t C, int dtype, int label_dtype, int target_dtype, int mode, int reduction,
               float eps, float lam, const float* dev_lam, hipStream_t stream);
 
+// ---- ViT patch embedding as an implicit GEMM on the NHWC bf16 batch (patch_embed.hip) ----
+// x [B][H][W][C], C = 3 or 4, 16-byte aligned; p C % 8 == 0, p p C % 64 == 0, H % p == W % p == 0, one
+// sample below 2^31 bytes, D % 64 == 0; n = (H / p)(W / p) tokens per sample, K' = p p C in (i, j, c)
+// order. An entry rejects a call outside these limits and names itself in the error.
+// wp [D][K'] (bf16) from the parameter w [D][3 p p] in (c, i, j) order; channel 3 (C = 4) is zero
+void patch_weight_pack(const void* w, void* wp, int D, int p, int C, hipStream_t stream);
+// out [B (n + 1)][ldo] (bf16, ldo >= D, ldo % 8 == 0): row b (n + 1) + 1 + t = bf16(A[m] . wp^T + bias +
+// pos[1 + t]) (fp32 sum, one rounding), row b (n + 1) = bf16(cls + pos[0]). bias [D], cls [D], pos
+// [n + 1][D]: each bf16 or fp32 (its own dtype code)
+void patch_embed_fwd(const void* x, const void* wp, const void* bias, const void* cls, const void* pos, void* out,
+                     int64_t B, int H, int W, int C, int p, int D, int64_t ldo, int bias_dtype, int cls_dtype,
+                     int pos_dtype, hipStream_t stream);
+// ws [s][D][3 p p] fp32 = the partials of dY[:, 1:]^T A over s token ranges, in the parameter's
+// (c, i, j) order with channel 3 dropped (sum them with gemm_splitk_reduce); dy [B (n + 1)][D] bf16 is
+// read in place. splits must be patch_embed_wgrad_splits(B n, wanted): whole 64-token steps, no empty range
+int patch_embed_wgrad_splits(int64_t M, int splits);
+void patch_embed_wgrad(const void* x, const void* dy, float* ws, int64_t B, int H, int W, int C, int p, int D, int splits,
+                       hipStream_t stream);
+
 }  // namespace fluxmpi

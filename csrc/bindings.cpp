@@ -414,3 +414,17 @@ PYBIND11_MODULE(_C_rrc, m) {
       py::arg("w"), py::arg("C"), py::arg("dtype"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"),
       py::arg("a"), py::arg("b"), py::arg("dev_block"), py::arg("stream"));
 }
+
+// A fourth module, loaded the same way: the ViT patch embedding (csrc/kernels/patch_embed.hip).
+PYBIND11_MODULE(_C_patch, m) {
+  m.doc() = "fluxmpi_amd native library: the patch-embedding entries (csrc/kernels/patch_embed.hip)";
+  m.def("patch_weight_pack", raw(&patch_weight_pack), py::arg("w"), py::arg("wp"), py::arg("D"), py::arg("p"),
+        py::arg("C"), py::arg("stream"));
+  m.def("patch_embed_fwd", raw(&patch_embed_fwd), py::arg("x"), py::arg("wp"), py::arg("bias"), py::arg("cls"),
+        py::arg("pos"), py::arg("out"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("p"),
+        py::arg("D"), py::arg("ldo"), py::arg("bias_dtype"), py::arg("cls_dtype"), py::arg("pos_dtype"),
+        py::arg("stream"));
+  m.def("patch_embed_wgrad_splits", &patch_embed_wgrad_splits, py::arg("M"), py::arg("splits"));
+  m.def("patch_embed_wgrad", raw(&patch_embed_wgrad), py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("B"),
+        py::arg("H"), py::arg("W"), py::arg("C"), py::arg("p"), py::arg("D"), py::arg("splits"), py::arg("stream"));
+}

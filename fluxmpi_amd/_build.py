@@ -74,12 +74,17 @@ _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {f: _NO_SLP for f in ("gemm_nt.hip", "attention.hip", "gemm_glds.hip", "gemm.hip", "conv3x3n.hip",
                                         "wgrad3x3n.hip", "linbwd.hip", "conv3bn3_bwd.hip", "conv3ds_bwd.hip",
                                         "bn_relu_conv1x1_fwd.hip", "conv3bn3_s2_bwd.hip")}
+# no packed fp32 math at all (v_pk_*_f32 off as a target feature): the epilogue of patch_embed.hip is
+# acc + bias + pos in fp32 beside MFMAs, the case the note above is about. What it changes is recorded,
+# not timed: without it the file compiles to 160 v_pk_add_f32 (the forward's epilogues), with it to none, at
+# the same VGPR counts and no scratch either way (profiles/patch_embed_resources.md)
+EXTRA_FLAGS["patch_embed.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 # kernels tuned to sit just under the 256-VGPR limit: a compiler that starts to spill them must show
 # at build time, not as a slow step (the resource remarks of their compile are checked for scratch)
 NO_SCRATCH = ("conv3bn3_bwd.hip", "conv3ds_bwd.hip", "bn_relu_conv1x1_fwd.hip", "xent.hip", "conv3bn3_s2_bwd.hip",
-              "resize_crop.hip")
+              "resize_crop.hip", "patch_embed.hip")
 
 
 def _check_no_scratch(src: str, remarks: str) -> None:

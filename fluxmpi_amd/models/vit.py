@@ -8,7 +8,8 @@ point of this config for the DDP layer (bucketing + backward/comm overlap).
 Attention runs our HIP kernels (``csrc/kernels/attention.hip``: MFMA, whole key range per
 workgroup) on the packed QKV projection, output written in the projection's layout and the
 three input gradients straight into one packed gradient (``packed_attention``); the patch embedding is a GEMM on the
-unfolded patches; LayerNorms are the fused HIP kernels with the residual adds
+unfolded patches, or with ``embed="fused"`` one implicit GEMM on the NHWC batch that also writes the ``[CLS]`` row
+and the position embedding (``fluxmpi_amd.ops.patch_embed``); LayerNorms are the fused HIP kernels with the residual adds
 folded in (``fluxmpi_amd.ops.layernorm``); every token-major Linear takes its weight
 gradient from the split-K HIP GEMM and its bias gradient from the ``colsum`` kernel
 (``fluxmpi_amd.ops.linear``).
@@ -201,9 +202,24 @@ class _ClsPos(torch.autograd.Function):
         return (dy[:, 1:] if need[0] else None), dcls, dpos
 
 
+def _default_embed() -> str:
+    """``"unfold"``, or ``FLUXMPI_PATCH_EMBED=fused`` for A/B runs of an unchanged ``bench.py``."""
+    return "fused" if os.environ.get("FLUXMPI_PATCH_EMBED", "unfold") == "fused" else "unfold"
+
+
 class ViT(nn.Module):
-    def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, num_classes=1000):
+    """``embed="unfold"``: the patch embedding as an unfold copy + Linear + ``cls_pos``. ``embed="fused"``:
+    ``ops.patch_embed`` reads a ``channels_last`` bf16 batch of 3 or 4 channels directly and writes the
+    token buffer once; whatever it does not take (NCHW, fp16, CPU, odd sizes, an image that requires a
+    gradient) runs the unfold path, on
+    ``x[:, :3]`` of a 4-channel batch. Parameters and ``state_dict()`` are the same either way."""
+
+    def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, num_classes=1000, embed=None):
         super().__init__()
+        embed = _default_embed() if embed is None else embed
+        if embed not in ("unfold", "fused"):
+            raise ValueError(f"embed must be 'unfold' or 'fused', got {embed!r}")
+        self.embed_mode = embed
         self.embed = PatchEmbed(img, patch, 3, dim)
         self.cls = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos = nn.Parameter(torch.randn(1, self.embed.n + 1, dim) * 0.02)
@@ -216,13 +232,25 @@ class ViT(nn.Module):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.zeros_(m.bias)
 
-    def forward(self, x):
+    def _tokens(self, x):
+        """``[B, n + 1, D]``: the patch projection with the [CLS] row and the position embedding."""
+        if self.embed_mode == "fused":
+            from ..ops import patch_embed as pe
+            proj = self.embed.proj
+            # (an image that wants a gradient takes the unfold path: the fused node has none for it)
+            if (proj.weight.dtype == torch.bfloat16 and pe.supported(x, self.embed.patch, proj.out_features)
+                    and not (x.requires_grad and torch.is_grad_enabled())):
+                return pe.patch_embed(x, proj.weight, proj.bias, self.cls, self.pos, self.embed.patch)
+            if x.shape[1] == 4:
+                x = x[:, :3]
         x = self.embed(x)
         if x.is_cuda and torch.is_grad_enabled():
-            x = _ClsPos.apply(x, self.cls, self.pos)
-        else:
-            # the differentiable composition (cls_pos writes through out=, which autograd does not trace)
-            x = torch.cat([self.cls.expand(x.shape[0], -1, -1).to(x.dtype), x], 1) + self.pos.to(x.dtype)
+            return _ClsPos.apply(x, self.cls, self.pos)
+        # the differentiable composition (cls_pos writes through out=, which autograd does not trace)
+        return torch.cat([self.cls.expand(x.shape[0], -1, -1).to(x.dtype), x], 1) + self.pos.to(x.dtype)
+
+    def forward(self, x):
+        x = self._tokens(x)
         pend = None
         last = len(self.blocks) - 1
         for i, blk in enumerate(self.blocks):
@@ -240,5 +268,5 @@ def vit_b16(num_classes=1000, img=224, **kw) -> ViT:
     return ViT(img=img, num_classes=num_classes, **kw)
 
 
-def vit_tiny(num_classes=10, img=32) -> ViT:
-    return ViT(img=img, patch=8, dim=64, depth=2, heads=4, mlp=128, num_classes=num_classes)
+def vit_tiny(num_classes=10, img=32, **kw) -> ViT:
+    return ViT(img=img, patch=8, dim=64, depth=2, heads=4, mlp=128, num_classes=num_classes, **kw)

@@ -11,8 +11,8 @@
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
 (``tests/test_bindings_surface.py`` says what may change in its surface). The exceptions go through
 :func:`submodule`: the fused softmax cross-entropy entries (:func:`xent`, ``_C_xent``) and the
-resized-crop entry (:func:`rrc`, ``_C_rrc``) are further pybind11 modules of the same shared object,
-until ``_C``'s recorded surface is next re-recorded.
+resized-crop entry (:func:`rrc`, ``_C_rrc``) and the patch-embedding entries (:func:`patch`, ``_C_patch``) are
+further pybind11 modules of the same shared object, until ``_C``'s recorded surface is next re-recorded.
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -112,6 +112,12 @@ def xent():
 def rrc():
     """The ``_C_rrc`` module (``resized_crop_batch``; ``csrc/kernels/resize_crop.hip``)."""
     return submodule("_C_rrc", "the resized-crop entry")
+
+
+def patch():
+    """The ``_C_patch`` module (``patch_weight_pack``, ``patch_embed_fwd``, ``patch_embed_wgrad``;
+    ``csrc/kernels/patch_embed.hip``)."""
+    return submodule("_C_patch", "the patch-embedding entries")
 
 
 def require_for(t: torch.Tensor):
