@@ -663,4 +663,21 @@ int patch_embed_wgrad_splits(int64_t M, int splits);
 void patch_embed_wgrad(const void* x, const void* dy, float* ws, int64_t B, int H, int W, int C, int p, int D, int splits,
                        hipStream_t stream);
 
+// ---- fp8 (fp8_quant.hip, gemm_fp8.hip; limits and block layout in kernels/fp8_host.h) ----
+// Per-tensor power-of-two scaling. A scale block is 8 device words {scale, 1 / scale, amax bits, the amax the
+// last update consumed, 4 spare}; fmt: 0 = e4m3, 1 = e5m2. An entry rejects a call outside its limits and names
+// itself in the error. Every launch is HIP-graph capturable.
+// q [R][ldq] = cast(clamp(x * scale)) of the bf16 x [R][ld] (C % 8 == 0; columns up to C rounded up to 16 are
+// written as zero), qt [C][ldt] its transpose with R rounded up to 16 and zero padding (either may be null); want_amax: max |x| is accumulated into the
+// block (integer atomicMax, one per workgroup). A non-finite input stays non-finite.
+void fp8_quantize(const void* x, int64_t R, int64_t C, int64_t ld, void* block, int fmt, void* q, int64_t ldq, void* qt,
+                  int64_t ldt, int want_amax, hipStream_t stream);
+// scale = 2^floor(log2(FMAX / amax)) (1 when amax is 0 or not finite), its exact inverse; amax is cleared
+void fp8_scale_update(void* block, int fmt, hipStream_t stream);
+// c bf16 [M][ldc] = (1 / sa)(1 / sb) a [M][lda] . b [N][ldb]^T (+ bias [N], bf16 = 9 or fp32 = 7, may be null):
+// fp8 operands (fa x fb: e4m3 x e4m3 or e5m2 x e4m3), fp32 accumulation, one rounding. K % 16 == 0, N % 8 == 0,
+// strides multiples of 16 bytes; sa / sb: the operands' scale blocks
+void fp8_gemm(const void* a, const void* b, void* c, const void* bias, int bias_dtype, const void* sa, const void* sb,
+              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int fa, int fb, hipStream_t stream);
+
 }  // namespace fluxmpi

@@ -428,3 +428,15 @@ PYBIND11_MODULE(_C_patch, m) {
   m.def("patch_embed_wgrad", raw(&patch_embed_wgrad), py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("C"), py::arg("p"), py::arg("D"), py::arg("splits"), py::arg("stream"));
 }
+
+// A fifth module, loaded the same way: the fp8 entries (csrc/kernels/fp8_quant.hip, gemm_fp8.hip).
+PYBIND11_MODULE(_C_fp8, m) {
+  m.doc() = "fluxmpi_amd native library: the fp8 entries (csrc/kernels/fp8_quant.hip, gemm_fp8.hip)";
+  m.def("fp8_quantize", raw(&fp8_quantize), py::arg("x"), py::arg("R"), py::arg("C"), py::arg("ld"), py::arg("block"),
+        py::arg("fmt"), py::arg("q"), py::arg("ldq"), py::arg("qt"), py::arg("ldt"), py::arg("want_amax"),
+        py::arg("stream"));
+  m.def("fp8_scale_update", raw(&fp8_scale_update), py::arg("block"), py::arg("fmt"), py::arg("stream"));
+  m.def("fp8_gemm", raw(&fp8_gemm), py::arg("a"), py::arg("b"), py::arg("c"), py::arg("bias"), py::arg("bias_dtype"),
+        py::arg("sa"), py::arg("sb"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"),
+        py::arg("ldc"), py::arg("fa"), py::arg("fb"), py::arg("stream"));
+}

@@ -79,12 +79,17 @@ EXTRA_FLAGS = {f: _NO_SLP for f in ("gemm_nt.hip", "attention.hip", "gemm_glds.h
 # not timed: without it the file compiles to 160 v_pk_add_f32 (the forward's epilogues), with it to none, at
 # the same VGPR counts and no scratch either way (profiles/patch_embed_resources.md)
 EXTRA_FLAGS["patch_embed.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# the same for the fp8 files, recorded and not timed as above (profiles/fp8_resources.md): without it gemm_fp8.hip
+# compiles to 128 packed fp32 multiplies / FMAs (the epilogue's acc * 1/sa * 1/sb + bias beside MFMAs) and 176
+# VGPRs, with it to none and 172; fp8_quant.hip has none either way (the flag keeps a later compiler from packing
+# its x * scale and clamp on 16 adjacent values per lane)
+EXTRA_FLAGS["gemm_fp8.hip"] = EXTRA_FLAGS["fp8_quant.hip"] = EXTRA_FLAGS["patch_embed.hip"]
 
 
 # kernels tuned to sit just under the 256-VGPR limit: a compiler that starts to spill them must show
 # at build time, not as a slow step (the resource remarks of their compile are checked for scratch)
 NO_SCRATCH = ("conv3bn3_bwd.hip", "conv3ds_bwd.hip", "bn_relu_conv1x1_fwd.hip", "xent.hip", "conv3bn3_s2_bwd.hip",
-              "resize_crop.hip", "patch_embed.hip")
+              "resize_crop.hip", "patch_embed.hip", "gemm_fp8.hip", "fp8_quant.hip")
 
 
 def _check_no_scratch(src: str, remarks: str) -> None:

@@ -122,12 +122,16 @@ class Block(nn.Module):
     (``ops/layernorm.linear_add_layer_norm``) whose backward also yields the Linear's bias
     gradient — no standalone add or bias-gradient kernels in either direction."""
 
-    def __init__(self, dim, heads, mlp):
+    def __init__(self, dim, heads, mlp, fp8=False):
         super().__init__()
         from ..ops.layernorm import FusedLayerNorm
         self.heads = heads
         self.ln1 = FusedLayerNorm(dim, eps=1e-6)
-        self.qkv = Linear(dim, 3 * dim)
+        if fp8:  # qkv is the block's one plain Linear: the others live in fused nodes and stay bf16
+            from ..ops.fp8 import Fp8Linear
+            self.qkv = Fp8Linear(dim, 3 * dim)
+        else:
+            self.qkv = Linear(dim, 3 * dim)
         self.proj = Linear(dim, dim)
         self.ln2 = FusedLayerNorm(dim, eps=1e-6)
         self.fc1 = nn.Linear(dim, mlp)
@@ -207,15 +211,24 @@ def _default_embed() -> str:
     return "fused" if os.environ.get("FLUXMPI_PATCH_EMBED", "unfold") == "fused" else "unfold"
 
 
+def _default_fp8() -> bool:
+    """False, or ``FLUXMPI_FP8=1`` for A/B runs of an unchanged ``bench.py``."""
+    return os.environ.get("FLUXMPI_FP8", "0") == "1"
+
+
 class ViT(nn.Module):
     """``embed="unfold"``: the patch embedding as an unfold copy + Linear + ``cls_pos``. ``embed="fused"``:
     ``ops.patch_embed`` reads a ``channels_last`` bf16 batch of 3 or 4 channels directly and writes the
     token buffer once; whatever it does not take (NCHW, fp16, CPU, odd sizes, an image that requires a
     gradient) runs the unfold path, on
-    ``x[:, :3]`` of a 4-channel batch. Parameters and ``state_dict()`` are the same either way."""
+    ``x[:, :3]`` of a 4-channel batch. Parameters and ``state_dict()`` are the same either way.
+    ``fp8=True``: every block's ``qkv`` is an ``ops.fp8.Fp8Linear`` (forward and input gradient in fp8 on the
+    128-deep MFMA, weight and bias gradients from the bf16 kernels); ``state_dict()`` is unchanged."""
 
-    def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, num_classes=1000, embed=None):
+    def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, num_classes=1000, embed=None,
+                 fp8=None):
         super().__init__()
+        fp8 = _default_fp8() if fp8 is None else bool(fp8)
         embed = _default_embed() if embed is None else embed
         if embed not in ("unfold", "fused"):
             raise ValueError(f"embed must be 'unfold' or 'fused', got {embed!r}")
@@ -223,7 +236,7 @@ class ViT(nn.Module):
         self.embed = PatchEmbed(img, patch, 3, dim)
         self.cls = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos = nn.Parameter(torch.randn(1, self.embed.n + 1, dim) * 0.02)
-        self.blocks = nn.ModuleList([Block(dim, heads, mlp) for _ in range(depth)])
+        self.blocks = nn.ModuleList([Block(dim, heads, mlp, fp8) for _ in range(depth)])
         from ..ops.layernorm import FusedLayerNorm
         self.ln = FusedLayerNorm(dim, eps=1e-6)
         self.head = Linear(dim, num_classes)  # ops.linear.Linear: dW / db into their bucket slices

@@ -11,8 +11,8 @@
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
 (``tests/test_bindings_surface.py`` says what may change in its surface). The exceptions go through
 :func:`submodule`: the fused softmax cross-entropy entries (:func:`xent`, ``_C_xent``) and the
-resized-crop entry (:func:`rrc`, ``_C_rrc``) and the patch-embedding entries (:func:`patch`, ``_C_patch``) are
-further pybind11 modules of the same shared object, until ``_C``'s recorded surface is next re-recorded.
+resized-crop entry (:func:`rrc`, ``_C_rrc``), the patch-embedding entries (:func:`patch`, ``_C_patch``) and the
+fp8 entries (:func:`fp8`, ``_C_fp8``) are further pybind11 modules of the same shared object, until ``_C``'s recorded surface is next re-recorded.
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -118,6 +118,12 @@ def patch():
     """The ``_C_patch`` module (``patch_weight_pack``, ``patch_embed_fwd``, ``patch_embed_wgrad``;
     ``csrc/kernels/patch_embed.hip``)."""
     return submodule("_C_patch", "the patch-embedding entries")
+
+
+def fp8():
+    """The ``_C_fp8`` module (``fp8_quantize``, ``fp8_scale_update``, ``fp8_gemm``; ``csrc/kernels/fp8_quant.hip``,
+    ``gemm_fp8.hip``)."""
+    return submodule("_C_fp8", "the fp8 entries")
 
 
 def require_for(t: torch.Tensor):

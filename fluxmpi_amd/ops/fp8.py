@@ -1,0 +1,292 @@
+"""fp8 Linear on the gfx950 matrix core: quantise kernels, an fp8 NT GEMM, ``Fp8Linear`` (opt-in).
+
+Scaling is per tensor and a power of two, ``s = 2^floor(log2(FMAX / amax))`` (:func:`pow2_scale`), so scaling
+and unscaling are exact and the cast to fp8 is the only rounding. A tensor's scale lives in an 8-word device
+block ``{scale, 1 / scale, amax bits, consumed amax, ...}`` (int32 storage, so that ``module.bfloat16()``
+leaves it alone); nothing is read back to the host and every launch is HIP-graph capturable.
+
+* :func:`quantize` -> :class:`Fp8Tensor` (``csrc/kernels/fp8_quant.hip``): ``block=None`` is *current*
+  scaling (an amax launch, ``fp8_scale_update``, the cast); with a block it casts with the block's stored scale
+  while accumulating the tensor's amax, and :func:`scale_update` turns that into the next scale (*delayed*).
+* :func:`gemm` (``csrc/kernels/gemm_fp8.hip``): ``a [M, K] x b [N, K]^T`` in fp32 on
+  ``v_mfma_f32_16x16x128_f8f6f4``, unscaled and rounded once to bf16, bias in the epilogue.
+* :func:`fp8_linear` / :class:`Fp8Linear`: forward ``x`` and ``W`` in e4m3, input gradient ``dy`` in e5m2 against
+  ``W``'s transposed image; ``dW`` and ``db`` come from the bf16 kernels of ``ops.linear`` (``wgrad_bgrad``: its
+  separate weight-gradient and column-sum calls, not the one-launch ``linbwd.hip`` node, whose input gradient
+  this path replaces) on the saved bf16 ``x`` and the bf16 ``dy``, delivered into their bucket slices. Parameters and ``state_dict()`` are ``nn.Linear``'s.
+  Whatever :func:`supported` refuses takes ``ops.linear.linear`` unchanged.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import torch
+
+from . import _ext
+from .linear import linear, wgrad_bgrad
+from .multi_tensor import DTYPE_CODE
+
+E4M3, E5M2 = "e4m3", "e5m2"
+FMT_CODE = {E4M3: 0, E5M2: 1}
+FMAX = {E4M3: 448.0, E5M2: 57344.0}
+TORCH_DTYPE = {E4M3: torch.float8_e4m3fn, E5M2: torch.float8_e5m2}
+BLOCK_WORDS = 8
+
+
+def _fmt(fmt: str) -> str:
+    if fmt not in FMT_CODE:
+        raise ValueError(f"fp8: the format is 'e4m3' or 'e5m2', got {fmt!r}")
+    return fmt
+
+
+def pow2_scale(amax: float, fmt: str) -> float:
+    """``2^floor(log2(FMAX / amax))`` with the exponent kept in -126 .. 126; 1 for an ``amax`` of 0, inf or NaN."""
+    amax = float(amax)
+    if amax == 0.0 or not math.isfinite(amax):
+        return 1.0
+    m, e = math.frexp(abs(amax))  # amax = (2 m) 2^(e - 1), 2 m in [1, 2); FMAX = 1.75 * 2^E
+    p = int(math.log2(FMAX[_fmt(fmt)] / 1.75)) - (e - 1) - (1 if 2 * m > 1.75 else 0)
+    return 2.0 ** max(-126, min(126, p))
+
+
+def quantize_reference(x: torch.Tensor, fmt: str, scale: float | None = None):
+    """``(q, scale)`` on the CPU with torch's round-to-nearest-even casts: ``q = cast(clamp(x * scale, +-FMAX))``
+    as a float8 tensor, non-finite inputs kept non-finite; ``scale=None``: :func:`pow2_scale` of ``x``'s amax."""
+    xf = x.detach().float().cpu()
+    if scale is None:
+        scale = pow2_scale(float(xf.abs().max()) if xf.numel() else 0.0, fmt)
+    y = (xf * scale).clamp(-FMAX[_fmt(fmt)], FMAX[fmt])
+    return torch.where(torch.isfinite(xf), y, xf).to(TORCH_DTYPE[fmt]), scale
+
+
+def new_block(device, scale: float = 1.0) -> torch.Tensor:
+    """A scale block (int32 ``[8]``) holding ``scale`` (a power of two) and an empty amax."""
+    f = torch.tensor([scale, 1.0 / scale], dtype=torch.float32).view(torch.int32)
+    return torch.cat([f, torch.zeros(BLOCK_WORDS - 2, dtype=torch.int32)]).to(device)
+
+
+@dataclass
+class Fp8Tensor:
+    """An fp8 image of a bf16 matrix: ``q [R, C]`` and, when asked for, ``q_t [C, R']`` (``R'`` = ``R`` rounded up
+    to 16, zero padding), both uint8 bit patterns of ``fmt``, and the device scale block they were cast with.
+    Where ``C % 16 != 0``, ``q`` is a view of rows that are zero up to ``C`` rounded up to 16: :func:`gemm` reads
+    that padding of both operands."""
+    q: torch.Tensor
+    q_t: torch.Tensor | None
+    block: torch.Tensor
+    fmt: str
+
+    def t(self) -> "Fp8Tensor":
+        """The transposed image as a GEMM operand."""
+        if self.q_t is None:
+            raise ValueError("fp8: this tensor was quantised without its transposed image")
+        return Fp8Tensor(self.q_t, None, self.block, self.fmt)
+
+
+def _pad16(n: int) -> int:
+    return -(-n // 16) * 16
+
+
+def _stream(t: torch.Tensor) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def layout_ok(x: torch.Tensor) -> bool:
+    """What ``fp8_quantize`` takes: a bf16 matrix with unit column stride, ``C % 8 == 0``, a row stride that is a
+    multiple of 8 elements, a 16-byte aligned base."""
+    return (x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[0] >= 1 and x.shape[1] >= 8
+            and x.shape[1] % 8 == 0 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0)
+
+
+def scale_update(block: torch.Tensor, fmt: str) -> None:
+    """``fp8_scale_update``: the block's amax becomes its scale (and exact inverse) and is cleared."""
+    _ext.fp8().fp8_scale_update(block.data_ptr(), FMT_CODE[_fmt(fmt)], _stream(block))
+
+
+def quantize_into(x, fmt, block, q=None, q_t=None, amax=True) -> None:
+    """One ``fp8_quantize`` launch on ``x`` with ``block``'s stored scale into the uint8 views ``q [R, C']`` and
+    ``q_t [C, R']`` (``C'``, ``R'``: rounded up to 16, the padding written as zero; each may be None; both None:
+    the amax pass alone)."""
+    if not (x.is_cuda and layout_ok(x)):
+        raise ValueError("fp8.quantize: the input must be a bf16 CUDA matrix with C % 8 == 0, a row stride "
+                         "that is a multiple of 8 and a 16-byte aligned base")
+    if block.dtype != torch.int32 or block.numel() < BLOCK_WORDS or not block.is_contiguous() or block.device != x.device:
+        raise ValueError("fp8.quantize: the scale block is a contiguous int32 tensor of 8 words on the input's device")
+    r, c = x.shape
+    for o, shape in ((q, (r, _pad16(c))), (q_t, (c, _pad16(r)))):
+        if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != shape or o.stride(1) != 1):
+            raise ValueError(f"fp8.quantize: an output must be a uint8 view of shape {shape}")
+    _ext.fp8().fp8_quantize(x.data_ptr(), r, c, x.stride(0), block.data_ptr(), FMT_CODE[_fmt(fmt)],
+                            q.data_ptr() if q is not None else 0, q.stride(0) if q is not None else 0,
+                            q_t.data_ptr() if q_t is not None else 0, q_t.stride(0) if q_t is not None else 0,
+                            int(amax), _stream(x))
+
+
+def quantize(x: torch.Tensor, fmt: str, block: torch.Tensor | None = None, transpose: bool = False) -> Fp8Tensor:
+    """The fp8 image of the bf16 matrix ``x``. ``block=None``: current scaling in a fresh block (amax pass, scale
+    update, cast). With a block: the cast uses its stored scale and accumulates ``x``'s amax into it (delayed
+    scaling; :func:`scale_update` then prepares the next scale); values the scale has outgrown saturate."""
+    _fmt(fmt)
+    if not x.is_cuda or x.dim() != 2:
+        raise ValueError("fp8.quantize: the input is a bf16 matrix on the GPU (CPU tensors take quantize_reference)")
+    current = block is None
+    if current:
+        block = torch.zeros(BLOCK_WORDS, dtype=torch.int32, device=x.device)
+        quantize_into(x, fmt, block)
+        scale_update(block, fmt)
+    r, c = x.shape
+    q = torch.empty(r, _pad16(c), dtype=torch.uint8, device=x.device)
+    q_t = torch.empty(c, _pad16(r), dtype=torch.uint8, device=x.device) if transpose else None
+    quantize_into(x, fmt, block, q, q_t, amax=not current)
+    return Fp8Tensor(q[:, :c], q_t, block, fmt)
+
+
+def gemm_into(out: torch.Tensor, a: Fp8Tensor, b: Fp8Tensor, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`gemm` into the bf16 view ``out [M, N]`` (any row stride that is a multiple of 8)."""
+    m, k = a.q.shape
+    n = b.q.shape[0]
+    if (a.fmt, b.fmt) not in ((E4M3, E4M3), (E5M2, E4M3)):
+        raise ValueError("fp8.gemm: the operands are e4m3 x e4m3 or e5m2 x e4m3")
+    # K is walked up to the next multiple of 16: the rows' zero padding (Fp8Tensor; b's columns k .. kp are that of
+    # a transposed image; more columns than that is another K)
+    kp = _pad16(k)
+    if not a.q.is_cuda or not k <= b.q.shape[1] <= kp or min(a.q.stride(0), b.q.stride(0)) < kp or n % 8:
+        raise ValueError(f"fp8.gemm: a [M, K] and b [N, K] need N % 8 == 0 and rows padded to K rounded up to 16 on "
+                         f"the GPU, got {tuple(a.q.shape)} and {tuple(b.q.shape)}")
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (m, n) or out.stride(1) != 1:
+        raise ValueError(f"fp8.gemm: the output must be a bf16 view of shape {(m, n)}")
+    if bias is not None:
+        bias = bias.detach()
+        if bias.dtype not in (torch.bfloat16, torch.float32):
+            bias = bias.float()
+        bias = bias.contiguous()
+        if bias.numel() != n:
+            raise ValueError(f"fp8.gemm: the bias must have {n} elements")
+    _ext.fp8().fp8_gemm(a.q.data_ptr(), b.q.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                        DTYPE_CODE[bias.dtype] if bias is not None else 0, a.block.data_ptr(), b.block.data_ptr(),
+                        m, n, kp, a.q.stride(0), b.q.stride(0), out.stride(0), FMT_CODE[a.fmt], FMT_CODE[b.fmt],
+                        _stream(a.q))
+    return out
+
+
+def gemm(a: Fp8Tensor, b: Fp8Tensor, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """``bf16(a b^T / (sa sb) + bias)``: ``a [M, K]`` e4m3 or e5m2, ``b [N, K]`` e4m3, fp32 accumulation."""
+    out = torch.empty(a.q.shape[0], b.q.shape[0], dtype=torch.bfloat16, device=a.q.device)
+    return gemm_into(out, a, b, bias)
+
+
+def supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """True when :func:`fp8_linear` runs ``x @ weight.T`` in fp8: bf16 on the GPU, both widths multiples of 8
+    (each is the N of one GEMM and the K of the other, which the images pad to 16), aligned contiguous storage,
+    and a gradient wanted."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2):
+        return False
+    n_out, n_in = weight.shape
+    if x.dim() < 1 or x.shape[-1] != n_in or n_in % 8 or n_out % 8 or x.numel() == 0:
+        return False
+    if not (torch.is_grad_enabled() and weight.requires_grad):
+        return False
+    return x.is_contiguous() and weight.is_contiguous() and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+
+
+class Fp8State:
+    """What an fp8 Linear keeps between calls: the scaling mode, under ``"delayed"`` the three scale blocks
+    (``blocks [3, 8]`` int32: x, W, dy; made on first use, scale 1). ``W``'s images are NOT kept from one forward
+    to the next: the fused optimisers write the parameters through raw pointers and leave ``weight._version``
+    alone, so nothing the module can see says that a cached image is still the weight's. A forward casts ``W``
+    (two small launches beside the activation's) and hands the images to its own backward."""
+
+    def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None):
+        if scaling not in ("current", "delayed"):
+            raise ValueError(f"fp8_linear: scaling must be 'current' or 'delayed', got {scaling!r}")
+        self.scaling = scaling
+        self.blocks = blocks
+
+    def block(self, i: int, device):
+        if self.scaling == "current":
+            return None
+        if self.blocks is None or self.blocks.device != device:
+            self.blocks = torch.stack([new_block(device) for _ in range(3)])
+        return self.blocks[i]
+
+    def image(self, x2: torch.Tensor, fmt: str, i: int, transpose: bool = False) -> Fp8Tensor:
+        """Delayed scaling prepares this step's scale from the previous step's amax, then casts with it."""
+        blk = self.block(i, x2.device)
+        if blk is not None:
+            scale_update(blk, fmt)
+        return quantize(x2, fmt, blk, transpose)
+
+
+
+class _Fp8LinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, state):
+        n_out, n_in = weight.shape
+        wq = state.image(weight.detach(), E4M3, 1, transpose=True)
+        xq = state.image(x.view(-1, n_in), E4M3, 0)
+        ctx.save_for_backward(x, weight)
+        ctx.state, ctx.wq, ctx.bias = state, wq, bias  # the bias leaf itself: its bucket slice
+        return gemm(xq, wq, bias).view(*x.shape[:-1], n_out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        n_out, n_in = w.shape
+        dy2 = dy.reshape(-1, n_out)
+        if dy2.dtype != torch.bfloat16 or not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.to(torch.bfloat16).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = gemm(ctx.state.image(dy2, E5M2, 2), ctx.wq.t()).view(x.shape)
+        # dW and db: the bf16 kernels on the bf16 x and dy, as _LinearFn's separate calls
+        need_b = ctx.bias is not None and ctx.needs_input_grad[2]
+        dw, db = wgrad_bgrad(x.reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
+        return dx, dw, db, None
+
+
+def fp8_linear(x, weight, bias=None, state: Fp8State | None = None) -> torch.Tensor:
+    """``F.linear`` with the forward and the input gradient in fp8 (see the module); ``state=None`` is stateless
+    current scaling. Unsupported input (:func:`supported`) takes ``ops.linear.linear``."""
+    if not supported(x, weight):
+        return linear(x, weight, bias)
+    return _Fp8LinearFn.apply(x, weight, bias, state if state is not None else Fp8State())
+
+
+class Fp8Linear(torch.nn.Linear):
+    """Drop-in for ``ops.linear.Linear``: same parameters and ``state_dict()``; the weight stays bf16 and the
+    fp8 images are per-step scratch. ``scaling="delayed"`` keeps its three scale blocks in a non-persistent
+    buffer."""
+
+    def __init__(self, in_features, out_features, bias=True, scaling="current", **kw):
+        super().__init__(in_features, out_features, bias=bias, **kw)
+        self.fp8 = Fp8State(scaling)
+        self.register_buffer("fp8_blocks", torch.stack([new_block("cpu") for _ in range(3)]), persistent=False)
+
+    def forward(self, x):
+        if not supported(x, self.weight):
+            return linear(x, self.weight, self.bias)
+        self.fp8.blocks = self.fp8_blocks  # follows .to(device)
+        return _Fp8LinearFn.apply(x, self.weight, self.bias, self.fp8)
+
+
+def fp8_linear_reference(x, w, b, dy, scales=None):
+    """``(y, dx, |y|, |dx|)`` in float64 on the CPU of the same quantisation: x, w in e4m3 and dy in e5m2 with
+    :func:`pow2_scale` of each tensor (or ``scales = (sx, sw, sdy)``), then float64 products of the dequantised
+    values; the last two are the same products of absolute values (what an error bound scales with)."""
+    sx, sw, sdy = scales if scales is not None else (None, None, None)
+    n_in = w.shape[1]
+    deq = []
+    for t, fmt, s in ((x.reshape(-1, n_in), E4M3, sx), (w, E4M3, sw), (dy.reshape(-1, w.shape[0]), E5M2, sdy)):
+        q, s = quantize_reference(t, fmt, s)
+        deq.append(q.double() / s)
+    xd, wd, dyd = deq
+    bd = b.detach().double().cpu() if b is not None else torch.zeros(w.shape[0], dtype=torch.float64)
+    y, ya = xd @ wd.t() + bd, xd.abs() @ wd.abs().t() + bd.abs()
+    return y, dyd @ wd, ya, dyd.abs() @ wd.abs()
+
+
+__all__ = ["E4M3", "E5M2", "FMAX", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
+           "quantize", "quantize_into", "quantize_reference", "pow2_scale", "scale_update", "new_block", "gemm",
+           "gemm_into", "supported", "layout_ok"]

@@ -174,6 +174,35 @@ def bias_grad(dy2: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
     return db.to(out_dtype)
 
 
+def wgrad_bgrad(x2: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, dy2: torch.Tensor, need_w: bool,
+                need_b: bool):
+    """``(dW, db)`` of a Linear from the bf16 ``x2 [rows, N_in]`` and the contiguous ``dy2 [rows, N_out]`` on the
+    separate weight-gradient and column-sum kernels (hipBLASLt / a torch sum where :func:`native_ok` refuses),
+    each written straight into its parameter's DDP bucket slice when a communicating engine is attached; None
+    where not needed. ``bias`` is the leaf itself (its slice, its dtype)."""
+    n_out = w.shape[0]
+    native = _wgrad_mode() == "ours" and native_ok(x2, dy2)
+    same = dy2.dtype == x2.dtype == w.dtype
+    dw = db = None
+    if need_w:
+        with graddst.into(w):
+            if native:
+                dw = weight_grad(dy2, x2, w.dtype)
+            elif same:  # short K (e.g. a classifier head): hipBLASLt, output in the slice
+                dw = torch.mm(dy2.t(), x2, out=graddst.empty(tuple(w.shape), w.dtype, dy2.device))
+            else:
+                dw = (dy2.t() @ x2).to(w.dtype)
+    if need_b:
+        with graddst.into(bias):
+            if native:
+                db = bias_grad(dy2, bias.dtype)
+            elif dy2.dtype == bias.dtype:
+                db = torch.sum(dy2, 0, out=graddst.empty((n_out,), bias.dtype, dy2.device))
+            else:
+                db = dy2.sum(0).to(bias.dtype)
+    return dw, db
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -206,23 +235,8 @@ class _LinearFn(torch.autograd.Function):
                 dx, dw = dgrad_wgrad(dy2, x2, w, w.dtype)
             dx = dx.reshape(x.shape)
             need_w = False
-        if need_w:
-            def wgrad():
-                with graddst.into(w):
-                    if native:
-                        return weight_grad(dy2, x2, w.dtype)
-                    if same:  # short K (e.g. a classifier head): hipBLASLt, output in the slice
-                        return torch.mm(dy2.t(), x2, out=graddst.empty(tuple(w.shape), w.dtype, dy2.device))
-                    return (dy2.t() @ x2).to(w.dtype)
-            dw = wgrad()
-        if need_b:
-            with graddst.into(ctx.bias):
-                if native:
-                    db = bias_grad(dy2, ctx.bias_dtype)
-                elif dy2.dtype == ctx.bias_dtype:
-                    db = torch.sum(dy2, 0, out=graddst.empty((n_out,), ctx.bias_dtype, dy2.device))
-                else:
-                    db = dy2.sum(0).to(ctx.bias_dtype)
+        dw_, db = wgrad_bgrad(x2, w, ctx.bias, dy2, need_w, need_b)
+        dw = dw_ if need_w else dw
         if dx is None and ctx.needs_input_grad[0]:
             dx = dgrad(dy2, w).reshape(x.shape)
         return dx, dw, db
@@ -261,4 +275,4 @@ class Linear(torch.nn.Linear):
         return linear(x, self.weight, self.bias)
 
 
-__all__ = ["linear", "Linear", "weight_grad", "bias_grad", "native_ok", "fwd", "dgrad", "dgrad_wgrad", "linbwd_ok"]
+__all__ = ["linear", "Linear", "weight_grad", "bias_grad", "wgrad_bgrad", "native_ok", "fwd", "dgrad", "dgrad_wgrad", "linbwd_ok"]

@@ -1,0 +1,110 @@
+#!/usr/bin/env python
+"""The fp8 path (``ops.fp8``: ``csrc/kernels/fp8_quant.hip``, ``gemm_fp8.hip``) against the bf16 kernels it would
+replace, at the ViT-B/16 shapes (50432 tokens = batch 256).
+
+Variants, alternated in one process, each a HIP-graph replay:
+
+  gemm_{fwd,dgrad}_{qkv,proj,fc1,fc2}_{fp8,bf16}   the GEMM alone: ``fp8.gemm`` on images made beforehand against
+                                                   ``ops.linear.fwd`` / ``dgrad`` (gemm_nt.hip, else hipBLASLt)
+  quant_x_{current,delayed}                        the activation's cast passes alone ([50432, 768], e4m3)
+  qkv_fwdbwd_{bf16,fp8_current,fp8_delayed}        ``Linear`` / ``Fp8Linear`` forward + backward (dx, dW, db)
+
+One JSON line per variant with the median of the rounds and min-max; fp8 lines carry ``bf16_over_fp8`` and the
+GEMM lines the achieved PFLOP/s (2 M N K over the median).
+
+usage: python scripts/bench_fp8.py [--out profiles/fp8_vit_b16.jsonl] [--rounds 7] [--iters 20] [--tokens 50432]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fluxmpi_amd.ops import fp8  # noqa: E402
+from fluxmpi_amd.ops import linear as L  # noqa: E402
+from scripts.bench_patch_embed import graphed, timed  # noqa: E402
+
+LAYERS = {"qkv": (768, 2304), "proj": (768, 768), "fc1": (768, 3072), "fc2": (3072, 768)}  # name -> (n_in, n_out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join("profiles", "fp8_vit_b16.jsonl"))
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--tokens", type=int, default=50432)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        print("bench_fp8.py needs a GPU", file=sys.stderr)
+        return 2
+    M = a.tokens
+    torch.manual_seed(0)
+    fns, flops, keep = {}, {}, []
+    rnd = lambda *s: torch.randn(*s, device="cuda").bfloat16()
+    for name, (n_in, n_out) in LAYERS.items():
+        x, w, b, dy = rnd(M, n_in), rnd(n_out, n_in) * n_in ** -0.5, rnd(n_out), rnd(M, n_out)
+        xq, wq, dyq = fp8.quantize(x, fp8.E4M3), fp8.quantize(w, fp8.E4M3, transpose=True), fp8.quantize(dy, fp8.E5M2)
+        keep += [x, w, b, dy, xq, wq, dyq]
+        with torch.no_grad():
+            for key, f in ((f"gemm_fwd_{name}_fp8", lambda xq=xq, wq=wq, b=b: fp8.gemm(xq, wq, b)),
+                           (f"gemm_fwd_{name}_bf16", lambda x=x, w=w, b=b: L.fwd(x, w, b)),
+                           (f"gemm_dgrad_{name}_fp8", lambda dyq=dyq, wq=wq: fp8.gemm(dyq, wq.t())),
+                           (f"gemm_dgrad_{name}_bf16", lambda dy=dy, w=w: L.dgrad(dy, w))):
+                fns[key], out = graphed(f)
+                flops[key] = 2.0 * M * n_in * n_out
+                keep += [f, out]
+        print(f"captured gemm {name}", file=sys.stderr, flush=True)
+    n_in, n_out = LAYERS["qkv"]
+    x, dy = rnd(M, n_in).requires_grad_(), rnd(M, n_out)
+    blk = fp8.new_block("cuda")
+
+    def delayed_cast():
+        fp8.scale_update(blk, fp8.E4M3)
+        return fp8.quantize(x.detach(), fp8.E4M3, blk)
+
+    for key, f in (("quant_x_current", lambda: fp8.quantize(x.detach(), fp8.E4M3)), ("quant_x_delayed", delayed_cast)):
+        fns[key], out = graphed(f)
+        keep += [f, out]
+    for key, lin in (("bf16", L.Linear(n_in, n_out)), ("fp8_current", fp8.Fp8Linear(n_in, n_out)),
+                     ("fp8_delayed", fp8.Fp8Linear(n_in, n_out, scaling="delayed"))):
+        lin = lin.cuda().bfloat16()
+
+        def fwdbwd(lin=lin):
+            lin.weight.grad = lin.bias.grad = x.grad = None
+            lin(x).backward(dy)
+            return x.grad, lin.weight.grad, lin.bias.grad
+
+        fns[f"qkv_fwdbwd_{key}"], out = graphed(fwdbwd)
+        keep += [lin, fwdbwd, out]
+        print(f"captured qkv {key}", file=sys.stderr, flush=True)
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(a.rounds):  # alternate the variants: drift of the shared machine hits all alike
+        for k, fn in fns.items():
+            us[k].append(timed(fn, a.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        for k, v in us.items():
+            r = {"variant": k, "us": round(med[k], 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1),
+                 "rounds": a.rounds, "iters": a.iters, "mode": "graph", "tokens": M}
+            if k in flops:
+                r["pflops"] = round(flops[k] / med[k] * 1e-9, 3)
+            base = k.replace("_fp8", "_bf16") if k.startswith("gemm_") else "qkv_fwdbwd_bf16"
+            if "fp8" in k and base in med:
+                r["bf16_over_fp8"] = round(med[base] / med[k], 2)
+                r["faster_than_bf16_worst_case"] = bool(max(v) < min(us[base]))
+            line = json.dumps(r)
+            print(line, flush=True)
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
