@@ -234,7 +234,7 @@ void bn_fwd_train(const void* x, void* y, const void* residual, const float* wei
 // y == nullptr with relu: the ReLU mask is recomputed from x (bit-identical to forward).
 // relu_mask (optional): the 1-bit-per-element mask written by bn_fwd_train.
 // dx == nullptr: reduce and finalize only. dweight / dbias (the finished sums of dy_eff * xhat and of
-// dy_eff) are written and no pass forms dx; the consumer forms it itself from them (gemm_bf16 mode 4).
+// dy_eff) are written and no pass forms dx; the consumer forms it itself from them (conv3bn3_bwd, conv3ds_bwd).
 // dres must then be null too (it is written by the dx pass): the combination is an error.
 void bn_bwd(const void* dy, const void* x, const void* y, const uint8_t* relu_mask, const float* weight,
             const float* bias,
@@ -413,20 +413,22 @@ struct GemmProblem {
   int conv_s = 1;
 };
 void gemm_bf16(const GemmProblem& g, hipStream_t stream);
-// mode 4 (conv3bn3_bwd.hip): the one-pass backward of conv3 (1x1, 64 -> 256) -> bn3 (+ residual,
+// conv3bn3_bwd.hip: the one-pass backward of conv3 (1x1, Cin = 64 -> Cout = 256) -> bn3 (+ residual,
 // ReLU) of a stage-1 identity block. dx3, bn3's input gradient, is formed in registers (the dx
-// pass's arithmetic, bit for bit) and never stored; c = d_a2 [M][64] = dx3 . W and the filter
-// gradient's fp32 partials stats[s][256][64], s < splits, of dx3^T . a2 (sum them with
-// gemm_splitk_reduce). Fields: M = pixels, N = 64, K = 256; a = dy [M][256] (K-major, lda = 256);
-// bnb_x = x3 [M][256]; bnb_mask = the 1-bit ReLU mask (bnb_rm = 3); bnb_w / bnb_mean / bnb_inv =
-// bn3's weight (nullable) / saved mean / saved invstd; a_scale = sum dy_eff, a_shift = sum dy_eff
-// xhat ([256] fp32, bn_bwd's dbias / dweight); b = W [256][64] as stored (N-major, ldb = 64);
-// res = a2 [M][64] (ldr = 64); ldc = 64. splits = the slab count = the workgroups launched, the
-// caller's choice: min(ceil(M / 64), 2 x compute units) fills the device with one round.
-// The same with N = 128, K = 512 (a stage-2 identity block's 128 -> 512; every 64 / 256 above doubled)
-// runs conv3bn3_s2_bwd.hip: one workgroup per compute unit, so splits = min(ceil(M / 32), compute units).
-// Any other (N, K) throws.
-void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream);
+// pass's arithmetic, bit for bit) and never stored; written are d_a2 [P][64] = dx3 . W (bf16) and the
+// filter gradient's fp32 partials ws[s][256][64], s < slabs, of dx3^T . a2 (sum them with
+// gemm_splitk_reduce). dy, c3 [P][256] bf16 (c3 = bn3's input); relu_mask = the 1-bit ReLU mask
+// [P * 256 / 8]; w / save_mean / save_invstd = bn3's weight (nullable: 1) / saved mean / saved invstd;
+// sum_dy / sum_dy_xhat: [256] fp32, bn_bwd's dbias / dweight (call it with dx = null); a2 [P][64] bf16;
+// wt = the filter [256][64] as stored. Every pointer but the mask 16-byte aligned. slabs = the
+// workgroups launched, the caller's choice: min(ceil(P / 32), 2 x compute units) fills the device with
+// one round.
+// The same with Cin = 128, Cout = 512 (a stage-2 identity block's 128 -> 512; every 64 / 256 above doubled)
+// runs conv3bn3_s2_bwd.hip: one workgroup per compute unit, so slabs = min(ceil(P / 32), compute units).
+// Any other (Cin, Cout) throws.
+void conv3bn3_bwd(const void* dy, const uint8_t* relu_mask, const void* c3, const float* w, const float* save_mean,
+                  const float* save_invstd, const float* sum_dy, const float* sum_dy_xhat, const void* a2,
+                  const void* wt, void* d_a2, float* ws, int64_t P, int Cin, int Cout, int slabs, hipStream_t stream);
 // conv3ds_bwd.hip: the same around the dual BatchNorm of a stage-1 downsample block,
 // out = relu(bn3(conv3(a2)) + bn_ds(conv_ds(x))), both convolutions 1x1, 64 -> 256, stride 1. One pass
 // over (dy [P][256], the 1-bit ReLU mask, c3, c_ds [P][256], a2, x [P][64]) forms dx3 and dx_ds in

@@ -177,8 +177,13 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("block"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"), py::arg("stream"));
 
-  // ---- ResNet one-pass nodes: the backward around the dual BatchNorm of a stage-1 downsample block
-  // (conv3ds_bwd.hip); bn2 apply + ReLU + conv3 forward (bn_relu_conv1x1_fwd.hip) ----
+  // ---- ResNet one-pass nodes: the conv3 -> bn3 backward of the identity blocks (conv3bn3_bwd.hip,
+  // conv3bn3_s2_bwd.hip) and around the dual BatchNorm of a stage-1 downsample block (conv3ds_bwd.hip);
+  // bn2 apply + ReLU + conv3 forward (bn_relu_conv1x1_fwd.hip) ----
+  m.def("conv3bn3_bwd", raw(&conv3bn3_bwd), py::arg("dy"), py::arg("mask"), py::arg("c3"), py::arg("w"),
+        py::arg("mean"), py::arg("inv"), py::arg("sum_dy"), py::arg("sum_dy_xhat"), py::arg("a2"), py::arg("wt"),
+        py::arg("d_a2"), py::arg("ws"), py::arg("P"), py::arg("Cin"), py::arg("Cout"), py::arg("slabs"),
+        py::arg("stream"));
   m.def("conv3ds_bwd", raw(&conv3ds_bwd), py::arg("dy"), py::arg("mask"), py::arg("c3"), py::arg("cds"), py::arg("w"),
         py::arg("mean"), py::arg("inv"), py::arg("sum_dy"), py::arg("sum_dy_xhat"), py::arg("w2"), py::arg("mean2"),
         py::arg("inv2"), py::arg("sum_dy2"), py::arg("sum_dy_xhat2"), py::arg("a2"), py::arg("x"), py::arg("wt3"),
@@ -375,12 +380,8 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("rank", &RcclComm::rank)
       .def_property_readonly("size", &RcclComm::size)
       .def_property_readonly("device", &RcclComm::device);
-}
 
-// A second module of the same shared object (loaded from _C.__file__ by ops/_ext.py: xent()): the
-// fused softmax cross-entropy entries, beside `_C` so that its recorded surface stays as it is.
-PYBIND11_MODULE(_C_xent, m) {
-  m.doc() = "fluxmpi_amd native library: the fused softmax cross-entropy entries (csrc/kernels/xent.hip)";
+  // ---- fused softmax cross-entropy (xent.hip) -------------------------------------------------
   m.def("xent_fwd", raw(&xent_fwd), py::arg("x"), py::arg("labels"), py::arg("target"), py::arg("loss_row"),
         py::arg("m"), py::arg("s"), py::arg("rank"), py::arg("B"), py::arg("C"), py::arg("dtype"),
         py::arg("label_dtype"), py::arg("target_dtype"), py::arg("mode"), py::arg("eps"), py::arg("lam"),
@@ -391,13 +392,9 @@ PYBIND11_MODULE(_C_xent, m) {
         py::arg("g"), py::arg("dx"), py::arg("B"), py::arg("C"), py::arg("dtype"), py::arg("label_dtype"),
         py::arg("target_dtype"), py::arg("mode"), py::arg("reduction"), py::arg("eps"), py::arg("lam"),
         py::arg("dev_lam"), py::arg("stream"));
-}
 
-// A third module of the same shared object, loaded the same way: the resampling form of the device
-// input pipeline (csrc/kernels/resize_crop.hip). `mode`, `box`, `lam`, `a`, `b` and `dev_block` are
-// AugHyper's; `boxes` is the device table int32 [B][5].
-PYBIND11_MODULE(_C_rrc, m) {
-  m.doc() = "fluxmpi_amd native library: the resized-crop entry (csrc/kernels/resize_crop.hip)";
+  // ---- the resampling form of the device input pipeline (resize_crop.hip): `mode`, `box`, `lam`, `a`,
+  // `b` and `dev_block` are AugHyper's; `boxes` is the device table int32 [B][5] ----
   m.def(
       "resized_crop_batch",
       [](uintptr_t in, uintptr_t out, uintptr_t boxes, int64_t B, int H, int W, int h, int w, int C, int dtype,
@@ -413,11 +410,8 @@ PYBIND11_MODULE(_C_rrc, m) {
       py::arg("input"), py::arg("out"), py::arg("boxes"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("h"),
       py::arg("w"), py::arg("C"), py::arg("dtype"), py::arg("step"), py::arg("mode"), py::arg("box"), py::arg("lam"),
       py::arg("a"), py::arg("b"), py::arg("dev_block"), py::arg("stream"));
-}
 
-// A fourth module, loaded the same way: the ViT patch embedding (csrc/kernels/patch_embed.hip).
-PYBIND11_MODULE(_C_patch, m) {
-  m.doc() = "fluxmpi_amd native library: the patch-embedding entries (csrc/kernels/patch_embed.hip)";
+  // ---- the ViT patch embedding (patch_embed.hip) ----------------------------------------------
   m.def("patch_weight_pack", raw(&patch_weight_pack), py::arg("w"), py::arg("wp"), py::arg("D"), py::arg("p"),
         py::arg("C"), py::arg("stream"));
   m.def("patch_embed_fwd", raw(&patch_embed_fwd), py::arg("x"), py::arg("wp"), py::arg("bias"), py::arg("cls"),
@@ -427,11 +421,8 @@ PYBIND11_MODULE(_C_patch, m) {
   m.def("patch_embed_wgrad_splits", &patch_embed_wgrad_splits, py::arg("M"), py::arg("splits"));
   m.def("patch_embed_wgrad", raw(&patch_embed_wgrad), py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("C"), py::arg("p"), py::arg("D"), py::arg("splits"), py::arg("stream"));
-}
 
-// A fifth module, loaded the same way: the fp8 entries (csrc/kernels/fp8_quant.hip, gemm_fp8.hip).
-PYBIND11_MODULE(_C_fp8, m) {
-  m.doc() = "fluxmpi_amd native library: the fp8 entries (csrc/kernels/fp8_quant.hip, gemm_fp8.hip)";
+  // ---- fp8 (fp8_quant.hip, gemm_fp8.hip) ------------------------------------------------------
   m.def("fp8_quantize", raw(&fp8_quantize), py::arg("x"), py::arg("R"), py::arg("C"), py::arg("ld"), py::arg("block"),
         py::arg("fmt"), py::arg("q"), py::arg("ldq"), py::arg("qt"), py::arg("ldt"), py::arg("want_amax"),
         py::arg("stream"));

@@ -1,8 +1,14 @@
 // MFMA operand helpers shared by the one-pass conv3 -> bn3 backward kernels (conv3bn3_bwd.hip and
 // conv3bn3_s2_bwd.hip, the identity blocks of stages 1 and 2; conv3ds_bwd.hip, the downsample block): one
-// copy of the transposed fragment read, and the identity-block kernels' argument block.
+// copy of the transposed fragment read, the identity-block kernels' argument block, and the host checks of
+// the two entries (conv3bn3_bwd, conv3ds_bwd).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <initializer_list>
+#include <stdexcept>
+#include <string>
 
 namespace fluxmpi {
 
@@ -30,6 +36,24 @@ struct C3Args {
 
 // the Cout = 512, Cin = 128 form (conv3bn3_s2_bwd.hip), launched by conv3bn3_bwd once it has checked the problem
 void conv3bn3_s2_launch(const C3Args& p, int slabs, hipStream_t stream);
+
+// What both entries check before they launch: every pointer of `required` present, those and the `nullable`
+// ones (the BatchNorm weights) 16-byte aligned, and a slab count (= workgroups) that is a valid grid. More
+// workgroups than tiles is allowed: the extra ones store zero slabs.
+inline void c3_check_operands(const char* entry, std::initializer_list<const void*> required,
+                              std::initializer_list<const void*> nullable, int slabs) {
+  const std::string name(entry);
+  uintptr_t bits = 0;
+  for (const void* q : required) {
+    if (q == nullptr)
+      throw std::runtime_error(name + ": a null operand; the operands other than the BatchNorm weights are all required");
+    bits |= reinterpret_cast<uintptr_t>(q);
+  }
+  for (const void* q : nullable) bits |= reinterpret_cast<uintptr_t>(q);
+  if ((bits & 15u) != 0) throw std::runtime_error(name + ": operands must be 16-byte aligned");
+  if (slabs < 1 || slabs > 65535)
+    throw std::runtime_error(name + ": slabs (the slab count = workgroups) must be in [1, 65535]");
+}
 
 // lane l: img[k0 + 8 (l >> 4) + j][c0 + (l & 15)], j = 0..7 (two transposed reads), ld in elements
 __device__ __forceinline__ bf16x8 frag_tr(const __bf16* __restrict__ img, int ld, int k0, int c0) {

@@ -28,7 +28,7 @@
 // workgroup without tiles stores zeros) and gemm_splitk_reduce sums the slabs: no float atomics,
 // no grid barrier. Rows past P are zero in both tiles, so the partial last tile adds nothing.
 // The stage-2 form (128 -> 512, one workgroup per CU) is conv3bn3_s2_bwd.hip; conv3bn3_bwd below checks
-// the problem for both and launches the one that (N, K) names.
+// the operands for both and launches the one that (Cin, Cout) names.
 #include <stdexcept>
 #include <string>
 
@@ -232,35 +232,23 @@ __global__ __launch_bounds__(kThreads, 2) void conv3bn3_bwd_kernel(C3Args p) {
 
 }  // namespace
 
-void conv3bn3_bwd(const GemmProblem& g, hipStream_t stream) {
-  // (N, K) = (Cin, Cout): (64, 256) here, (128, 512) in conv3bn3_s2_bwd.hip
-  const bool s2 = g.N == 128 && g.K == 512;
-  if (!((g.N == kCi && g.K == kCo) || s2) || g.M < 1 || g.lda != g.K || g.ldb != g.N || g.ldc != g.N || g.ldr != g.N ||
-      !g.a_kmajor || g.b_kmajor || g.bnb_rm != 3)
-    throw std::runtime_error("gemm_bf16 mode 4: needs (N, K) = (64, 256) or (128, 512), dense operands (lda = K, ldb = "
-                             "ldc = ldr = N), K-major A, N-major B and the 1-bit ReLU mask (bnb_rm = 3); got M=" +
-                             std::to_string(g.M) + ", N=" + std::to_string(g.N) + ", K=" + std::to_string(g.K));
-  if (g.a == nullptr || g.b == nullptr || g.c == nullptr || g.res == nullptr || g.bnb_x == nullptr ||
-      g.bnb_mask == nullptr || g.bnb_mean == nullptr || g.bnb_inv == nullptr || g.a_scale == nullptr ||
-      g.a_shift == nullptr || g.stats == nullptr)
-    throw std::runtime_error("gemm_bf16 mode 4: dy, W, d_a2, a2 (res), x3 (bnb_x), the mask, mean / invstd, the two "
-                             "sums (a_scale / a_shift) and the slab workspace (stats) are all required");
-  uintptr_t bits = 0;
-  for (const void* q : {g.a, g.b, static_cast<const void*>(g.c), g.res, g.bnb_x, static_cast<const void*>(g.bnb_w),
-                        static_cast<const void*>(g.bnb_mean), static_cast<const void*>(g.bnb_inv),
-                        static_cast<const void*>(g.a_scale), static_cast<const void*>(g.a_shift),
-                        static_cast<const void*>(g.stats)})
-    bits |= reinterpret_cast<uintptr_t>(q);
-  if ((bits & 15u) != 0) throw std::runtime_error("gemm_bf16 mode 4: operands must be 16-byte aligned");
-  // (more workgroups than tiles is allowed: the extra ones store zero slabs)
-  if (g.splits < 1 || g.splits > 65535)
-    throw std::runtime_error("gemm_bf16 mode 4: splits (the slab count = workgroups) must be in [1, 65535]");
-  C3Args p{static_cast<const bf16*>(g.a), static_cast<const bf16*>(g.bnb_x), g.bnb_mask, g.bnb_w, g.bnb_mean,
-           g.bnb_inv, g.a_scale, g.a_shift, static_cast<const bf16*>(g.res), static_cast<const bf16*>(g.b),
-           static_cast<bf16*>(g.c), g.stats, g.M};
-  if (s2) return conv3bn3_s2_launch(p, g.splits, stream);
+void conv3bn3_bwd(const void* dy, const uint8_t* relu_mask, const void* c3, const float* w, const float* save_mean,
+                  const float* save_invstd, const float* sum_dy, const float* sum_dy_xhat, const void* a2,
+                  const void* wt, void* d_a2, float* ws, int64_t P, int Cin, int Cout, int slabs, hipStream_t stream) {
+  // (64, 256) here, (128, 512) in conv3bn3_s2_bwd.hip
+  const bool s2 = Cin == 128 && Cout == 512;
+  if (!((Cin == kCi && Cout == kCo) || s2) || P < 1)
+    throw std::runtime_error("conv3bn3_bwd: needs (Cin, Cout) = (64, 256) or (128, 512) and P (pixels) >= 1; got P=" +
+                             std::to_string(P) + ", Cin=" + std::to_string(Cin) + ", Cout=" + std::to_string(Cout));
+  // the mask is required like the rest, but not among the operands held to 16 bytes
+  if (relu_mask == nullptr) throw std::runtime_error("conv3bn3_bwd: the ReLU mask is required");
+  c3_check_operands("conv3bn3_bwd", {dy, c3, save_mean, save_invstd, sum_dy, sum_dy_xhat, a2, wt, d_a2, ws}, {w},
+                    slabs);
+  C3Args p{static_cast<const bf16*>(dy), static_cast<const bf16*>(c3), relu_mask, w, save_mean, save_invstd, sum_dy,
+           sum_dy_xhat, static_cast<const bf16*>(a2), static_cast<const bf16*>(wt), static_cast<bf16*>(d_a2), ws, P};
+  if (s2) return conv3bn3_s2_launch(p, slabs, stream);
   allow_dynamic_lds(reinterpret_cast<const void*>(&conv3bn3_bwd_kernel), kSmem);
-  conv3bn3_bwd_kernel<<<static_cast<unsigned>(g.splits), kThreads, kSmem, stream>>>(p);
+  conv3bn3_bwd_kernel<<<static_cast<unsigned>(slabs), kThreads, kSmem, stream>>>(p);
   FLUXMPI_HIP_CHECK(hipGetLastError());
 }
 

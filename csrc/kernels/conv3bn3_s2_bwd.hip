@@ -2,7 +2,7 @@
 // block — gfx950. The Cout = 512, Cin = 128 sibling of conv3bn3_bwd.hip (read that file's header first):
 // the same semantics (dx3 from bn_dx.h, bit-identical to the dx pass, rounded to bf16 once into an LDS
 // tile that feeds both MFMA products; d_a2 in bf16; one fp32 dW slab per workgroup by plain stores;
-// rows past P contribute nothing), reached through the same entry (gemm_bf16 mode 4, N = 128, K = 512).
+// rows past P contribute nothing), reached through the same entry (conv3bn3_bwd with Cin = 128, Cout = 512).
 //
 // What differs is the budget. dW [512][128] fp32 is 256 KiB, half of a CU's register file, so exactly
 // one workgroup is resident per CU and its accumulator takes 128 registers of every lane:

@@ -256,24 +256,10 @@ void conv3ds_bwd(const void* dy, const uint8_t* mask, const void* c3, const void
                  const void* x, const void* wt3, const void* wtds, void* d_a2, void* d_xside, float* ws3, float* wsds,
                  int64_t P, int slabs, hipStream_t stream) {
   if (P < 1) throw std::runtime_error("conv3ds_bwd: P (pixels) must be >= 1, got " + std::to_string(P));
-  uintptr_t bits = 0;
-  for (const void* q : {dy, static_cast<const void*>(mask), c3, cds, static_cast<const void*>(mean),
-                        static_cast<const void*>(inv), static_cast<const void*>(sum_dy),
-                        static_cast<const void*>(sum_dy_xhat), static_cast<const void*>(mean2),
-                        static_cast<const void*>(inv2), static_cast<const void*>(sum_dy2),
-                        static_cast<const void*>(sum_dy_xhat2), a2, x, wt3, wtds, static_cast<const void*>(d_a2),
-                        static_cast<const void*>(d_xside), static_cast<const void*>(ws3),
-                        static_cast<const void*>(wsds)}) {
-    if (q == nullptr)
-      throw std::runtime_error("conv3ds_bwd: dy, the mask, c3, c_ds, both BatchNorms' mean / invstd / two sums, a2, x, "
-                               "both filters, d_a2, d_xside and both slab workspaces are all required");
-    bits |= reinterpret_cast<uintptr_t>(q);
-  }
-  bits |= reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(w2);  // the BatchNorm weights: nullable (1)
-  if ((bits & 15u) != 0) throw std::runtime_error("conv3ds_bwd: operands must be 16-byte aligned");
-  // (more workgroups than tiles is allowed: the extra ones store zero slabs)
-  if (slabs < 1 || slabs > 65535)
-    throw std::runtime_error("conv3ds_bwd: slabs (the slab count = workgroups) must be in [1, 65535]");
+  c3_check_operands("conv3ds_bwd",
+                    {dy, mask, c3, cds, mean, inv, sum_dy, sum_dy_xhat, mean2, inv2, sum_dy2, sum_dy_xhat2, a2, x, wt3,
+                     wtds, d_a2, d_xside, ws3, wsds},
+                    {w, w2}, slabs);
   allow_dynamic_lds(reinterpret_cast<const void*>(&conv3ds_bwd_kernel), kSmem);
   DsArgs p{static_cast<const bf16*>(dy), mask,
            {Branch{static_cast<const bf16*>(c3), w, mean, inv, sum_dy, sum_dy_xhat, static_cast<const bf16*>(a2),

@@ -639,10 +639,9 @@ void launch(const GemmArgs& a0, int splits, hipStream_t s) {
 }  // namespace
 
 void gemm_bf16(const GemmProblem& g, hipStream_t stream) {
-  if (g.mode == 4) {  // conv3 -> bn3 one-pass backward (operand mapping: api.h)
-    conv3bn3_bwd(g, stream);
-    return;
-  }
+  // (neither launcher does this: the LDS-DMA kernel takes any mode <= 1, this file's stores 4 as it does 0)
+  if (g.mode < 0 || g.mode > 3)
+    throw std::runtime_error("gemm_bf16: mode must be 0, 1, 2 or 3, got " + std::to_string(g.mode));
   // engine 0 (auto): the LDS-DMA pipelined kernel for every problem it covers
   // (not for a prologue affine: its per-fragment transform costs the LDS-DMA kernel 1.3-2.3x —
   // measured — while register staging applies it on the way to LDS; engine 2 forces it)

@@ -9,10 +9,7 @@
 * the native RCCL communicator (``csrc/comm/rccl_comm.cpp``).
 
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
-(``tests/test_bindings_surface.py`` says what may change in its surface). The exceptions go through
-:func:`submodule`: the fused softmax cross-entropy entries (:func:`xent`, ``_C_xent``) and the
-resized-crop entry (:func:`rrc`, ``_C_rrc``), the patch-embedding entries (:func:`patch`, ``_C_patch``) and the
-fp8 entries (:func:`fp8`, ``_C_fp8``) are further pybind11 modules of the same shared object, until ``_C``'s recorded surface is next re-recorded.
+(``tests/test_bindings_surface.py`` says what may change in its surface).
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -28,7 +25,6 @@ and as the numerics oracle in tests.
 from __future__ import annotations
 
 import importlib
-import importlib.util
 import os
 
 import torch
@@ -79,51 +75,6 @@ def get(required: bool = True):
             f"{_ERR!r}. Run `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`."
         )
     return mod
-
-
-_SUB: dict = {}
-
-
-def submodule(name: str, what: str):
-    """A further pybind11 module ``fluxmpi_amd.<name>`` of the shared object ``_C`` was loaded from (its
-    ``PyInit_<name>``); ``what`` names its entries in the error. Missing: an error, as for ``_C``."""
-    mod = _SUB.get(name)
-    if mod is None:
-        C = get(required=True)
-        if C is None:
-            raise NativeExtensionError(f"fluxmpi_amd.{name} needs the native extension fluxmpi_amd._C")
-        spec = importlib.util.spec_from_file_location(f"fluxmpi_amd.{name}", C.__file__)
-        try:
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-        except Exception as e:
-            raise NativeExtensionError(
-                f"fluxmpi_amd.{name} ({what} of {C.__file__}) failed to load: {e!r}. "
-                "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
-        _SUB[name] = mod
-    return mod
-
-
-def xent():
-    """The ``_C_xent`` module (``xent_fwd``, ``xent_finish``, ``xent_bwd``; ``csrc/kernels/xent.hip``)."""
-    return submodule("_C_xent", "the cross-entropy entries")
-
-
-def rrc():
-    """The ``_C_rrc`` module (``resized_crop_batch``; ``csrc/kernels/resize_crop.hip``)."""
-    return submodule("_C_rrc", "the resized-crop entry")
-
-
-def patch():
-    """The ``_C_patch`` module (``patch_weight_pack``, ``patch_embed_fwd``, ``patch_embed_wgrad``;
-    ``csrc/kernels/patch_embed.hip``)."""
-    return submodule("_C_patch", "the patch-embedding entries")
-
-
-def fp8():
-    """The ``_C_fp8`` module (``fp8_quantize``, ``fp8_scale_update``, ``fp8_gemm``; ``csrc/kernels/fp8_quant.hip``,
-    ``gemm_fp8.hip``)."""
-    return submodule("_C_fp8", "the fp8 entries")
 
 
 def require_for(t: torch.Tensor):

@@ -418,7 +418,7 @@ def resized_crop_batch(u8: torch.Tensor, boxes, *, size, mean=IMAGENET_MEAN, std
             return z.permute(0, 3, 1, 2)
         (out if out.shape == z.shape else out.permute(0, 2, 3, 1)).copy_(z)
         return out if tuple(out.shape) == (c.B, channels, c.h, c.w) else out.permute(0, 3, 1, 2)
-    R = _ext.rrc()
+    R = _ext.get(required=True)
     if not on_device:  # pageable memory: the copy is ordered with the stream
         boxes = torch.from_numpy(table.astype(np.int32)).to(u8.device)
     buf = out if out is not None else torch.empty(c.B, c.h, c.w, channels, device=u8.device, dtype=dtype)

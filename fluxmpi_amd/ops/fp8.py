@@ -102,7 +102,7 @@ def layout_ok(x: torch.Tensor) -> bool:
 
 def scale_update(block: torch.Tensor, fmt: str) -> None:
     """``fp8_scale_update``: the block's amax becomes its scale (and exact inverse) and is cleared."""
-    _ext.fp8().fp8_scale_update(block.data_ptr(), FMT_CODE[_fmt(fmt)], _stream(block))
+    _ext.get(required=True).fp8_scale_update(block.data_ptr(), FMT_CODE[_fmt(fmt)], _stream(block))
 
 
 def quantize_into(x, fmt, block, q=None, q_t=None, amax=True) -> None:
@@ -118,10 +118,10 @@ def quantize_into(x, fmt, block, q=None, q_t=None, amax=True) -> None:
     for o, shape in ((q, (r, _pad16(c))), (q_t, (c, _pad16(r)))):
         if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != shape or o.stride(1) != 1):
             raise ValueError(f"fp8.quantize: an output must be a uint8 view of shape {shape}")
-    _ext.fp8().fp8_quantize(x.data_ptr(), r, c, x.stride(0), block.data_ptr(), FMT_CODE[_fmt(fmt)],
-                            q.data_ptr() if q is not None else 0, q.stride(0) if q is not None else 0,
-                            q_t.data_ptr() if q_t is not None else 0, q_t.stride(0) if q_t is not None else 0,
-                            int(amax), _stream(x))
+    _ext.get(required=True).fp8_quantize(
+        x.data_ptr(), r, c, x.stride(0), block.data_ptr(), FMT_CODE[_fmt(fmt)],
+        q.data_ptr() if q is not None else 0, q.stride(0) if q is not None else 0,
+        q_t.data_ptr() if q_t is not None else 0, q_t.stride(0) if q_t is not None else 0, int(amax), _stream(x))
 
 
 def quantize(x: torch.Tensor, fmt: str, block: torch.Tensor | None = None, transpose: bool = False) -> Fp8Tensor:
@@ -164,10 +164,10 @@ def gemm_into(out: torch.Tensor, a: Fp8Tensor, b: Fp8Tensor, bias: torch.Tensor 
         bias = bias.contiguous()
         if bias.numel() != n:
             raise ValueError(f"fp8.gemm: the bias must have {n} elements")
-    _ext.fp8().fp8_gemm(a.q.data_ptr(), b.q.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                        DTYPE_CODE[bias.dtype] if bias is not None else 0, a.block.data_ptr(), b.block.data_ptr(),
-                        m, n, kp, a.q.stride(0), b.q.stride(0), out.stride(0), FMT_CODE[a.fmt], FMT_CODE[b.fmt],
-                        _stream(a.q))
+    _ext.get(required=True).fp8_gemm(
+        a.q.data_ptr(), b.q.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else 0,
+        DTYPE_CODE[bias.dtype] if bias is not None else 0, a.block.data_ptr(), b.block.data_ptr(),
+        m, n, kp, a.q.stride(0), b.q.stride(0), out.stride(0), FMT_CODE[a.fmt], FMT_CODE[b.fmt], _stream(a.q))
     return out
 
 

@@ -422,7 +422,7 @@ class _Conv3BN3(torch.autograd.Function):
     """out = relu(bn3(conv3(a2)) + residual) of a stage-1 or stage-2 identity block (1x1, 64 -> 256 or
     128 -> 512: the shape is the filter's), whose backward never materialises bn3's input gradient dx3.
     Forward: exactly the launches of ``conv1x1_hybrid(ours_stats=True)`` + ``bn_from_stats``. Backward: bn3's
-    reduce + finalize (``bn_bwd`` without a dx), then one kernel (``gemm_bf16`` mode 4,
+    reduce + finalize (``bn_bwd`` without a dx), then one kernel (``conv3bn3_bwd``:
     csrc/kernels/conv3bn3_bwd.hip or conv3bn3_s2_bwd.hip) that streams (dy, c3, mask, a2) once, forms dx3
     in registers and produces d_a2 = dx3 . W and the per-workgroup partials of dW = dx3^T . a2, then the
     split-K reduce into the filter's gradient. Unfused, dx3 (the network's largest activation size) is
@@ -459,22 +459,26 @@ class _Conv3BN3(torch.autograd.Function):
         _, _, dbw, dbb = launch_bwd(dy, c3, mask, w32, b32, mean, inv, True, params=ctx.params, want_dx=False)
         part = torch.empty(conv3bn3_slabs(n * h * w, dy.device, weight.shape[0]), weight.shape[0], ci,
                            device=dy.device, dtype=torch.float32)
-        d_a2 = _one_pass_branch(dy, mask, c3, w32, mean, inv, (dbb, dbw), a2, weight, part, _empty_nhwc(n, ci, h, w, a2))
+        d_a2 = _one_pass_branch(dy, mask, c3, w32, mean, inv, dbb, dbw, a2, weight, part, _empty_nhwc(n, ci, h, w, a2))
         dw = _slabs_to_wgrad(part, weight) if ctx.needs_input_grad[1] else None
         # the residual's gradient travels as (dy, mask): conv1's dgrad epilogue applies the mask
         dbw, dbb, _ = finish_bwd(dbw, dbb, ctx.wdtype, True, True, ctx.link, dy, mask, None, True)
         return (d_a2, dw, dbw, dbb, None, None, None, None, None, None, None, None, None)
 
 
-def _one_pass_branch(dy, mask, c, w32, mean, inv, sums, act, weight, part, out):
-    """One branch of the one-pass backward around a BatchNorm after a 1x1 convolution (``gemm_bf16`` mode 4,
+def _one_pass_branch(dy, mask, c, w32, mean, inv, sum_dy, sum_dy_xhat, act, weight, part, out):
+    """One branch of the one-pass backward around a BatchNorm after a 1x1 convolution (``conv3bn3_bwd``:
     csrc/kernels/conv3bn3_bwd.hip for 64 -> 256, conv3bn3_s2_bwd.hip for 128 -> 512): streams (dy, c, mask, act)
-    once, forms the BatchNorm's input gradient in registers from its finished ``sums`` = (sum dy, sum dy xhat), writes ``out`` = d_act = dx . W and one fp32
-    partial of dW = dx^T . act per workgroup into the slab set ``part`` [slabs, Cout, Cin]."""
+    once, forms the BatchNorm's input gradient in registers from its finished sums ``sum_dy`` (its dbias) and
+    ``sum_dy_xhat`` (its dweight), writes ``out`` = d_act = dx . W and one fp32 partial of dW = dx^T . act per
+    workgroup into the slab set ``part`` [slabs, Cout, Cin]."""
     co, ci = weight.shape[0], weight.shape[1]
-    return gemm(dy, weight, out, M=act.numel() // ci, N=ci, K=co, lda=co, ldb=ci, ldc=ci, a_kmajor=True, b_kmajor=False,
-                mode=4, splits=part.shape[0], a_affine=sums, stats=part, residual=_nhwc2d(act),
-                bn_bwd=(c, w32, None, mean, inv, mask, 3))
+    _ext.get(required=True).conv3bn3_bwd(
+        dy.data_ptr(), mask.data_ptr(), c.data_ptr(), w32.data_ptr(), mean.data_ptr(), inv.data_ptr(),
+        sum_dy=sum_dy.data_ptr(), sum_dy_xhat=sum_dy_xhat.data_ptr(), a2=act.data_ptr(), wt=weight.data_ptr(),
+        d_a2=out.data_ptr(), ws=part.data_ptr(), P=act.numel() // ci, Cin=ci, Cout=co, slabs=part.shape[0],
+        stream=_stream(dy))
+    return out
 
 
 def _slabs_to_wgrad(part, weight):
@@ -495,7 +499,7 @@ CONV3BN3 = int(os.environ.get("FLUXMPI_CONV3BN3", "2"))
 
 
 def conv3bn3_slabs(rows: int, device, cout: int = 256) -> int:
-    """Workgroups (= fp32 partial slabs) of the mode-4 kernel: one resident round, never more than the
+    """Workgroups (= fp32 partial slabs) of the ``conv3bn3_bwd`` kernels: one resident round, never more than the
     32-pixel tiles there are. 64 -> 256: two workgroups per compute unit; 128 -> 512 (``cout`` 512): one, its
     filter-gradient accumulator being half of a compute unit's registers."""
     cus = torch.cuda.get_device_properties(device).multi_processor_count
@@ -635,7 +639,7 @@ class _Conv3DsBN(torch.autograd.Function):
     exactly the launches of ``conv1x1_hybrid`` + ``conv1x1_downsample`` + ``dual_bn_relu`` (each
     convolution on its per-shape choice). Backward: the dual reduce + finalize (``bn_bwd_dual`` without a
     dx), then either one kernel over both branches (``form`` 2: csrc/kernels/conv3ds_bwd.hip) or the
-    identity blocks' kernel once per branch (``form`` 1: ``gemm_bf16`` mode 4 on (dy, c3, mask, a2, W3),
+    identity blocks' kernel once per branch (``form`` 1: ``conv3bn3_bwd`` on (dy, c3, mask, a2, W3),
     then on (dy, c_ds, mask, x, W_ds)), and the two split-K reduces into the filters' gradients. The
     downsample convolution's input gradient goes to conv1's dgrad epilogue through the block's
     :class:`SideGradLink`, as ``_Conv1x1Downsample`` hands it over.
@@ -682,8 +686,8 @@ class _Conv3DsBN(torch.autograd.Function):
                 d_a2.data_ptr(), d_x.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), rows, slabs, _stream(dy))
         else:
             part = torch.empty(2, conv3bn3_slabs(rows, dev), co, ci, device=dev, dtype=torch.float32)
-            _one_pass_branch(dy, mask, c3, w32, mean, inv, (db, dw), a2, w3, part[0], d_a2)
-            _one_pass_branch(dy, mask, cds, w232, mean2, inv2, (db2, dw2), x, wds, part[1], d_x)
+            _one_pass_branch(dy, mask, c3, w32, mean, inv, db, dw, a2, w3, part[0], d_a2)
+            _one_pass_branch(dy, mask, cds, w232, mean2, inv2, db2, dw2, x, wds, part[1], d_x)
         grads = [_slabs_to_wgrad(part[i], wt) if ctx.needs_input_grad[1 + 2 * i] else None
                  for i, wt in enumerate((w3, wds))]
         if ctx.link is not None and ctx.link.offer(d_x):

@@ -58,7 +58,7 @@ def pack_weight(weight: torch.Tensor, patch: int, channels: int) -> torch.Tensor
     if weight.dtype != torch.bfloat16 or tuple(weight.shape) != (d, 3 * patch * patch) or not weight.is_contiguous():
         raise ValueError("patch_embed: the filter must be a contiguous bf16 [D, 3 p p] matrix")
     wp = torch.empty(d, patch * patch * channels, device=weight.device, dtype=torch.bfloat16)
-    _ext.patch().patch_weight_pack(weight.data_ptr(), wp.data_ptr(), d, patch, channels, _stream(weight))
+    _ext.get(required=True).patch_weight_pack(weight.data_ptr(), wp.data_ptr(), d, patch, channels, _stream(weight))
     return wp
 
 
@@ -82,9 +82,9 @@ def forward_into(out: torch.Tensor, x, weight, bias, cls, pos, patch: int) -> to
         raise ValueError("patch_embed: bias [D], cls [1, 1, D] and pos [1, n + 1, D] do not fit the image")
     wp = pack_weight(weight.detach(), patch, c)
     bias_, cls_, pos_ = _param(bias), _param(cls), _param(pos)
-    _ext.patch().patch_embed_fwd(x.data_ptr(), wp.data_ptr(), bias_.data_ptr(), cls_.data_ptr(), pos_.data_ptr(),
-                                 out.data_ptr(), b, h, w, c, patch, d, out.stride(0), DTYPE_CODE[bias_.dtype],
-                                 DTYPE_CODE[cls_.dtype], DTYPE_CODE[pos_.dtype], _stream(x))
+    _ext.get(required=True).patch_embed_fwd(
+        x.data_ptr(), wp.data_ptr(), bias_.data_ptr(), cls_.data_ptr(), pos_.data_ptr(), out.data_ptr(), b, h, w, c,
+        patch, d, out.stride(0), DTYPE_CODE[bias_.dtype], DTYPE_CODE[cls_.dtype], DTYPE_CODE[pos_.dtype], _stream(x))
     return out
 
 
@@ -94,7 +94,7 @@ def weight_grad(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor, patch: 
     b, c, h, w = x.shape
     d = weight.shape[0]
     m = b * (h // patch) * (w // patch)
-    P = _ext.patch()
+    P = _ext.get(required=True)
     tiles = (d // 64) * (patch * patch * c // 64)
     s = P.patch_embed_wgrad_splits(m, splits or max(1, -(-WGRAD_TARGET // tiles)))
     ws = torch.empty(s, d, 3 * patch * patch, device=x.device, dtype=torch.float32)

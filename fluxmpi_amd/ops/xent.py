@@ -221,7 +221,7 @@ def _target_args(spec: _Spec):
 
 
 def _fwd_gpu(x, spec: _Spec, want_rank: bool):
-    X = _ext.xent()
+    X = _ext.get(required=True)
     B, C = x.shape
     stats = torch.empty(3, B, device=x.device, dtype=torch.float32)  # loss_row, m, s
     rank = torch.empty(B, device=x.device, dtype=torch.int32) if want_rank else None
@@ -233,7 +233,7 @@ def _fwd_gpu(x, spec: _Spec, want_rank: bool):
 
 
 def _bwd_gpu(x, spec: _Spec, m, s, g, reduction: int):
-    X = _ext.xent()
+    X = _ext.get(required=True)
     B, C = x.shape
     dx = torch.empty_like(x)
     lp, dp, lcode, tcode = _target_args(spec)
@@ -267,9 +267,10 @@ class _XentFn(torch.autograd.Function):
                 loss = torch.empty((), device=x.device, dtype=torch.float32)
             if red != 2 or meter is not None:
                 k0, k1 = meter.topk if meter is not None else (1, 1)
-                _ext.xent().xent_finish(loss_row.data_ptr(), _p(rank), loss.data_ptr() if red != 2 else 0,
-                                        meter._block_on(x.device).data_ptr() if meter is not None else 0, B,
-                                        min(red, 1), k0, k1, _stream(x))
+                _ext.get(required=True).xent_finish(
+                    loss_row.data_ptr(), _p(rank), loss.data_ptr() if red != 2 else 0,
+                    meter._block_on(x.device).data_ptr() if meter is not None else 0, B, min(red, 1), k0, k1,
+                    _stream(x))
             ctx.save_for_backward(x, m, s)
         else:
             _check_range(OP, spec, C)

@@ -1,4 +1,4 @@
-"""The one-pass backward of conv3 (1x1, 64 -> 256) -> bn3 (+ residual, ReLU): ``gemm_bf16`` mode 4
+"""The one-pass backward of conv3 (1x1, 64 -> 256) -> bn3 (+ residual, ReLU): ``conv3bn3_bwd``
 (csrc/kernels/conv3bn3_bwd.hip), ``bn_bwd`` without a dx, and the autograd node built on them.
 
 The kernel forms bn3's input gradient dx3 in registers with the dx pass's own arithmetic (bn_dx.h) and
@@ -70,14 +70,13 @@ def _dx3_from_sums(C, dy, x3, mask, bw, mean, inv, sums):
 
 
 def _fused(C, dy, x3, mask, bw, mean, inv, sum_dy, sum_dy_xhat, a2, w, slabs, errs, name):
-    """gemm_bf16 mode 4 into guarded outputs; returns (d_a2 [P, 64] bf16, slabs [s, 256 * 64] fp32)."""
-    from fluxmpi_amd.ops.gemm import gemm
+    """conv3bn3_bwd into guarded outputs; returns (d_a2 [P, 64] bf16, slabs [s, 256 * 64] fp32)."""
     P = dy.shape[0]
     obuf, oview = E.guarded(P, CI, CI, torch.bfloat16, dy.device)
     sbuf, sview = E.guarded(slabs, CO * CI, CO * CI, torch.float32, dy.device)
-    gemm(dy, w, oview, M=P, N=CI, K=CO, lda=CO, ldb=CI, ldc=CI, a_kmajor=True, b_kmajor=False, mode=4,
-         splits=slabs, a_affine=(sum_dy, sum_dy_xhat), stats=sview, residual=a2,
-         bn_bwd=(x3, bw, None, mean, inv, mask, 3))
+    C.conv3bn3_bwd(dy.data_ptr(), mask.data_ptr(), x3.data_ptr(), bw.data_ptr(), mean.data_ptr(), inv.data_ptr(),
+                   sum_dy=sum_dy.data_ptr(), sum_dy_xhat=sum_dy_xhat.data_ptr(), a2=a2.data_ptr(), wt=w.data_ptr(),
+                   d_a2=oview.data_ptr(), ws=sview.data_ptr(), P=P, Cin=CI, Cout=CO, slabs=slabs, stream=_st())
     torch.cuda.synchronize()
     return E.take_guarded(f"{name} d_a2", obuf, oview, errs), E.take_guarded(f"{name} slabs", sbuf, sview, errs)
 

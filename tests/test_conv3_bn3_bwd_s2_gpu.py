@@ -1,5 +1,5 @@
 """The one-pass backward of conv3 (1x1, 128 -> 512) -> bn3 (+ residual, ReLU) of a stage-2 identity block:
-``gemm_bf16`` mode 4 with (N, K) = (128, 512) (csrc/kernels/conv3bn3_s2_bwd.hip) and the autograd node on it.
+``conv3bn3_bwd`` with (Cin, Cout) = (128, 512) (csrc/kernels/conv3bn3_s2_bwd.hip) and the autograd node on it.
 
 The checks are those of test_conv3_bn3_bwd_gpu.py (read its docstring) with CO = 512, CI = 128: the unfused dx
 pass run from the SAME finished sums stores the dx3 that the kernel forms in registers, so it is the exact
@@ -69,15 +69,21 @@ def _dx3_from_sums(C, dy, x3, mask, bw, mean, inv, sums):
     return dx3
 
 
+def _ptr(t):
+    return t if isinstance(t, int) else t.data_ptr()
+
+
 def _launch(dy, x3, mask, bw, mean, inv, sum_dy, sum_dy_xhat, a2, w, out, part, slabs, n=CI, k=CO):
-    from fluxmpi_amd.ops.gemm import gemm
-    gemm(dy, w, out, M=dy.shape[0], N=n, K=k, lda=k, ldb=n, ldc=n, a_kmajor=True, b_kmajor=False, mode=4,
-         splits=slabs, a_affine=(sum_dy, sum_dy_xhat), stats=part, residual=a2,
-         bn_bwd=(x3, bw, None, mean, inv, mask, 3))
+    """conv3bn3_bwd; an operand may be a tensor or a raw address (0: a missing pointer)."""
+    from fluxmpi_amd.ops import _ext
+    _ext.get(required=True).conv3bn3_bwd(
+        _ptr(dy), _ptr(mask), _ptr(x3), _ptr(bw), _ptr(mean), _ptr(inv), sum_dy=_ptr(sum_dy),
+        sum_dy_xhat=_ptr(sum_dy_xhat), a2=_ptr(a2), wt=_ptr(w), d_a2=_ptr(out), ws=_ptr(part), P=dy.shape[0], Cin=n,
+        Cout=k, slabs=slabs, stream=_st())
 
 
 def _fused(dy, x3, mask, bw, mean, inv, sum_dy, sum_dy_xhat, a2, w, slabs, errs, name):
-    """gemm_bf16 mode 4 into guarded outputs; returns (d_a2 [P, 128] bf16, slabs [s, 512 * 128] fp32)."""
+    """conv3bn3_bwd into guarded outputs; returns (d_a2 [P, 128] bf16, slabs [s, 512 * 128] fp32)."""
     P = dy.shape[0]
     obuf, oview = E.guarded(P, CI, CI, torch.bfloat16, dy.device)
     sbuf, sview = E.guarded(slabs, CO * CI, CO * CI, torch.float32, dy.device)
@@ -184,8 +190,10 @@ def test_deterministic(gpu_ext):
 
 
 def test_guards(gpu_ext):
-    """Mode 4 takes (N, K) = (64, 256) and (128, 512) only, 16-byte aligned operands and 1 <= splits <= 65535:
-    anything else raises before a launch (the outputs keep their fill)."""
+    """conv3bn3_bwd takes (Cin, Cout) = (64, 256) and (128, 512) only, every required pointer, 16-byte aligned
+    operands and 1 <= slabs <= 65535: anything else raises before a launch (the outputs keep their fill). So
+    does ``gemm_bf16`` with a mode outside 0-3, on the operands that used to reach these kernels through it."""
+    from fluxmpi_amd.ops.gemm import gemm
     P = 49
     dy, a2, w, x3, mask, bw, mean, inv = _inputs("uniform", P, 6)
     sums = torch.zeros(2 * CO, device="cuda")
@@ -193,16 +201,23 @@ def test_guards(gpu_ext):
     part = torch.full((2, CO * CI), 7.0, device="cuda")
     args = (dy, x3, mask, bw, mean, inv, sums[:CO], sums[CO:], a2, w, out, part)
     for n, k in ((128, 256), (64, 512), (256, 1024), (128, 384)):
-        with pytest.raises(RuntimeError, match="mode 4"):
+        with pytest.raises(RuntimeError, match="conv3bn3_bwd"):
             _launch(*args, 2, n=n, k=k)
-    for splits in (0, -1, 65536):
-        with pytest.raises(RuntimeError, match="splits"):
-            _launch(*args, splits)
+    for slabs in (0, -1, 65536):
+        with pytest.raises(RuntimeError, match="slabs"):
+            _launch(*args, slabs)
     off = torch.zeros(P * CI + 8, device="cuda", dtype=torch.bfloat16)[1:1 + P * CI].view(P, CI)  # 2 bytes off
     with pytest.raises(RuntimeError, match="aligned"):
         _launch(dy, x3, mask, bw, mean, inv, sums[:CO], sums[CO:], off, w, out, part, 2)
     with pytest.raises(RuntimeError, match="aligned"):
         _launch(dy, x3, mask, bw, mean, inv, sums[:CO], sums[CO:], a2, w, off, part, 2)
+    with pytest.raises(RuntimeError, match="all required"):
+        _launch(dy, x3, mask, bw, mean, inv, sums[:CO], sums[CO:], 0, w, out, part, 2)
+    for mode in (4, 5, -1):  # 4: what used to reach these kernels
+        with pytest.raises(RuntimeError, match="mode"):
+            gemm(dy, w, out, M=P, N=CI, K=CO, lda=CO, ldb=CI, ldc=CI, a_kmajor=True, b_kmajor=False, mode=mode,
+                 splits=2, a_affine=(sums[:CO], sums[CO:]), stats=part, residual=a2,
+                 bn_bwd=(x3, bw, None, mean, inv, mask, 3))
     torch.cuda.synchronize()
     assert bool((out.float() == 7.0).all()) and bool((part == 7.0).all())
 
