@@ -682,4 +682,18 @@ void fp8_scale_update(void* block, int fmt, hipStream_t stream);
 void fp8_gemm(const void* a, const void* b, void* c, const void* bias, int bias_dtype, const void* sa, const void* sb,
               int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int fa, int fb, hipStream_t stream);
 
+// ---- MX block-scaled fp8 (mx_quant.hip, mx_gemm.hip; the format and the limits in kernels/mx_host.h) ----
+// One power-of-two scale per 32 elements along the reduction axis, stored as the E8M0 byte of its inverse in a
+// scale image (one dword per row and 128 elements, padded with 127). No scale blocks, no state, no atomics.
+// x bf16 [R][ld], C % 32 == 0 -> q [R][ldq] with s [R][lds] (blocks along C) and / or qt [C][ldt] with
+// st [C][ldst] (blocks along R, R % 32 == 0), in one launch; each pair may be null.
+void mx_quantize(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, void* q, int64_t ldq, void* s, int64_t lds,
+                 void* qt, int64_t ldt, void* st, int64_t ldst, hipStream_t stream);
+// c bf16 [M][ldc] = sum over K blocks of 2^(sa - 127) 2^(sb - 127) a_blk . b_blk (+ bias [N], bf16 = 9 or fp32 = 7,
+// may be null) on v_mfma_scale_f32_16x16x128_f8f6f4: fa x fb e4m3 x e4m3 or e5m2 x e4m3, K % 32 == 0, N % 8 == 0;
+// sa [M][ldsa], sb [N][ldsb]: the operands' scale images
+void mx_gemm(const void* a, const void* b, void* c, const void* bias, int bias_dtype, const void* sa, const void* sb,
+             int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa,
+             int fb, hipStream_t stream);
+
 }  // namespace fluxmpi

@@ -1,0 +1,103 @@
+// Host side of the MX (block-scaled fp8) entries (mx_quant.hip, mx_gemm.hip) without the launches: the
+// argument checks and the launch geometry, plain C++ as fp8_host.h (scripts/mx_host_check.cpp walks them
+// under a sanitizer).
+//
+// The format: a block is kMxBlock = 32 consecutive elements along the reduction axis of the GEMM that reads
+// the image. Its elements are fp8 (fp8_host.h's formats) of x * s with s = 2^floor(log2(FMAX / block amax)),
+// exponent kept in -126 .. 126, 1 for an amax of 0, inf or NaN; what is stored per block is the E8M0 byte of
+// 1 / s, b = 127 - log2(s) in 1 .. 253. A scale image has one row per image row: the row's block bytes in
+// order, then 127 (= 2^0) up to 4 ceil(blocks / 4), so that one aligned dword holds the four blocks of one
+// 128-byte K tile (mx_scale_row).
+//   quantise: a workgroup owns a kMxQTile x kMxQTile tile of x, i.e. whole scale dwords of both images; the
+//             grid is col_tiles x row_tiles with the column tiles of one row tile adjacent.
+//   GEMM:     fp8_host.h's geometry (128 x 128 of C per workgroup, K in tiles of 128 bytes).
+#pragma once
+#include "fp8_host.h"
+
+namespace fluxmpi {
+
+constexpr int kMxBlock = 32;
+constexpr int kMxQTile = 128;       // quantise tile: rows and columns (4 blocks = one scale dword each way)
+constexpr unsigned kMxOne = 127;    // the E8M0 byte of 2^0: padding, empty and non-finite blocks
+
+struct MxQuantGeometry {
+  int64_t col_tiles, row_tiles, grid;
+};
+
+// bytes of a scale row for a reduction length k: one dword per 128-byte K tile
+inline int64_t mx_scale_row(int64_t k) { return 4 * ((k + 127) / 128); }
+
+inline void mx_scale_check(const char* e, const void* s, int64_t lds, int64_t k, const char* what) {
+  if (s == nullptr) fp8_fail(e, std::string("null ") + what);
+  if (reinterpret_cast<uintptr_t>(s) % 4 != 0) fp8_fail(e, std::string(what) + " must be 4-byte aligned");
+  if (lds < mx_scale_row(k) || lds % 4 != 0)
+    fp8_fail(e, std::string(what) + ": the row stride must be >= 4 ceil(K / 128) and a multiple of 4");
+}
+
+// x bf16 [R][C] (row stride ld elements), C % 32 == 0. Row-wise image: q [R][ldq] with s [R][lds], both or
+// neither. Transposed image (blocks along R, so R % 32 == 0): qt [C][ldt] with st [C][ldst], both or neither.
+inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, const void* q,
+                                      int64_t ldq, const void* s, int64_t lds, const void* qt, int64_t ldt,
+                                      const void* st, int64_t ldst) {
+  const char* e = "mx_quantize";
+  fp8_format_check(e, fmt);
+  if (R < 1 || R > kFp8MaxDim) fp8_fail(e, "R must lie in 1 .. 2^31 - 256");
+  if (C < kMxBlock || C % kMxBlock != 0 || C > kFp8MaxDim)
+    fp8_fail(e, "C must be a positive multiple of 32 below 2^31 - 256");
+  if (ld < C || ld % 8 != 0) fp8_fail(e, "the input's row stride must be >= C and a multiple of 8 elements");
+  if (x == nullptr) fp8_fail(e, "null input");
+  if (!fp8_aligned16(x)) fp8_fail(e, "the input must be 16-byte aligned");
+  if ((q == nullptr) != (s == nullptr)) fp8_fail(e, "the row-wise image and its scales come together");
+  if ((qt == nullptr) != (st == nullptr)) fp8_fail(e, "the transposed image and its scales come together");
+  if (q == nullptr && qt == nullptr) fp8_fail(e, "nothing to do: no output");
+  if (q != nullptr) {
+    if (!fp8_aligned16(q)) fp8_fail(e, "the output must be 16-byte aligned");
+    if (ldq < C || ldq % 16 != 0) fp8_fail(e, "the output's row stride must be >= C and a multiple of 16");
+    mx_scale_check(e, s, lds, C, "the scale image");
+  }
+  if (qt != nullptr) {
+    if (R % kMxBlock != 0) fp8_fail(e, "the transposed image needs R % 32 == 0 (its blocks run along R)");
+    if (!fp8_aligned16(qt)) fp8_fail(e, "the transposed output must be 16-byte aligned");
+    if (ldt < R || ldt % 16 != 0) fp8_fail(e, "the transposed output's row stride must be >= R and a multiple of 16");
+    mx_scale_check(e, st, ldst, R, "the transposed scale image");
+  }
+  MxQuantGeometry g{};
+  g.col_tiles = (C + kMxQTile - 1) / kMxQTile;
+  g.row_tiles = (R + kMxQTile - 1) / kMxQTile;
+  g.grid = g.col_tiles * g.row_tiles;
+  if (g.grid > 0x7fffffffLL) fp8_fail(e, "too many workgroups for one launch");
+  return g;
+}
+
+// C bf16 [M][ldc] = A fp8 [M][K] (lda bytes, scales sa [M][ldsa]) x B fp8 [N][K] (ldb, sb [N][ldsb]); bias [N]
+// bf16 (9) or fp32 (7) or null
+inline Fp8GemmGeometry mx_gemm_check(const void* a, const void* b, const void* c, const void* bias, int bias_dtype,
+                                     const void* sa, const void* sb, int64_t M, int64_t N, int64_t K, int64_t lda,
+                                     int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa, int fb) {
+  const char* e = "mx_gemm";
+  fp8_format_check(e, fa);
+  fp8_format_check(e, fb);
+  if (fb != kFp8E4M3) fp8_fail(e, "the B operand is e4m3 (e4m3 x e4m3 and e5m2 x e4m3 are built)");
+  if (M < 1 || M > kFp8MaxDim) fp8_fail(e, "M must lie in 1 .. 2^31 - 256");
+  if (N < 8 || N % 8 != 0 || N > kFp8MaxDim) fp8_fail(e, "N must be a positive multiple of 8 below 2^31 - 256");
+  if (K < kMxBlock || K % kMxBlock != 0 || K > kFp8MaxDim)
+    fp8_fail(e, "K must be a positive multiple of 32 below 2^31 - 256");
+  if (lda < K || lda % 16 != 0 || ldb < K || ldb % 16 != 0)
+    fp8_fail(e, "the operands' row strides must be >= K and multiples of 16 bytes");
+  if (ldc < N || ldc % 8 != 0) fp8_fail(e, "the output's row stride must be >= N and a multiple of 8 elements");
+  if (a == nullptr || b == nullptr || c == nullptr) fp8_fail(e, "null tensor");
+  if (!fp8_aligned16(a) || !fp8_aligned16(b) || !fp8_aligned16(c) || !fp8_aligned16(bias))
+    fp8_fail(e, "every tensor must be 16-byte aligned");
+  if (bias != nullptr && bias_dtype != 9 && bias_dtype != 7) fp8_fail(e, "the bias is bf16 or fp32");
+  mx_scale_check(e, sa, ldsa, K, "A's scale image");
+  mx_scale_check(e, sb, ldsb, K, "B's scale image");
+  Fp8GemmGeometry g{};
+  g.m_tiles = (M + kFp8Tile - 1) / kFp8Tile;
+  g.n_tiles = (N + kFp8Tile - 1) / kFp8Tile;
+  g.grid = g.m_tiles * g.n_tiles;
+  if (g.grid > 0x7fffffffLL) fp8_fail(e, "too many workgroups for one launch");
+  g.k_tiles = static_cast<int>((K + kFp8TileK - 1) / kFp8TileK);
+  return g;
+}
+
+}  // namespace fluxmpi

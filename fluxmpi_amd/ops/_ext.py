@@ -9,7 +9,9 @@
 * the native RCCL communicator (``csrc/comm/rccl_comm.cpp``).
 
 Every native call goes through :func:`get`; a new entry is one more ``m.def`` in ``_C``
-(``tests/test_bindings_surface.py`` says what may change in its surface).
+(``tests/test_bindings_surface.py`` says what may change in its surface). The exception goes through
+:func:`submodule`: the MX fp8 entries (:func:`mx`, ``_C_mx``) are a further pybind11 module of the same shared
+object, until ``_C``'s recorded surface is next re-recorded.
 
 The binding layer is plain pybind11 that takes raw device pointers and a HIP
 stream handle, so the kernels are independent of the ATen C++ ABI and can be
@@ -25,6 +27,7 @@ and as the numerics oracle in tests.
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import os
 
 import torch
@@ -75,6 +78,34 @@ def get(required: bool = True):
             f"{_ERR!r}. Run `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`."
         )
     return mod
+
+
+_SUB: dict = {}
+
+
+def submodule(name: str, what: str):
+    """A further pybind11 module ``fluxmpi_amd.<name>`` of the shared object ``_C`` was loaded from (its
+    ``PyInit_<name>``); ``what`` names its entries in the error. Missing: an error, as for ``_C``."""
+    mod = _SUB.get(name)
+    if mod is None:
+        C = get(required=True)
+        if C is None:
+            raise NativeExtensionError(f"fluxmpi_amd.{name} needs the native extension fluxmpi_amd._C")
+        spec = importlib.util.spec_from_file_location(f"fluxmpi_amd.{name}", C.__file__)
+        try:
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        except Exception as e:
+            raise NativeExtensionError(
+                f"fluxmpi_amd.{name} ({what} of {C.__file__}) failed to load: {e!r}. "
+                "Rebuild: `python -c 'import fluxmpi_amd; fluxmpi_amd.build()'`.") from e
+        _SUB[name] = mod
+    return mod
+
+
+def mx():
+    """The ``_C_mx`` module (``mx_quantize``, ``mx_gemm``; ``csrc/kernels/mx_quant.hip``, ``mx_gemm.hip``)."""
+    return submodule("_C_mx", "the MX fp8 entries")
 
 
 def require_for(t: torch.Tensor):

@@ -193,14 +193,15 @@ def supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
 
 class Fp8State:
     """What an fp8 Linear keeps between calls: the scaling mode, under ``"delayed"`` the three scale blocks
-    (``blocks [3, 8]`` int32: x, W, dy; made on first use, scale 1). ``W``'s images are NOT kept from one forward
+    (``blocks [3, 8]`` int32: x, W, dy; made on first use, scale 1); ``"mx"`` (block scaling, the MX section
+    below) keeps nothing and uses no scale block. ``W``'s images are NOT kept from one forward
     to the next: the fused optimisers write the parameters through raw pointers and leave ``weight._version``
     alone, so nothing the module can see says that a cached image is still the weight's. A forward casts ``W``
     (two small launches beside the activation's) and hands the images to its own backward."""
 
     def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None):
-        if scaling not in ("current", "delayed"):
-            raise ValueError(f"fp8_linear: scaling must be 'current' or 'delayed', got {scaling!r}")
+        if scaling not in ("current", "delayed", "mx"):
+            raise ValueError(f"fp8_linear: scaling must be 'current', 'delayed' or 'mx', got {scaling!r}")
         self.scaling = scaling
         self.blocks = blocks
 
@@ -249,15 +250,18 @@ class _Fp8LinearFn(torch.autograd.Function):
 def fp8_linear(x, weight, bias=None, state: Fp8State | None = None) -> torch.Tensor:
     """``F.linear`` with the forward and the input gradient in fp8 (see the module); ``state=None`` is stateless
     current scaling. Unsupported input (:func:`supported`) takes ``ops.linear.linear``."""
+    state = state if state is not None else Fp8State()
+    if state.scaling == "mx":
+        return _MxLinearFn.apply(x, weight, bias) if mx_supported(x, weight) else linear(x, weight, bias)
     if not supported(x, weight):
         return linear(x, weight, bias)
-    return _Fp8LinearFn.apply(x, weight, bias, state if state is not None else Fp8State())
+    return _Fp8LinearFn.apply(x, weight, bias, state)
 
 
 class Fp8Linear(torch.nn.Linear):
     """Drop-in for ``ops.linear.Linear``: same parameters and ``state_dict()``; the weight stays bf16 and the
     fp8 images are per-step scratch. ``scaling="delayed"`` keeps its three scale blocks in a non-persistent
-    buffer."""
+    buffer; ``scaling="mx"`` is block scaling (``mx_quant.hip``, ``mx_gemm.hip``) where :func:`mx_supported`."""
 
     def __init__(self, in_features, out_features, bias=True, scaling="current", **kw):
         super().__init__(in_features, out_features, bias=bias, **kw)
@@ -265,6 +269,8 @@ class Fp8Linear(torch.nn.Linear):
         self.register_buffer("fp8_blocks", torch.stack([new_block("cpu") for _ in range(3)]), persistent=False)
 
     def forward(self, x):
+        if self.fp8.scaling == "mx":
+            return fp8_linear(x, self.weight, self.bias, self.fp8)
         if not supported(x, self.weight):
             return linear(x, self.weight, self.bias)
         self.fp8.blocks = self.fp8_blocks  # follows .to(device)
@@ -287,6 +293,194 @@ def fp8_linear_reference(x, w, b, dy, scales=None):
     return y, dyd @ wd, ya, dyd.abs() @ wd.abs()
 
 
+# ---------------------------------------------------------------------------------------------------- MX
+# Block scaling (OCP MX): one :func:`pow2_scale` per MX_BLOCK consecutive elements along the reduction axis of
+# the GEMM that reads the image, stored as the E8M0 byte of its inverse, ``127 - log2(s)`` (1 .. 253; 127 for an
+# all-zero or non-finite block). ``csrc/kernels/mx_quant.hip`` casts in ONE launch with no amax pass, no scale
+# block and no state; ``mx_gemm.hip`` applies the scales inside ``v_mfma_scale_f32_16x16x128_f8f6f4``.
+MX_BLOCK = 32
+MX_ONE = 127
+
+
+def mx_scale_cols(k: int) -> int:
+    """Bytes of a scale-image row for a reduction length ``k``: a dword per 128 elements."""
+    return 4 * (-(-k // 128))
+
+
+@dataclass
+class MxTensor:
+    """An MX image of a bf16 matrix ``[R, C]``: ``q [R, C]`` uint8 bit patterns of ``fmt`` with ``scales
+    [R, 4 ceil(C / 128)]`` (the ``C / 32`` block bytes of a row, then 127), blocks along ``C``; and, when asked for,
+    ``q_t [C, R]`` with ``scales_t [C, 4 ceil(R / 128)]``, blocks along ``R``: an image of its own, not ``q``'s
+    transpose."""
+    q: torch.Tensor
+    scales: torch.Tensor
+    q_t: torch.Tensor | None
+    scales_t: torch.Tensor | None
+    fmt: str
+
+    def t(self) -> "MxTensor":
+        """The transposed image as a GEMM operand."""
+        if self.q_t is None:
+            raise ValueError("fp8.mx: this tensor was quantised without its transposed image")
+        return MxTensor(self.q_t, self.scales_t, None, None, self.fmt)
+
+
+def mx_quantize_reference(x: torch.Tensor, fmt: str):
+    """``(q, bytes)`` on the CPU: ``q`` float8 ``[R, C]`` and the blocks' E8M0 bytes uint8 ``[R, C / 32]``, blocks
+    along the last axis; :func:`pow2_scale` of every block's amax (vectorised with ``torch.frexp``), torch's
+    round-to-nearest-even cast, non-finite inputs kept non-finite in a block of scale 1."""
+    xf = x.detach().float().cpu()
+    r, c = xf.shape
+    if c % MX_BLOCK:
+        raise ValueError(f"fp8.mx: the blocked axis must be a multiple of {MX_BLOCK}, got {c}")
+    blk = xf.view(r, c // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(-1)
+    ok = torch.isfinite(amax) & (amax > 0)
+    m, e = torch.frexp(torch.where(ok, amax, torch.ones_like(amax)))  # amax = (2 m) 2^(e - 1), 2 m in [1, 2)
+    p = int(math.log2(FMAX[_fmt(fmt)] / 1.75)) - (e - 1) - (2 * m > 1.75).int()
+    p = torch.where(ok, p.clamp(-126, 126), torch.zeros_like(p))
+    y = (blk * torch.ldexp(torch.ones_like(amax), p).unsqueeze(-1)).clamp(-FMAX[fmt], FMAX[fmt])
+    return torch.where(torch.isfinite(blk), y, blk).view(r, c).to(TORCH_DTYPE[fmt]), (MX_ONE - p).to(torch.uint8)
+
+
+def mx_dequantize(q: torch.Tensor, block_bytes: torch.Tensor) -> torch.Tensor:
+    """float64 values of a reference image: ``q 2^(byte - 127)`` block by block (exact)."""
+    return q.double() * torch.ldexp(torch.ones(1, dtype=torch.float64),
+                                    block_bytes.int() - MX_ONE).repeat_interleave(MX_BLOCK, 1)
+
+
+def mx_scale_image(block_bytes: torch.Tensor) -> torch.Tensor:
+    """Block bytes ``[R, C / 32]`` as a scale image ``[R, 4 ceil(C / 128)]``, padded with 127."""
+    r, nb = block_bytes.shape
+    out = torch.full((r, mx_scale_cols(nb * MX_BLOCK)), MX_ONE, dtype=torch.uint8, device=block_bytes.device)
+    out[:, :nb] = block_bytes
+    return out
+
+
+def mx_layout_ok(x: torch.Tensor) -> bool:
+    """What ``mx_quantize`` takes: a bf16 matrix with unit column stride, ``C % 32 == 0``, a row stride that is a
+    multiple of 8 elements, a 16-byte aligned base."""
+    return (x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[0] >= 1 and x.shape[1] >= MX_BLOCK
+            and x.shape[1] % MX_BLOCK == 0 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
+            and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0)
+
+
+def mx_quantize_into(x, fmt, q=None, scales=None, q_t=None, scales_t=None) -> None:
+    """One ``mx_quantize`` launch on ``x [R, C]`` into the uint8 views ``q [R, C]`` with ``scales`` and / or
+    ``q_t [C, R]`` with ``scales_t`` (each pair may be None; shapes as :class:`MxTensor`)."""
+    if not (x.is_cuda and mx_layout_ok(x)):
+        raise ValueError("fp8.mx_quantize: the input must be a bf16 CUDA matrix with C % 32 == 0, a row stride "
+                         "that is a multiple of 8 and a 16-byte aligned base")
+    r, c = x.shape
+    if q_t is not None and r % MX_BLOCK:
+        raise ValueError(f"fp8.mx_quantize: the transposed image needs R % {MX_BLOCK} == 0, got R = {r}")
+    for o, shape in ((q, (r, c)), (scales, (r, mx_scale_cols(c))), (q_t, (c, r)), (scales_t, (c, mx_scale_cols(r)))):
+        if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != shape or o.stride(1) != 1):
+            raise ValueError(f"fp8.mx_quantize: an output must be a uint8 view of shape {shape}")
+    if (q is None) != (scales is None) or (q_t is None) != (scales_t is None) or (q is None and q_t is None):
+        raise ValueError("fp8.mx_quantize: an image and its scales come together, and one pair is needed")
+    arg = lambda o: (o.data_ptr(), o.stride(0)) if o is not None else (0, 0)
+    _ext.mx().mx_quantize(x.data_ptr(), r, c, x.stride(0), FMT_CODE[_fmt(fmt)], *arg(q), *arg(scales), *arg(q_t),
+                          *arg(scales_t), _stream(x))
+
+
+def mx_quantize(x: torch.Tensor, fmt: str, transpose: bool = False) -> MxTensor:
+    """The MX image of the bf16 matrix ``x`` in one launch; ``transpose``: the image blocked along ``R`` too."""
+    _fmt(fmt)
+    if not x.is_cuda or x.dim() != 2:
+        raise ValueError("fp8.mx_quantize: the input is a bf16 matrix on the GPU (CPU tensors take "
+                         "mx_quantize_reference)")
+    r, c = x.shape
+    new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=x.device)
+    t = MxTensor(new(r, c), new(r, mx_scale_cols(c)), new(c, r) if transpose else None,
+                 new(c, mx_scale_cols(r)) if transpose else None, fmt)
+    mx_quantize_into(x, fmt, t.q, t.scales, t.q_t, t.scales_t)
+    return t
+
+
+def mx_gemm_into(out: torch.Tensor, a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`mx_gemm` into the bf16 view ``out [M, N]`` (any row stride that is a multiple of 8)."""
+    m, k = a.q.shape
+    n = b.q.shape[0]
+    if (a.fmt, b.fmt) not in ((E4M3, E4M3), (E5M2, E4M3)):
+        raise ValueError("fp8.mx_gemm: the operands are e4m3 x e4m3 or e5m2 x e4m3")
+    if not a.q.is_cuda or b.q.shape[1] != k or k % MX_BLOCK or n % 8:
+        raise ValueError(f"fp8.mx_gemm: a [M, K] and b [N, K] on the GPU need K % 32 == 0 and N % 8 == 0, got "
+                         f"{tuple(a.q.shape)} and {tuple(b.q.shape)}")
+    for t, rows in ((a, m), (b, n)):
+        if t.scales.dtype != torch.uint8 or t.scales.shape[0] != rows or t.scales.shape[1] < mx_scale_cols(k):
+            raise ValueError(f"fp8.mx_gemm: a scale image must be uint8 [{rows}, >= {mx_scale_cols(k)}]")
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (m, n) or out.stride(1) != 1:
+        raise ValueError(f"fp8.mx_gemm: the output must be a bf16 view of shape {(m, n)}")
+    if bias is not None:
+        bias = bias.detach()
+        if bias.dtype not in (torch.bfloat16, torch.float32):
+            bias = bias.float()
+        bias = bias.contiguous()
+        if bias.numel() != n:
+            raise ValueError(f"fp8.mx_gemm: the bias must have {n} elements")
+    _ext.mx().mx_gemm(
+        a.q.data_ptr(), b.q.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else 0,
+        DTYPE_CODE[bias.dtype] if bias is not None else 0, a.scales.data_ptr(), b.scales.data_ptr(), m, n, k,
+        a.q.stride(0), b.q.stride(0), out.stride(0), a.scales.stride(0), b.scales.stride(0), FMT_CODE[a.fmt],
+        FMT_CODE[b.fmt], _stream(a.q))
+    return out
+
+
+def mx_gemm(a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """``bf16(sum over K blocks of the dequantised a_blk . b_blk + bias)``: ``a [M, K]`` e4m3 or e5m2, ``b [N, K]``
+    e4m3, the block scales applied inside the MFMA, fp32 accumulation."""
+    out = torch.empty(a.q.shape[0], b.q.shape[0], dtype=torch.bfloat16, device=a.q.device)
+    return mx_gemm_into(out, a, b, bias)
+
+
+def mx_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """:func:`supported` with both widths multiples of 32 (each is the blocked axis of one GEMM)."""
+    return supported(x, weight) and weight.shape[0] % MX_BLOCK == 0 and weight.shape[1] % MX_BLOCK == 0
+
+
+class _MxLinearFn(torch.autograd.Function):
+    """x, W and dy all in e4m3 (the OCP / Transformer Engine recipe: with a scale per 32 values e5m2's range is
+    not needed); W's two images come from one launch in every forward (:class:`Fp8State` says why)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        n_out, n_in = weight.shape
+        wq = mx_quantize(weight.detach(), E4M3, transpose=True)
+        xq = mx_quantize(x.view(-1, n_in), E4M3)
+        ctx.save_for_backward(x, weight)
+        ctx.wq, ctx.bias = wq, bias
+        return mx_gemm(xq, wq, bias).view(*x.shape[:-1], n_out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        n_out, n_in = w.shape
+        dy2 = dy.reshape(-1, n_out)
+        if dy2.dtype != torch.bfloat16 or not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.to(torch.bfloat16).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = mx_gemm(mx_quantize(dy2, E4M3), ctx.wq.t()).view(x.shape)
+        need_b = ctx.bias is not None and ctx.needs_input_grad[2]
+        dw, db = wgrad_bgrad(x.reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
+        return dx, dw, db
+
+
+def mx_linear_reference(x, w, b, dy):
+    """``(y, dx, |y|, |dx|)`` in float64 on the CPU of the same quantisation, as :func:`fp8_linear_reference`: x and
+    w blocked along ``n_in`` for y, dy and w blocked along ``n_out`` for dx, all e4m3."""
+    n_out, n_in = w.shape
+    xd, wd, dyd, wtd = (mx_dequantize(*mx_quantize_reference(t, E4M3)) for t in
+                        (x.reshape(-1, n_in), w, dy.reshape(-1, n_out), w.detach().t().contiguous()))
+    bd = b.detach().double().cpu() if b is not None else torch.zeros(n_out, dtype=torch.float64)
+    y, ya = xd @ wd.t() + bd, xd.abs() @ wd.abs().t() + bd.abs()
+    return y, dyd @ wtd.t(), ya, dyd.abs() @ wtd.abs().t()
+
+
 __all__ = ["E4M3", "E5M2", "FMAX", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
            "quantize", "quantize_into", "quantize_reference", "pow2_scale", "scale_update", "new_block", "gemm",
-           "gemm_into", "supported", "layout_ok"]
+           "gemm_into", "supported", "layout_ok", "MX_BLOCK", "MxTensor", "mx_quantize", "mx_quantize_into",
+           "mx_quantize_reference", "mx_dequantize", "mx_scale_image", "mx_gemm", "mx_gemm_into", "mx_supported",
+           "mx_linear_reference"]

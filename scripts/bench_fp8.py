@@ -7,7 +7,9 @@ Variants, alternated in one process, each a HIP-graph replay:
   gemm_{fwd,dgrad}_{qkv,proj,fc1,fc2}_{fp8,bf16}   the GEMM alone: ``fp8.gemm`` on images made beforehand against
                                                    ``ops.linear.fwd`` / ``dgrad`` (gemm_nt.hip, else hipBLASLt)
   quant_x_{current,delayed}                        the activation's cast passes alone ([50432, 768], e4m3)
-  qkv_fwdbwd_{bf16,fp8_current,fp8_delayed}        ``Linear`` / ``Fp8Linear`` forward + backward (dx, dW, db)
+  qkv_fwdbwd_{bf16,fp8_current,fp8_delayed,fp8_mx} ``Linear`` / ``Fp8Linear`` forward + backward (dx, dW, db)
+  gemm_{fwd,dgrad}_*_fp8_mx, quant_x_mx, quant_w_mx the MX block-scaled counterparts (``mx_gemm.hip``, ``mx_quant.hip``:
+                                                   one launch per cast; ``quant_w_mx`` is W [2304, 768], both images)
 
 One JSON line per variant with the median of the rounds and min-max; fp8 lines carry ``bf16_over_fp8`` and the
 GEMM lines the achieved PFLOP/s (2 M N K over the median).
@@ -47,12 +49,15 @@ def main():
     for name, (n_in, n_out) in LAYERS.items():
         x, w, b, dy = rnd(M, n_in), rnd(n_out, n_in) * n_in ** -0.5, rnd(n_out), rnd(M, n_out)
         xq, wq, dyq = fp8.quantize(x, fp8.E4M3), fp8.quantize(w, fp8.E4M3, transpose=True), fp8.quantize(dy, fp8.E5M2)
-        keep += [x, w, b, dy, xq, wq, dyq]
+        xm, wm, dym = fp8.mx_quantize(x, fp8.E4M3), fp8.mx_quantize(w, fp8.E4M3, transpose=True), fp8.mx_quantize(dy, fp8.E4M3)
+        keep += [x, w, b, dy, xq, wq, dyq, xm, wm, dym]
         with torch.no_grad():
             for key, f in ((f"gemm_fwd_{name}_fp8", lambda xq=xq, wq=wq, b=b: fp8.gemm(xq, wq, b)),
                            (f"gemm_fwd_{name}_bf16", lambda x=x, w=w, b=b: L.fwd(x, w, b)),
                            (f"gemm_dgrad_{name}_fp8", lambda dyq=dyq, wq=wq: fp8.gemm(dyq, wq.t())),
-                           (f"gemm_dgrad_{name}_bf16", lambda dy=dy, w=w: L.dgrad(dy, w))):
+                           (f"gemm_dgrad_{name}_bf16", lambda dy=dy, w=w: L.dgrad(dy, w)),
+                           (f"gemm_fwd_{name}_fp8_mx", lambda xm=xm, wm=wm, b=b: fp8.mx_gemm(xm, wm, b)),
+                           (f"gemm_dgrad_{name}_fp8_mx", lambda dym=dym, wm=wm: fp8.mx_gemm(dym, wm.t()))):
                 fns[key], out = graphed(f)
                 flops[key] = 2.0 * M * n_in * n_out
                 keep += [f, out]
@@ -65,11 +70,15 @@ def main():
         fp8.scale_update(blk, fp8.E4M3)
         return fp8.quantize(x.detach(), fp8.E4M3, blk)
 
-    for key, f in (("quant_x_current", lambda: fp8.quantize(x.detach(), fp8.E4M3)), ("quant_x_delayed", delayed_cast)):
+    wqkv = rnd(n_out, n_in) * n_in ** -0.5
+    for key, f in (("quant_x_current", lambda: fp8.quantize(x.detach(), fp8.E4M3)), ("quant_x_delayed", delayed_cast),
+                   ("quant_x_mx", lambda: fp8.mx_quantize(x.detach(), fp8.E4M3)),
+                   ("quant_w_mx", lambda: fp8.mx_quantize(wqkv, fp8.E4M3, transpose=True))):
         fns[key], out = graphed(f)
         keep += [f, out]
     for key, lin in (("bf16", L.Linear(n_in, n_out)), ("fp8_current", fp8.Fp8Linear(n_in, n_out)),
-                     ("fp8_delayed", fp8.Fp8Linear(n_in, n_out, scaling="delayed"))):
+                     ("fp8_delayed", fp8.Fp8Linear(n_in, n_out, scaling="delayed")),
+                     ("fp8_mx", fp8.Fp8Linear(n_in, n_out, scaling="mx"))):
         lin = lin.cuda().bfloat16()
 
         def fwdbwd(lin=lin):
@@ -96,7 +105,7 @@ def main():
                  "rounds": a.rounds, "iters": a.iters, "mode": "graph", "tokens": M}
             if k in flops:
                 r["pflops"] = round(flops[k] / med[k] * 1e-9, 3)
-            base = k.replace("_fp8", "_bf16") if k.startswith("gemm_") else "qkv_fwdbwd_bf16"
+            base = k.replace("_fp8_mx", "_bf16").replace("_fp8", "_bf16") if k.startswith("gemm_") else "qkv_fwdbwd_bf16"
             if "fp8" in k and base in med:
                 r["bf16_over_fp8"] = round(med[base] / med[k], 2)
                 r["faster_than_bf16_worst_case"] = bool(max(v) < min(us[base]))
