@@ -682,7 +682,7 @@ void fp8_scale_update(void* block, int fmt, hipStream_t stream);
 void fp8_gemm(const void* a, const void* b, void* c, const void* bias, int bias_dtype, const void* sa, const void* sb,
               int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int fa, int fb, hipStream_t stream);
 
-// ---- MX block-scaled fp8 (mx_quant.hip, mx_gemm.hip; the format and the limits in kernels/mx_host.h) ----
+// ---- MX block-scaled fp8 (mx_quant.hip, mx_gemm.hip, mx_wgrad.hip; the format and the limits in kernels/mx_host.h) ----
 // One power-of-two scale per 32 elements along the reduction axis, stored as the E8M0 byte of its inverse in a
 // scale image (one dword per row and 128 elements, padded with 127). No scale blocks, no state, no atomics.
 // x bf16 [R][ld], C % 32 == 0 -> q [R][ldq] with s [R][lds] (blocks along C) and / or qt [C][ldt] with
@@ -695,5 +695,11 @@ void mx_quantize(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, void*
 void mx_gemm(const void* a, const void* b, void* c, const void* bias, int bias_dtype, const void* sa, const void* sb,
              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa,
              int fb, hipStream_t stream);
+// The weight gradient's shape (mx_wgrad.hip): ws fp32 [splits][M][N], ws[s] = the block-scaled products of a [M][K] and
+// b [N][K] (as mx_gemm's operands) over the 128-byte K tiles of split s; M = 1 .. , N % 8 == 0, K % 32 == 0. splits
+// must be mx_wgrad_splits(K, wanted) of kernels/mx_host.h (whole K tiles, no empty range), from which the caller
+// sizes ws; sum the splits with gemm_splitk_reduce (fixed order, no atomics)
+void mx_wgrad(const void* a, const void* b, float* ws, const void* sa, const void* sb, int64_t M, int64_t N, int64_t K,
+              int64_t lda, int64_t ldb, int64_t ldsa, int64_t ldsb, int fa, int fb, int splits, hipStream_t stream);
 
 }  // namespace fluxmpi

@@ -13,6 +13,7 @@
 
 #include "api.h"
 #include "comm/rccl_comm.h"
+#include "kernels/mx_host.h"
 
 namespace py = pybind11;
 using namespace fluxmpi;
@@ -436,11 +437,17 @@ PYBIND11_MODULE(_C, m) {
 // block-scaled fp8 entries (csrc/kernels/mx_quant.hip, mx_gemm.hip), beside `_C` so that its recorded
 // surface stays as it is until it is next re-recorded.
 PYBIND11_MODULE(_C_mx, m) {
-  m.doc() = "fluxmpi_amd native library: the MX fp8 entries (csrc/kernels/mx_quant.hip, mx_gemm.hip)";
+  m.doc() = "fluxmpi_amd native library: the MX fp8 entries (csrc/kernels/mx_quant.hip, mx_gemm.hip, mx_wgrad.hip)";
   m.def("mx_quantize", raw(&mx_quantize), py::arg("x"), py::arg("R"), py::arg("C"), py::arg("ld"), py::arg("fmt"),
         py::arg("q"), py::arg("ldq"), py::arg("s"), py::arg("lds"), py::arg("qt"), py::arg("ldt"), py::arg("st"),
         py::arg("ldst"), py::arg("stream"));
   m.def("mx_gemm", raw(&mx_gemm), py::arg("a"), py::arg("b"), py::arg("c"), py::arg("bias"), py::arg("bias_dtype"),
         py::arg("sa"), py::arg("sb"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"),
         py::arg("ldc"), py::arg("ldsa"), py::arg("ldsb"), py::arg("fa"), py::arg("fb"), py::arg("stream"));
+  m.def("mx_wgrad", raw(&mx_wgrad), py::arg("a"), py::arg("b"), py::arg("ws"), py::arg("sa"), py::arg("sb"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"), py::arg("ldsa"), py::arg("ldsb"), py::arg("fa"),
+        py::arg("fb"), py::arg("splits"), py::arg("stream"));
+  m.def("mx_wgrad_splits", &mx_wgrad_splits, py::arg("K"), py::arg("wanted"));
+  m.attr("MX_WGRAD_TILE") = kMxWgTile;
+  m.attr("MX_WGRAD_PER_CU") = kMxWgPerCu;
 }

@@ -1,4 +1,4 @@
-// Host side of the MX (block-scaled fp8) entries (mx_quant.hip, mx_gemm.hip) without the launches: the
+// Host side of the MX (block-scaled fp8) entries (mx_quant.hip, mx_gemm.hip, mx_wgrad.hip) without the launches: the
 // argument checks and the launch geometry, plain C++ as fp8_host.h (scripts/mx_host_check.cpp walks them
 // under a sanitizer).
 //
@@ -11,6 +11,7 @@
 //   quantise: a workgroup owns a kMxQTile x kMxQTile tile of x, i.e. whole scale dwords of both images; the
 //             grid is col_tiles x row_tiles with the column tiles of one row tile adjacent.
 //   GEMM:     fp8_host.h's geometry (128 x 128 of C per workgroup, K in tiles of 128 bytes).
+//   wgrad:    256 x 256 of the output per workgroup, the K tiles split over workgroups (below).
 #pragma once
 #include "fp8_host.h"
 
@@ -97,6 +98,65 @@ inline Fp8GemmGeometry mx_gemm_check(const void* a, const void* b, const void* c
   g.grid = g.m_tiles * g.n_tiles;
   if (g.grid > 0x7fffffffLL) fp8_fail(e, "too many workgroups for one launch");
   g.k_tiles = static_cast<int>((K + kFp8TileK - 1) / kFp8TileK);
+  return g;
+}
+
+// ---- the weight gradient (mx_wgrad.hip): ws fp32 [splits][M][N], split s = the K tiles of its range ----
+constexpr int kMxWgTile = 256;     // rows and columns of the output per workgroup
+constexpr int kMxWgThreads = 512;  // 8 waves: 2 (M) x 4 (N), 128 x 64 each
+constexpr int kMxWgPerCu = 1;      // workgroups resident per CU (132 KiB of LDS each)
+
+struct MxWgradGeometry {
+  int64_t m_tiles, n_tiles, tiles, grid;
+  int k_tiles, splits;
+};
+
+// K tiles of split s out of `splits` over `k_tiles`: contiguous, sizes differing by at most one, none empty
+// (splits <= k_tiles): the first k_tiles % splits ranges hold one tile more. constexpr: the kernel calls it too
+constexpr int mx_wgrad_first_tile(int k_tiles, int splits, int s) {
+  const int base = k_tiles / splits, rem = k_tiles % splits;
+  return s * base + (s < rem ? s : rem);
+}
+
+// the split count a launch uses for `wanted`: 1 .. the number of 128-byte K tiles (wanted < 1 counts as 1)
+inline int mx_wgrad_splits(int64_t K, int64_t wanted) {
+  const char* e = "mx_wgrad_splits";
+  if (K < kMxBlock || K % kMxBlock != 0 || K > kFp8MaxDim)
+    fp8_fail(e, "K must be a positive multiple of 32 below 2^31 - 256");
+  const int64_t k_tiles = (K + kFp8TileK - 1) / kFp8TileK;
+  return static_cast<int>(wanted < 1 ? 1 : (wanted < k_tiles ? wanted : k_tiles));
+}
+
+// ws fp32 [splits][M][N] (dense) from A fp8 [M][K] (lda bytes, scales sa [M][ldsa]) and B fp8 [N][K] (ldb,
+// sb [N][ldsb]); `splits` must be mx_wgrad_splits(K, .) of itself: the caller sized ws from it
+inline MxWgradGeometry mx_wgrad_check(const void* a, const void* b, const void* ws, const void* sa, const void* sb,
+                                      int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldsa,
+                                      int64_t ldsb, int fa, int fb, int64_t splits) {
+  const char* e = "mx_wgrad";
+  fp8_format_check(e, fa);
+  fp8_format_check(e, fb);
+  if (fb != kFp8E4M3) fp8_fail(e, "the B operand is e4m3 (e4m3 x e4m3 and e5m2 x e4m3 are built)");
+  if (M < 1 || M > kFp8MaxDim) fp8_fail(e, "M must lie in 1 .. 2^31 - 256");
+  if (N < 8 || N % 8 != 0 || N > kFp8MaxDim) fp8_fail(e, "N must be a positive multiple of 8 below 2^31 - 256");
+  if (K < kMxBlock || K % kMxBlock != 0 || K > kFp8MaxDim)
+    fp8_fail(e, "K must be a positive multiple of 32 below 2^31 - 256");
+  if (lda < K || lda % 16 != 0 || ldb < K || ldb % 16 != 0)
+    fp8_fail(e, "the operands' row strides must be >= K and multiples of 16 bytes");
+  if (a == nullptr || b == nullptr || ws == nullptr) fp8_fail(e, "null tensor");
+  if (!fp8_aligned16(a) || !fp8_aligned16(b) || !fp8_aligned16(ws))
+    fp8_fail(e, "every tensor must be 16-byte aligned");
+  mx_scale_check(e, sa, ldsa, K, "A's scale image");
+  mx_scale_check(e, sb, ldsb, K, "B's scale image");
+  if (splits < 1 || splits != mx_wgrad_splits(K, splits))
+    fp8_fail(e, "the split count must be mx_wgrad_splits(K, wanted): 1 .. the number of 128-byte K tiles");
+  MxWgradGeometry g{};
+  g.m_tiles = (M + kMxWgTile - 1) / kMxWgTile;
+  g.n_tiles = (N + kMxWgTile - 1) / kMxWgTile;
+  g.tiles = g.m_tiles * g.n_tiles;
+  g.grid = g.tiles * splits;
+  if (g.tiles > 0x7fffffffLL || g.grid > 0x7fffffffLL) fp8_fail(e, "too many workgroups for one launch");
+  g.k_tiles = static_cast<int>((K + kFp8TileK - 1) / kFp8TileK);
+  g.splits = static_cast<int>(splits);
   return g;
 }
 

@@ -104,7 +104,8 @@ def submodule(name: str, what: str):
 
 
 def mx():
-    """The ``_C_mx`` module (``mx_quantize``, ``mx_gemm``; ``csrc/kernels/mx_quant.hip``, ``mx_gemm.hip``)."""
+    """The ``_C_mx`` module (``mx_quantize``, ``mx_gemm``, ``mx_wgrad``; ``csrc/kernels/mx_quant.hip``, ``mx_gemm.hip``,
+    ``mx_wgrad.hip``)."""
     return submodule("_C_mx", "the MX fp8 entries")
 
 

@@ -24,6 +24,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _ext
+from . import graddst
 from .linear import linear, wgrad_bgrad
 from .multi_tensor import DTYPE_CODE
 
@@ -194,16 +195,22 @@ def supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
 class Fp8State:
     """What an fp8 Linear keeps between calls: the scaling mode, under ``"delayed"`` the three scale blocks
     (``blocks [3, 8]`` int32: x, W, dy; made on first use, scale 1); ``"mx"`` (block scaling, the MX section
-    below) keeps nothing and uses no scale block. ``W``'s images are NOT kept from one forward
+    below) keeps nothing and uses no scale block, and ``wgrad="mx"`` runs its weight gradient in fp8 as well
+    (:func:`mx_wgrad`; the default ``"bf16"`` is the bf16 kernels). ``W``'s images are NOT kept from one forward
     to the next: the fused optimisers write the parameters through raw pointers and leave ``weight._version``
     alone, so nothing the module can see says that a cached image is still the weight's. A forward casts ``W``
     (two small launches beside the activation's) and hands the images to its own backward."""
 
-    def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None):
+    def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None, wgrad: str = "bf16"):
         if scaling not in ("current", "delayed", "mx"):
             raise ValueError(f"fp8_linear: scaling must be 'current', 'delayed' or 'mx', got {scaling!r}")
+        if wgrad not in ("bf16", "mx"):
+            raise ValueError(f"fp8_linear: wgrad must be 'bf16' or 'mx', got {wgrad!r}")
+        if wgrad == "mx" and scaling != "mx":
+            raise ValueError(f"fp8_linear: wgrad='mx' needs scaling='mx', got scaling={scaling!r}")
         self.scaling = scaling
         self.blocks = blocks
+        self.wgrad = wgrad  # "mx": the weight gradient in block-scaled fp8 too (mx_wgrad.hip), T % 32 == 0
 
     def block(self, i: int, device):
         if self.scaling == "current":
@@ -252,7 +259,9 @@ def fp8_linear(x, weight, bias=None, state: Fp8State | None = None) -> torch.Ten
     current scaling. Unsupported input (:func:`supported`) takes ``ops.linear.linear``."""
     state = state if state is not None else Fp8State()
     if state.scaling == "mx":
-        return _MxLinearFn.apply(x, weight, bias) if mx_supported(x, weight) else linear(x, weight, bias)
+        if not mx_supported(x, weight):
+            return linear(x, weight, bias)
+        return _MxLinearFn.apply(x, weight, bias, state.wgrad == "mx" and (x.numel() // weight.shape[1]) % MX_BLOCK == 0)
     if not supported(x, weight):
         return linear(x, weight, bias)
     return _Fp8LinearFn.apply(x, weight, bias, state)
@@ -261,11 +270,13 @@ def fp8_linear(x, weight, bias=None, state: Fp8State | None = None) -> torch.Ten
 class Fp8Linear(torch.nn.Linear):
     """Drop-in for ``ops.linear.Linear``: same parameters and ``state_dict()``; the weight stays bf16 and the
     fp8 images are per-step scratch. ``scaling="delayed"`` keeps its three scale blocks in a non-persistent
-    buffer; ``scaling="mx"`` is block scaling (``mx_quant.hip``, ``mx_gemm.hip``) where :func:`mx_supported`."""
+    buffer; ``scaling="mx"`` is block scaling (``mx_quant.hip``, ``mx_gemm.hip``) where :func:`mx_supported`, and
+    with ``wgrad="mx"`` the weight gradient runs in fp8 too (``mx_wgrad.hip``) where the token count is a multiple
+    of 32."""
 
-    def __init__(self, in_features, out_features, bias=True, scaling="current", **kw):
+    def __init__(self, in_features, out_features, bias=True, scaling="current", wgrad="bf16", **kw):
         super().__init__(in_features, out_features, bias=bias, **kw)
-        self.fp8 = Fp8State(scaling)
+        self.fp8 = Fp8State(scaling, wgrad=wgrad)
         self.register_buffer("fp8_blocks", torch.stack([new_block("cpu") for _ in range(3)]), persistent=False)
 
     def forward(self, x):
@@ -440,32 +451,100 @@ def mx_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
     return supported(x, weight) and weight.shape[0] % MX_BLOCK == 0 and weight.shape[1] % MX_BLOCK == 0
 
 
+def mx_wgrad_splits(m: int, n: int, k: int, cus: int) -> int:
+    """The default split count, ``wgrad256``'s rule: one round of resident workgroups, floor and not ceil (a second,
+    partial round costs a whole one), at most one split per 128-byte K tile."""
+    C = _ext.mx()
+    tile = C.MX_WGRAD_TILE
+    tiles = -(-m // tile) * (-(-n // tile))
+    return max(1, min(cus * C.MX_WGRAD_PER_CU // tiles, -(-k // 128)))
+
+
+def mx_wgrad(a_t: MxTensor, b_t: MxTensor, out_dtype: torch.dtype = torch.float32,
+             splits: int | None = None) -> torch.Tensor:
+    """``[M, N]``: the sum over K blocks of the dequantised ``a_t [M, K]`` (e4m3 or e5m2) times ``b_t [N, K]`` (e4m3)
+    blocks, i.e. a Linear's ``dW`` from the transposed images of ``dy`` and ``x`` (``K`` = tokens). ``mx_wgrad.hip``
+    writes fp32 partials of ``splits`` token ranges (default :func:`mx_wgrad_splits`; the kernel clamps it to the
+    number of K tiles) and ``gemm_splitk_reduce`` sums them in order into ``graddst.empty``: under
+    ``graddst.into(weight)`` the gradient lands in the bucket slice; bit-identical run to run."""
+    m, k = a_t.q.shape
+    n = b_t.q.shape[0]
+    if (a_t.fmt, b_t.fmt) not in ((E4M3, E4M3), (E5M2, E4M3)):
+        raise ValueError("fp8.mx_wgrad: the operands are e4m3 x e4m3 or e5m2 x e4m3")
+    if not a_t.q.is_cuda or b_t.q.shape[1] != k or k % MX_BLOCK or n % 8:
+        raise ValueError(f"fp8.mx_wgrad: a_t [M, K] and b_t [N, K] on the GPU need K % 32 == 0 and N % 8 == 0, got "
+                         f"{tuple(a_t.q.shape)} and {tuple(b_t.q.shape)}")
+    for t, rows in ((a_t, m), (b_t, n)):
+        if t.scales.dtype != torch.uint8 or t.scales.shape[0] != rows or t.scales.shape[1] < mx_scale_cols(k):
+            raise ValueError(f"fp8.mx_wgrad: a scale image must be uint8 [{rows}, >= {mx_scale_cols(k)}]")
+    C, dev = _ext.mx(), a_t.q.device
+    if splits is None:
+        splits = mx_wgrad_splits(m, n, k, torch.cuda.get_device_properties(dev).multi_processor_count)
+    s = C.mx_wgrad_splits(k, splits)
+    ws = torch.empty(s, m, n, device=dev, dtype=torch.float32)
+    stream = _stream(a_t.q)
+    C.mx_wgrad(a_t.q.data_ptr(), b_t.q.data_ptr(), ws.data_ptr(), a_t.scales.data_ptr(), b_t.scales.data_ptr(), m, n, k,
+               a_t.q.stride(0), b_t.q.stride(0), a_t.scales.stride(0), b_t.scales.stride(0), FMT_CODE[a_t.fmt],
+               FMT_CODE[b_t.fmt], s, stream)
+    odt = out_dtype if out_dtype in (torch.float32, torch.bfloat16) else torch.float32
+    dw = graddst.empty((m, n), odt, dev)
+    _ext.get(required=True).gemm_splitk_reduce(ws.data_ptr(), s, dw.numel(), dw.data_ptr(), DTYPE_CODE[odt], stream)
+    return dw.to(out_dtype)
+
+
+def mx_wgrad_reference(dy, x, fmt: str = E4M3):
+    """``(dW, |dW|)`` in float64 on the CPU of the same quantisation: ``dy.t()`` (``fmt``) and ``x.t()`` (e4m3) blocked
+    along the tokens, dequantised, then multiplied; the second is the product of absolute values."""
+    dyd = mx_dequantize(*mx_quantize_reference(dy.detach().reshape(-1, dy.shape[-1]).t().contiguous(), fmt))
+    xd = mx_dequantize(*mx_quantize_reference(x.detach().reshape(-1, x.shape[-1]).t().contiguous(), E4M3))
+    return dyd @ xd.t(), dyd.abs() @ xd.abs().t()
+
+
 class _MxLinearFn(torch.autograd.Function):
     """x, W and dy all in e4m3 (the OCP / Transformer Engine recipe: with a scale per 32 values e5m2's range is
-    not needed); W's two images come from one launch in every forward (:class:`Fp8State` says why)."""
+    not needed); W's two images come from one launch in every forward (:class:`Fp8State` says why). ``fp8_wgrad``
+    (``wgrad="mx"`` and a token count that is a multiple of 32): x and dy are cast with their token-blocked images in
+    the same launches, the backward keeps x's instead of the bf16 x, and dW is :func:`mx_wgrad` of the two."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, fp8_wgrad=False):
         n_out, n_in = weight.shape
         wq = mx_quantize(weight.detach(), E4M3, transpose=True)
-        xq = mx_quantize(x.view(-1, n_in), E4M3)
-        ctx.save_for_backward(x, weight)
-        ctx.wq, ctx.bias = wq, bias
+        xq = mx_quantize(x.view(-1, n_in), E4M3, transpose=fp8_wgrad)
+        if fp8_wgrad:
+            ctx.save_for_backward(weight, xq.q_t, xq.scales_t)
+        else:
+            ctx.save_for_backward(x, weight)
+        ctx.wq, ctx.bias, ctx.fp8_wgrad, ctx.x_shape = wq, bias, fp8_wgrad, x.shape
         return mx_gemm(xq, wq, bias).view(*x.shape[:-1], n_out)
 
     @staticmethod
     def backward(ctx, dy):
-        x, w = ctx.saved_tensors
+        w = ctx.saved_tensors[0] if ctx.fp8_wgrad else ctx.saved_tensors[1]
         n_out, n_in = w.shape
         dy2 = dy.reshape(-1, n_out)
         if dy2.dtype != torch.bfloat16 or not dy2.is_contiguous() or dy2.data_ptr() % 16:
             dy2 = dy2.to(torch.bfloat16).contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = mx_gemm(mx_quantize(dy2, E4M3), ctx.wq.t()).view(x.shape)
         need_b = ctx.bias is not None and ctx.needs_input_grad[2]
-        dw, db = wgrad_bgrad(x.reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
-        return dx, dw, db
+        dx = None
+        if not ctx.fp8_wgrad:
+            if ctx.needs_input_grad[0]:
+                dx = mx_gemm(mx_quantize(dy2, E4M3), ctx.wq.t()).view(ctx.x_shape)
+            dw, db = wgrad_bgrad(ctx.saved_tensors[0].reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
+            return dx, dw, db, None
+        # one cast of dy: the row-wise image feeds dx, the token-blocked one dW
+        dyq = mx_quantize(dy2, E4M3, transpose=ctx.needs_input_grad[1])
+        if ctx.needs_input_grad[0]:
+            dx = mx_gemm(dyq, ctx.wq.t()).view(ctx.x_shape)
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            _, xq_t, xs_t = ctx.saved_tensors
+            with graddst.into(w):
+                dw = mx_wgrad(dyq.t(), MxTensor(xq_t, xs_t, None, None, E4M3), w.dtype)
+        # db as the default path takes it (bias_grad where ops.linear.native_ok): the bf16 x is gone, and dy2 has
+        # its rows and layout, which is all that wgrad_bgrad asks of it when no dW is wanted
+        _, db = wgrad_bgrad(dy2, w, ctx.bias, dy2, False, need_b)
+        return dx, dw, db, None
 
 
 def mx_linear_reference(x, w, b, dy):
@@ -483,4 +562,4 @@ __all__ = ["E4M3", "E5M2", "FMAX", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_li
            "quantize", "quantize_into", "quantize_reference", "pow2_scale", "scale_update", "new_block", "gemm",
            "gemm_into", "supported", "layout_ok", "MX_BLOCK", "MxTensor", "mx_quantize", "mx_quantize_into",
            "mx_quantize_reference", "mx_dequantize", "mx_scale_image", "mx_gemm", "mx_gemm_into", "mx_supported",
-           "mx_linear_reference"]
+           "mx_linear_reference", "mx_wgrad", "mx_wgrad_splits", "mx_wgrad_reference"]

@@ -14,12 +14,23 @@ Variants, alternated in one process, each a HIP-graph replay:
 One JSON line per variant with the median of the rounds and min-max; fp8 lines carry ``bf16_over_fp8`` and the
 GEMM lines the achieved PFLOP/s (2 M N K over the median).
 
+``--wgrad`` measures the MX weight gradient (``mx_wgrad.hip``) instead, at qkv's shape, the same way:
+
+  mx_wgrad_s{n}                        ``fp8.mx_wgrad`` (kernel + reduce) at the default split count, half and double it
+  wgrad_bf16                           ``ops.linear.weight_grad`` (wgrad256.hip + reduce) on the bf16 operands
+  quant_x_mx_t, quant_dy_mx_t          the two casts with their token-blocked images (one launch each)
+  qkv_fwdbwd_{bf16,fp8_mx,fp8_mx_wgrad} ``Linear`` / ``Fp8Linear(scaling="mx")`` with ``wgrad="bf16"`` and ``"mx"``
+  vit_b16_step_{bf16,mx,mx_wgrad}      ``bench.py --model vit_b16 --force-comm`` as child processes with ``FLUXMPI_FP8``
+                                       unset / ``mx`` / ``mx+wgrad``, alternated: img/s and ``pack_copies_per_step``
+
 usage: python scripts/bench_fp8.py [--out profiles/fp8_vit_b16.jsonl] [--rounds 7] [--iters 20] [--tokens 50432]
+       python scripts/bench_fp8.py --wgrad [--out profiles/mx_wgrad_vit_b16.jsonl] [--vit-steps 20] [--vit-rounds 2]
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 
 import torch
@@ -32,9 +43,106 @@ from scripts.bench_patch_embed import graphed, timed  # noqa: E402
 LAYERS = {"qkv": (768, 2304), "proj": (768, 768), "fc1": (768, 3072), "fc2": (3072, 768)}  # name -> (n_in, n_out)
 
 
+def measure(fns, a):
+    """Median and min-max of ``a.rounds`` rounds of ``a.iters`` replays, the variants alternated."""
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k, fn in fns.items():
+            us[k].append(timed(fn, a.iters))
+    return us
+
+
+def vit_steps(a):
+    """``bench.py --model vit_b16`` per ``FLUXMPI_FP8`` value in child processes, alternated ``a.vit_rounds`` times."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {"bf16": [], "mx": [], "mx_wgrad": []}
+    for _ in range(a.vit_rounds):
+        for key in runs:
+            env = dict(os.environ)
+            env.pop("FLUXMPI_FP8", None)
+            if key != "bf16":
+                env["FLUXMPI_FP8"] = key.replace("_", "+")
+            r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "vit_b16", "--gpus", "1", "--steps",
+                                str(a.vit_steps), "--warmup", "5", "--force-comm"], env=env, capture_output=True, text=True,
+                               timeout=600)
+            if r.returncode != 0:
+                raise RuntimeError(f"bench.py failed for {key}:\n{r.stderr[-2000:]}")
+            runs[key].append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    return runs
+
+
+def main_wgrad(a):
+    M = a.tokens
+    n_in, n_out = LAYERS["qkv"]
+    torch.manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device="cuda").bfloat16()
+    x, dy = rnd(M, n_in).requires_grad_(), rnd(M, n_out)
+    xd = x.detach()
+    xm, dym = fp8.mx_quantize(xd, fp8.E4M3, transpose=True), fp8.mx_quantize(dy, fp8.E4M3, transpose=True)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    s0 = fp8.mx_wgrad_splits(n_out, n_in, M, cus)
+    fns, keep, flops = {}, [xm, dym], {}
+    with torch.no_grad():
+        for sp in sorted({max(1, s0 // 2), s0, 2 * s0}):
+            fns[f"mx_wgrad_s{sp}"], out = graphed(lambda sp=sp: fp8.mx_wgrad(dym.t(), xm.t(), torch.bfloat16, splits=sp))
+            keep.append(out)
+        fns["wgrad_bf16"], out = graphed(lambda: L.weight_grad(dy, xd, torch.bfloat16))
+        keep.append(out)
+        for key, t in (("quant_x_mx_t", xd), ("quant_dy_mx_t", dy)):
+            fns[key], out = graphed(lambda t=t: fp8.mx_quantize(t, fp8.E4M3, transpose=True))
+            keep.append(out)
+    for k in fns:
+        if "wgrad" in k:
+            flops[k] = 2.0 * M * n_in * n_out
+    for key, lin in (("bf16", L.Linear(n_in, n_out)), ("fp8_mx", fp8.Fp8Linear(n_in, n_out, scaling="mx")),
+                     ("fp8_mx_wgrad", fp8.Fp8Linear(n_in, n_out, scaling="mx", wgrad="mx"))):
+        lin = lin.cuda().bfloat16()
+
+        def fwdbwd(lin=lin):
+            lin.weight.grad = lin.bias.grad = x.grad = None
+            lin(x).backward(dy)
+            return x.grad, lin.weight.grad, lin.bias.grad
+
+        fns[f"qkv_fwdbwd_{key}"], out = graphed(fwdbwd)
+        keep += [lin, fwdbwd, out]
+    us = measure(fns, a)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        def emit(r):
+            line = json.dumps(r)
+            print(line, flush=True)
+            f.write(line + "\n")
+
+        for k, v in us.items():
+            r = {"variant": k, "us": round(med[k], 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1),
+                 "rounds": a.rounds, "iters": a.iters, "mode": "graph", "tokens": M}
+            if k in flops:
+                r["pflops"] = round(flops[k] / med[k] * 1e-9, 3)
+            if k.startswith("mx_wgrad_s"):
+                r["splits"], r["default_splits"], r["bf16_over_fp8"] = int(k[10:]), s0, round(med["wgrad_bf16"] / med[k], 2)
+            if k.startswith("qkv_fwdbwd_fp8"):
+                r["bf16_over_fp8"] = round(med["qkv_fwdbwd_bf16"] / med[k], 2)
+            emit(r)
+        del fns, keep
+        torch.cuda.empty_cache()
+        if a.vit_rounds > 0:
+            for key, rs in vit_steps(a).items():
+                emit({"variant": f"vit_b16_step_{key}", "value": [r.get("value") for r in rs], "unit": rs[0].get("unit"),
+                      "pack_copies_per_step": [r.get("config", {}).get("pack_copies_per_step") for r in rs], "steps": a.vit_steps})
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "fp8_vit_b16.jsonl"))
+    ap.add_argument("--wgrad", action="store_true", help="the MX weight-gradient rows (module docstring)")
+    ap.add_argument("--vit-steps", type=int, default=20)
+    ap.add_argument("--vit-rounds", type=int, default=2)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--tokens", type=int, default=50432)
@@ -42,6 +150,9 @@ def main():
     if not torch.cuda.is_available():
         print("bench_fp8.py needs a GPU", file=sys.stderr)
         return 2
+    a.out = a.out or os.path.join("profiles", "mx_wgrad_vit_b16.jsonl" if a.wgrad else "fp8_vit_b16.jsonl")
+    if a.wgrad:
+        return main_wgrad(a)
     M = a.tokens
     torch.manual_seed(0)
     fns, flops, keep = {}, {}, []

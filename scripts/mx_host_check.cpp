@@ -8,8 +8,11 @@
 // sizes that fit and the first that do not, and every rejected argument, and verifies the geometry: the quantise
 // grid covers every 128 x 128 tile once, every 16-byte access of a lane (input, both images) and every scale dword
 // (both scale images; the GEMM's loader) lies inside its row, no two tiles share a scale dword, and the GEMM's
-// scale scatter fills each operand's area exactly once with the dword order its reader expects. Exit status 0
-// and "ok" when all hold.
+// scale scatter fills each operand's area exactly once with the dword order its reader expects. For the weight
+// gradient (mx_wgrad_check, mx_wgrad_splits): the shapes and split counts of tests/test_mx_wgrad_gpu.py and the
+// ViT-B/16 ones, wanted counts of 0, 1 and above the tile count, the split ranges (contiguous, none empty, within one
+// tile of each other) and the kernel's LDS row and scale-area maps over 256 rows. Exit status 0 and "ok" when all
+// hold.
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -101,6 +104,66 @@ static void walk_scale_area() {
   for (int v : seen) EXPECT(v == 1);
 }
 
+// mx_wgrad.hip: the tiles cover M x N once, the splits partition the K tiles (contiguous, none empty, sizes within
+// one of each other), every operand chunk and scale dword a workgroup reads and every 8-column store lies inside
+static void walk_wgrad(int64_t M, int64_t N, int64_t K, int64_t wanted) {
+  const int splits = mx_wgrad_splits(K, wanted);
+  const int64_t k_tiles = (K + kFp8TileK - 1) / kFp8TileK, lds = mx_scale_row(K);
+  EXPECT(splits >= 1 && splits <= k_tiles && (wanted < 1 || splits <= wanted));
+  EXPECT(splits == wanted || wanted < 1 || wanted > k_tiles);
+  EXPECT(mx_wgrad_splits(K, splits) == splits);
+  for (int fa : {kFp8E4M3, kFp8E5M2}) {
+    const MxWgradGeometry g = mx_wgrad_check(X, Q, QT, S, ST, M, N, K, K, (K + 15) / 16 * 16, lds, lds + 4, fa, kFp8E4M3, splits);
+    EXPECT(g.m_tiles * kMxWgTile >= M && (g.m_tiles - 1) * kMxWgTile < M);
+    EXPECT(g.n_tiles * kMxWgTile >= N && (g.n_tiles - 1) * kMxWgTile < N);
+    EXPECT(g.tiles == g.m_tiles * g.n_tiles && g.grid == g.tiles * splits && g.splits == splits && g.k_tiles == k_tiles);
+    EXPECT(mx_wgrad_first_tile(g.k_tiles, splits, 0) == 0 && mx_wgrad_first_tile(g.k_tiles, splits, splits) == g.k_tiles);
+    int lo = g.k_tiles, hi = 0;
+    for (int s = 0; s < splits; ++s) {
+      const int n = mx_wgrad_first_tile(g.k_tiles, splits, s + 1) - mx_wgrad_first_tile(g.k_tiles, splits, s);
+      lo = n < lo ? n : lo, hi = n > hi ? n : hi;
+    }
+    EXPECT(lo >= 1 && hi - lo <= 1);
+    EXPECT(4 * static_cast<int64_t>(g.k_tiles) <= lds);  // the last K tile's scale dword
+    for (int kc = 0; kc < 8; ++kc) {
+      const int64_t k = static_cast<int64_t>(g.k_tiles - 1) * kFp8TileK + kc * 16;
+      if (k < K) EXPECT(k + 16 <= K);
+    }
+    for (int n8 = 0; n8 < kMxWgTile; n8 += 8) {
+      const int64_t n = (g.n_tiles - 1) * kMxWgTile + n8;
+      if (n < N) EXPECT(n + 8 <= N);
+    }
+  }
+}
+
+// mx_wgrad.hip's LDS rows: wave w's DMA piece j holds rows 32 w + 8 j .. + 7, and B's row of LDS row rho0 + 8 j is
+// b_row(rho0) + 16 (j & 1) + 4 (j >> 1); b_row is a permutation of each 64-row group. Its scale area is
+// walk_scale_area's over 256 rows: wave row wm reads groups 2 wm and 2 wm + 1, wave column wn group wn
+static void walk_wgrad_lds() {
+  const auto b_row = [](int rho) {
+    return (rho & 192) + 32 * ((rho >> 5) & 1) + 8 * ((rho >> 2) & 3) + 4 * ((rho >> 4) & 1) + (rho & 3);
+  };
+  std::vector<int> rows(kMxWgTile, 0), brows(kMxWgTile, 0), seen(kMxWgTile * 4, 0);
+  for (int w = 0; w < kMxWgThreads / 64; ++w)
+    for (int j = 0; j < 4; ++j)
+      for (int r = 0; r < 8; ++r) {
+        const int rho = 32 * w + 8 * j + r;
+        EXPECT(rho < kMxWgTile && b_row(rho) == b_row(32 * w + r) + 16 * (j & 1) + 4 * (j >> 1));
+        EXPECT((b_row(rho) & 192) == (rho & 192));
+        if (rho < kMxWgTile) ++rows[rho], ++brows[b_row(rho)];
+      }
+  for (int v : rows) EXPECT(v == 1);
+  for (int v : brows) EXPECT(v == 1);
+  for (int rho = 0; rho < kMxWgTile; ++rho)
+    for (int g = 0; g < 4; ++g) {
+      const int ofs = (((rho >> 6) * 4) * 16 + (rho & 15)) * 4 + ((rho >> 4) & 3) + g * 64;
+      EXPECT(ofs >= 0 && ofs < kMxWgTile * 4);
+      if (ofs >= 0 && ofs < kMxWgTile * 4) ++seen[ofs];
+      EXPECT(ofs == ((rho >> 6) * 64 + 16 * g + (rho & 15)) * 4 + ((rho >> 4) & 3));
+    }
+  for (int v : seen) EXPECT(v == 1);
+}
+
 template <typename F> static void rejects(const char* what, F&& f) {
   try {
     f();
@@ -130,6 +193,16 @@ int main() {
                                                           {1, kFp8MaxDim - 248, 32}, {1, 8, kFp8MaxDim - 224}})
     walk_gemm(m, n, k), ++shapes;
   walk_scale_area();
+  for (int64_t m : {1, 129, 300})
+    for (int64_t n : {8, 264})
+      for (auto [k, wanted] : std::vector<std::array<int64_t, 2>>{{32, 1}, {160, 2}, {416, 3}, {1312, 4}, {1312, 64}, {1312, 0}})
+        walk_wgrad(m, n, k, wanted), ++shapes;
+  for (auto [m, n, k, wanted] : std::vector<std::array<int64_t, 4>>{{2304, 768, 50432, 9}, {768, 768, 50432, 28},
+                                                                  {3072, 768, 50432, 7}, {768, 3072, 50432, 1},
+                                                                  {160, 96, 160, -5}, {kFp8MaxDim, 8, 32, 1},
+                                                                  {1, 8, kFp8MaxDim - 224, 1 << 30}})
+    walk_wgrad(m, n, k, wanted), ++shapes;
+  walk_wgrad_lds();
 
   const auto quant = [&](int64_t R, int64_t C, int64_t ld, const void* x = X, int fmt = 0, void* q = Q, int64_t ldq = -1,
                          void* s = S, int64_t lds = -1, void* qt = QT, int64_t ldt = -1, void* st = ST, int64_t ldst = -1) {
@@ -197,6 +270,41 @@ int main() {
   rejects("format of a", [&] { gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 2); });
   rejects("e5m2 b", [&] { gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 0, 1); });
   rejects("too many workgroups", [&] { gemm(kFp8MaxDim, kFp8MaxDim - 248, 32); });
+
+  const auto wgrad = [&](int64_t M, int64_t N, int64_t K, int64_t splits = 1, int64_t lda = -1, int64_t ldb = -1,
+                         const void* a = X, const void* b = Q, const void* ws = QT, const void* sa = S,
+                         const void* sb = ST, int64_t ldsa = -1, int64_t ldsb = -1, int fa = 0, int fb = 0) {
+    mx_wgrad_check(a, b, ws, sa, sb, M, N, K, lda < 0 ? K : lda, ldb < 0 ? K : ldb, ldsa < 0 ? mx_scale_row(K) : ldsa,
+                   ldsb < 0 ? mx_scale_row(K) : ldsb, fa, fb, splits);
+  };
+  wgrad(300, 264, 416, 3);
+  rejects("M = 0", [&] { wgrad(0, 264, 416); });
+  rejects("M too large", [&] { wgrad(kFp8MaxDim + 1, 8, 32); });
+  rejects("N = 0", [&] { wgrad(300, 0, 416); });
+  rejects("N % 8", [&] { wgrad(300, 260, 416); });
+  rejects("K = 0", [&] { wgrad(300, 264, 0); });
+  rejects("K % 32", [&] { wgrad(300, 264, 400); });
+  rejects("K too large", [&] { wgrad(1, 8, kFp8MaxDim + 224); });
+  rejects("splits = 0", [&] { wgrad(300, 264, 416, 0); });
+  rejects("splits above the K tiles", [&] { wgrad(300, 264, 416, 5); });
+  rejects("lda < K", [&] { wgrad(300, 264, 416, 1, 384); });
+  rejects("lda % 16", [&] { wgrad(300, 264, 416, 1, 424); });
+  rejects("ldb < K", [&] { wgrad(300, 264, 416, 1, 416, 384); });
+  rejects("ldb % 16", [&] { wgrad(300, 264, 416, 1, 416, 424); });
+  rejects("null a", [&] { wgrad(300, 264, 416, 1, -1, -1, nullptr); });
+  rejects("null ws", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, nullptr); });
+  rejects("unaligned b", [&] { wgrad(300, 264, 416, 1, -1, -1, X, mem + 4); });
+  rejects("unaligned ws", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, mem + 8); });
+  rejects("null scale image", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, nullptr); });
+  rejects("unaligned scale image", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, mem + 1); });
+  rejects("ldsa < 4 ceil(K / 128)", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, 12); });
+  rejects("ldsb % 4", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, 16, 18); });
+  rejects("format of a", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 2); });
+  rejects("e5m2 b", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 0, 1); });
+  rejects("too many workgroups", [&] { wgrad(kFp8MaxDim, kFp8MaxDim - 248, 32); });
+  rejects("mx_wgrad_splits: K = 0", [&] { mx_wgrad_splits(0, 1); });
+  rejects("mx_wgrad_splits: K % 32", [&] { mx_wgrad_splits(144, 2); });
+  rejects("mx_wgrad_splits: K too large", [&] { mx_wgrad_splits(kFp8MaxDim + 224, 2); });
 
   if (failures != 0) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);
