@@ -19,6 +19,7 @@
 namespace fluxmpi {
 
 constexpr int kFp8E4M3 = 0, kFp8E5M2 = 1;
+constexpr int kFp8E2M1 = 2;  // fp4 (two values per byte): the MX entries only (mx_host.h); fp8_format_check rejects it
 constexpr int kFp8BlockWords = 8;
 constexpr int kFp8Threads = 256;
 constexpr int kFp8QTile = 64;    // quantise tile: rows and columns

@@ -226,6 +226,9 @@ void mx_gemm(const void* a, const void* b, void* c, const void* bias, int bias_d
              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa,
              int fb, hipStream_t stream) {
   const Fp8GemmGeometry g = mx_gemm_check(a, b, c, bias, bias_dtype, sa, sb, M, N, K, lda, ldb, ldc, ldsa, ldsb, fa, fb);
+  if (fb == kFp8E2M1)
+    return mx4_gemm_launch(a, b, c, bias, bias_dtype == static_cast<int>(kF32), sa, sb, M, N, K, lda, ldb, ldc, ldsa, ldsb,
+                           fa, g.n_tiles, g.k_tiles, g.grid, stream);
   const MxGemmArgs p{static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(b), static_cast<bf16*>(c), bias,
                      static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb), lda, ldb, ldc, ldsa, ldsb,
                      static_cast<int>(M), static_cast<int>(N), static_cast<int>(K), static_cast<int>(g.n_tiles),

@@ -11,6 +11,12 @@
 //   quantise: a workgroup owns a kMxQTile x kMxQTile tile of x, i.e. whole scale dwords of both images; the
 //             grid is col_tiles x row_tiles with the column tiles of one row tile adjacent.
 //   GEMM:     fp8_host.h's geometry (128 x 128 of C per workgroup, K in tiles of 128 bytes).
+//   fp4:      format 2 (e2m1: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, no inf / NaN) is packed two values per byte, element
+//             2 i in the low nibble of byte i, so an image row of k values is k / 2 bytes and its strides are in
+//             bytes. The scale images are the same (a byte per 32 VALUES). Its scale is 2^floor(log2(FMAX /
+//             amax)) too, with the format's top significand 1.5; a block with an inf or NaN is all zero with the
+//             byte 255. mx_quantize and mx_gemm take it (mx4_quant.hip, mx4_gemm.hip: K in tiles of 256 values),
+//             mx_wgrad does not.
 //   wgrad:    256 x 256 of the output per workgroup, the K tiles split over workgroups (below).
 #pragma once
 #include "fp8_host.h"
@@ -28,6 +34,17 @@ struct MxQuantGeometry {
 // bytes of a scale row for a reduction length k: one dword per 128-byte K tile
 inline int64_t mx_scale_row(int64_t k) { return 4 * ((k + 127) / 128); }
 
+// the MX entries that have fp4 kernels take format 2 as well
+inline void mx_format_check(const char* entry, int fmt) {
+  if (fmt != kFp8E4M3 && fmt != kFp8E5M2 && fmt != kFp8E2M1)
+    fp8_fail(entry, "the format is 0 (e4m3), 1 (e5m2) or 2 (e2m1, packed fp4)");
+}
+
+// bytes of k values of a format
+inline int64_t mx_row_bytes(int64_t k, int fmt) { return fmt == kFp8E2M1 ? k / 2 : k; }
+
+constexpr int kMx4TileK = 256;  // mx4_gemm.hip: K VALUES per step (a 128-byte LDS row of fp4)
+
 inline void mx_scale_check(const char* e, const void* s, int64_t lds, int64_t k, const char* what) {
   if (s == nullptr) fp8_fail(e, std::string("null ") + what);
   if (reinterpret_cast<uintptr_t>(s) % 4 != 0) fp8_fail(e, std::string(what) + " must be 4-byte aligned");
@@ -37,11 +54,12 @@ inline void mx_scale_check(const char* e, const void* s, int64_t lds, int64_t k,
 
 // x bf16 [R][C] (row stride ld elements), C % 32 == 0. Row-wise image: q [R][ldq] with s [R][lds], both or
 // neither. Transposed image (blocks along R, so R % 32 == 0): qt [C][ldt] with st [C][ldst], both or neither.
+// ldq / ldt are bytes: >= C / R for fp8, >= C / 2 and R / 2 for fp4.
 inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, const void* q,
                                       int64_t ldq, const void* s, int64_t lds, const void* qt, int64_t ldt,
                                       const void* st, int64_t ldst) {
   const char* e = "mx_quantize";
-  fp8_format_check(e, fmt);
+  mx_format_check(e, fmt);
   if (R < 1 || R > kFp8MaxDim) fp8_fail(e, "R must lie in 1 .. 2^31 - 256");
   if (C < kMxBlock || C % kMxBlock != 0 || C > kFp8MaxDim)
     fp8_fail(e, "C must be a positive multiple of 32 below 2^31 - 256");
@@ -53,13 +71,15 @@ inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64
   if (q == nullptr && qt == nullptr) fp8_fail(e, "nothing to do: no output");
   if (q != nullptr) {
     if (!fp8_aligned16(q)) fp8_fail(e, "the output must be 16-byte aligned");
-    if (ldq < C || ldq % 16 != 0) fp8_fail(e, "the output's row stride must be >= C and a multiple of 16");
+    if (ldq < mx_row_bytes(C, fmt) || ldq % 16 != 0)
+      fp8_fail(e, "the output's row stride must be >= C (fp4: C / 2) bytes and a multiple of 16");
     mx_scale_check(e, s, lds, C, "the scale image");
   }
   if (qt != nullptr) {
     if (R % kMxBlock != 0) fp8_fail(e, "the transposed image needs R % 32 == 0 (its blocks run along R)");
     if (!fp8_aligned16(qt)) fp8_fail(e, "the transposed output must be 16-byte aligned");
-    if (ldt < R || ldt % 16 != 0) fp8_fail(e, "the transposed output's row stride must be >= R and a multiple of 16");
+    if (ldt < mx_row_bytes(R, fmt) || ldt % 16 != 0)
+      fp8_fail(e, "the transposed output's row stride must be >= R (fp4: R / 2) bytes and a multiple of 16");
     mx_scale_check(e, st, ldst, R, "the transposed scale image");
   }
   MxQuantGeometry g{};
@@ -71,20 +91,21 @@ inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64
 }
 
 // C bf16 [M][ldc] = A fp8 [M][K] (lda bytes, scales sa [M][ldsa]) x B fp8 [N][K] (ldb, sb [N][ldsb]); bias [N]
-// bf16 (9) or fp32 (7) or null
+// bf16 (9) or fp32 (7) or null. K counts values: an fp4 operand's row is K / 2 bytes
 inline Fp8GemmGeometry mx_gemm_check(const void* a, const void* b, const void* c, const void* bias, int bias_dtype,
                                      const void* sa, const void* sb, int64_t M, int64_t N, int64_t K, int64_t lda,
                                      int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa, int fb) {
   const char* e = "mx_gemm";
-  fp8_format_check(e, fa);
-  fp8_format_check(e, fb);
-  if (fb != kFp8E4M3) fp8_fail(e, "the B operand is e4m3 (e4m3 x e4m3 and e5m2 x e4m3 are built)");
+  mx_format_check(e, fa);
+  mx_format_check(e, fb);
+  if (!(fb == kFp8E4M3 && fa != kFp8E2M1) && !(fb == kFp8E2M1 && fa != kFp8E5M2))
+    fp8_fail(e, "A x B is e4m3 x e4m3, e5m2 x e4m3, e2m1 x e2m1 or e4m3 x e2m1 (no other pair is built)");
   if (M < 1 || M > kFp8MaxDim) fp8_fail(e, "M must lie in 1 .. 2^31 - 256");
   if (N < 8 || N % 8 != 0 || N > kFp8MaxDim) fp8_fail(e, "N must be a positive multiple of 8 below 2^31 - 256");
   if (K < kMxBlock || K % kMxBlock != 0 || K > kFp8MaxDim)
     fp8_fail(e, "K must be a positive multiple of 32 below 2^31 - 256");
-  if (lda < K || lda % 16 != 0 || ldb < K || ldb % 16 != 0)
-    fp8_fail(e, "the operands' row strides must be >= K and multiples of 16 bytes");
+  if (lda < mx_row_bytes(K, fa) || lda % 16 != 0 || ldb < mx_row_bytes(K, fb) || ldb % 16 != 0)
+    fp8_fail(e, "the operands' row strides must be >= K (fp4: K / 2) bytes and multiples of 16");
   if (ldc < N || ldc % 8 != 0) fp8_fail(e, "the output's row stride must be >= N and a multiple of 8 elements");
   if (a == nullptr || b == nullptr || c == nullptr) fp8_fail(e, "null tensor");
   if (!fp8_aligned16(a) || !fp8_aligned16(b) || !fp8_aligned16(c) || !fp8_aligned16(bias))
@@ -97,7 +118,8 @@ inline Fp8GemmGeometry mx_gemm_check(const void* a, const void* b, const void* c
   g.n_tiles = (N + kFp8Tile - 1) / kFp8Tile;
   g.grid = g.m_tiles * g.n_tiles;
   if (g.grid > 0x7fffffffLL) fp8_fail(e, "too many workgroups for one launch");
-  g.k_tiles = static_cast<int>((K + kFp8TileK - 1) / kFp8TileK);
+  const int tile_k = fb == kFp8E2M1 ? kMx4TileK : kFp8TileK;
+  g.k_tiles = static_cast<int>((K + tile_k - 1) / tile_k);
   return g;
 }
 

@@ -29,15 +29,19 @@ from .linear import linear, wgrad_bgrad
 from .multi_tensor import DTYPE_CODE
 
 E4M3, E5M2 = "e4m3", "e5m2"
-FMT_CODE = {E4M3: 0, E5M2: 1}
-FMAX = {E4M3: 448.0, E5M2: 57344.0}
+E2M1 = "e2m1"  # fp4, the MX entries only (the MX section below)
+FMT_CODE = {E4M3: 0, E5M2: 1, E2M1: 2}
+FMAX = {E4M3: 448.0, E5M2: 57344.0, E2M1: 6.0}
+TOP = {E4M3: 1.75, E5M2: 1.75, E2M1: 1.5}  # the significand of FMAX
 TORCH_DTYPE = {E4M3: torch.float8_e4m3fn, E5M2: torch.float8_e5m2}
 BLOCK_WORDS = 8
 
 
-def _fmt(fmt: str) -> str:
-    if fmt not in FMT_CODE:
-        raise ValueError(f"fp8: the format is 'e4m3' or 'e5m2', got {fmt!r}")
+def _fmt(fmt: str, mx: bool = False) -> str:
+    """The format's name checked: ``'e2m1'`` where ``mx`` (the block-scaled entries that have fp4 kernels) only."""
+    if fmt not in FMT_CODE or (fmt == E2M1 and not mx):
+        names = "'e4m3', 'e5m2' or 'e2m1'" if mx else "'e4m3' or 'e5m2'"
+        raise ValueError(f"fp8: the format is {names}, got {fmt!r}")
     return fmt
 
 
@@ -46,8 +50,9 @@ def pow2_scale(amax: float, fmt: str) -> float:
     amax = float(amax)
     if amax == 0.0 or not math.isfinite(amax):
         return 1.0
-    m, e = math.frexp(abs(amax))  # amax = (2 m) 2^(e - 1), 2 m in [1, 2); FMAX = 1.75 * 2^E
-    p = int(math.log2(FMAX[_fmt(fmt)] / 1.75)) - (e - 1) - (1 if 2 * m > 1.75 else 0)
+    m, e = math.frexp(abs(amax))  # amax = (2 m) 2^(e - 1), 2 m in [1, 2); FMAX = TOP * 2^E
+    top = TOP[_fmt(fmt, mx=True)]
+    p = int(math.log2(FMAX[fmt] / top)) - (e - 1) - (1 if 2 * m > top else 0)
     return 2.0 ** max(-126, min(126, p))
 
 
@@ -201,14 +206,21 @@ class Fp8State:
     alone, so nothing the module can see says that a cached image is still the weight's. A forward casts ``W``
     (two small launches beside the activation's) and hands the images to its own backward."""
 
-    def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None, wgrad: str = "bf16"):
+    def __init__(self, scaling: str = "current", blocks: torch.Tensor | None = None, wgrad: str = "bf16",
+                 fwd: str = E4M3):
         if scaling not in ("current", "delayed", "mx"):
             raise ValueError(f"fp8_linear: scaling must be 'current', 'delayed' or 'mx', got {scaling!r}")
         if wgrad not in ("bf16", "mx"):
             raise ValueError(f"fp8_linear: wgrad must be 'bf16' or 'mx', got {wgrad!r}")
         if wgrad == "mx" and scaling != "mx":
             raise ValueError(f"fp8_linear: wgrad='mx' needs scaling='mx', got scaling={scaling!r}")
+        if fwd not in (E4M3, E2M1) or (fwd == E2M1 and scaling != "mx"):
+            raise ValueError(f"fp8_linear: fwd is 'e4m3', or 'e2m1' with scaling='mx', got {fwd!r} with {scaling!r}")
+        if fwd == E2M1 and wgrad == "mx":
+            raise ValueError("fp8_linear: fwd='e2m1' has no fp8 weight gradient (wgrad='mx' wants an e4m3 token-blocked "
+                             "image of x, which this mode does not produce)")
         self.scaling = scaling
+        self.fwd = fwd  # "e2m1" (MX only): x and W in fp4 for the forward, dy e4m3 against W's packed transposed image
         self.blocks = blocks
         self.wgrad = wgrad  # "mx": the weight gradient in block-scaled fp8 too (mx_wgrad.hip), T % 32 == 0
 
@@ -261,7 +273,8 @@ def fp8_linear(x, weight, bias=None, state: Fp8State | None = None) -> torch.Ten
     if state.scaling == "mx":
         if not mx_supported(x, weight):
             return linear(x, weight, bias)
-        return _MxLinearFn.apply(x, weight, bias, state.wgrad == "mx" and (x.numel() // weight.shape[1]) % MX_BLOCK == 0)
+        return _MxLinearFn.apply(x, weight, bias,
+                                 state.wgrad == "mx" and (x.numel() // weight.shape[1]) % MX_BLOCK == 0, state.fwd)
     if not supported(x, weight):
         return linear(x, weight, bias)
     return _Fp8LinearFn.apply(x, weight, bias, state)
@@ -272,11 +285,12 @@ class Fp8Linear(torch.nn.Linear):
     fp8 images are per-step scratch. ``scaling="delayed"`` keeps its three scale blocks in a non-persistent
     buffer; ``scaling="mx"`` is block scaling (``mx_quant.hip``, ``mx_gemm.hip``) where :func:`mx_supported`, and
     with ``wgrad="mx"`` the weight gradient runs in fp8 too (``mx_wgrad.hip``) where the token count is a multiple
-    of 32."""
+    of 32; ``fwd="e2m1"`` (with ``scaling="mx"``) runs the forward on fp4 images of ``x`` and ``W`` and the input
+    gradient on e4m3 ``dy`` against ``W``'s fp4 transposed image (``mx4_quant.hip``, ``mx4_gemm.hip``)."""
 
-    def __init__(self, in_features, out_features, bias=True, scaling="current", wgrad="bf16", **kw):
+    def __init__(self, in_features, out_features, bias=True, scaling="current", wgrad="bf16", fwd=E4M3, **kw):
         super().__init__(in_features, out_features, bias=bias, **kw)
-        self.fp8 = Fp8State(scaling, wgrad=wgrad)
+        self.fp8 = Fp8State(scaling, wgrad=wgrad, fwd=fwd)
         self.register_buffer("fp8_blocks", torch.stack([new_block("cpu") for _ in range(3)]), persistent=False)
 
     def forward(self, x):
@@ -309,8 +323,45 @@ def fp8_linear_reference(x, w, b, dy, scales=None):
 # the GEMM that reads the image, stored as the E8M0 byte of its inverse, ``127 - log2(s)`` (1 .. 253; 127 for an
 # all-zero or non-finite block). ``csrc/kernels/mx_quant.hip`` casts in ONE launch with no amax pass, no scale
 # block and no state; ``mx_gemm.hip`` applies the scales inside ``v_mfma_scale_f32_16x16x128_f8f6f4``.
+#
+# ``'e2m1'`` (fp4: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, no inf or NaN) is packed two values per byte, element ``2 i`` in the
+# low nibble of byte ``i``: ``q`` is ``[R, C / 2]``, the scale images are the same. Its scale follows the same
+# non-saturating rule with the format's top significand 1.5 (a valid MX scale, not the OCP document's floor rule); a
+# block with an inf or NaN is zeros under the byte 255. ``mx4_quant.hip`` / ``mx4_gemm.hip``; pairs e2m1 x e2m1 and
+# e4m3 x e2m1.
 MX_BLOCK = 32
 MX_ONE = 127
+MX_NAN = 255  # E8M0's NaN: an e2m1 block that held a non-finite value
+MX4_STAGES = 2  # LDS stages of mx4_gemm.hip, each 256 values of K deep
+MX_PAIRS = ((E4M3, E4M3), (E5M2, E4M3), (E2M1, E2M1), (E4M3, E2M1))  # what mx_gemm builds, a x b
+FP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # code = sign << 3 | index
+
+
+def _cols(fmt: str, k: int) -> int:
+    """Bytes of ``k`` values of ``fmt``."""
+    return k // 2 if fmt == E2M1 else k
+
+
+def mx_pack_fp4(values: torch.Tensor) -> torch.Tensor:
+    """Grid values ``[R, C]`` (float) as packed codes uint8 ``[R, C / 2]``, element ``2 i`` in the low nibble."""
+    v = values.detach().double()
+    code = torch.bucketize(v.abs(), torch.tensor(FP4_GRID, dtype=torch.float64)) | (torch.signbit(v).long() << 3)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+
+
+def mx_unpack_fp4(q: torch.Tensor) -> torch.Tensor:
+    """Packed codes uint8 ``[R, C / 2]`` as their float32 values ``[R, C]``."""
+    code = torch.stack([q & 15, q >> 4], -1).reshape(q.shape[0], -1).long()
+    v = torch.tensor(FP4_GRID, dtype=torch.float32, device=q.device)[code & 7]
+    return torch.where((code & 8) != 0, -v, v)
+
+
+def _round_fp4(y: torch.Tensor) -> torch.Tensor:
+    """``y`` (float32, ``|y| <= 6``) to the e2m1 grid: nearest, a midpoint to the neighbour with the even code."""
+    a = y.abs()
+    mids = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False))
+    idx = sum(((a >= m) if up else (a > m)).long() for m, up in mids)
+    return torch.copysign(torch.tensor(FP4_GRID, dtype=torch.float32)[idx], y)
 
 
 def mx_scale_cols(k: int) -> int:
@@ -328,7 +379,7 @@ class MxTensor:
     scales: torch.Tensor
     q_t: torch.Tensor | None
     scales_t: torch.Tensor | None
-    fmt: str
+    fmt: str  # 'e2m1': q and q_t are packed, [R, C / 2] and [C, R / 2]
 
     def t(self) -> "MxTensor":
         """The transposed image as a GEMM operand."""
@@ -340,7 +391,9 @@ class MxTensor:
 def mx_quantize_reference(x: torch.Tensor, fmt: str):
     """``(q, bytes)`` on the CPU: ``q`` float8 ``[R, C]`` and the blocks' E8M0 bytes uint8 ``[R, C / 32]``, blocks
     along the last axis; :func:`pow2_scale` of every block's amax (vectorised with ``torch.frexp``), torch's
-    round-to-nearest-even cast, non-finite inputs kept non-finite in a block of scale 1."""
+    round-to-nearest-even cast, non-finite inputs kept non-finite in a block of scale 1. ``'e2m1'``: ``q`` is float32
+    values on the fp4 grid (:func:`mx_pack_fp4` packs them), and a block with a non-finite input is zeros under the
+    byte 255."""
     xf = x.detach().float().cpu()
     r, c = xf.shape
     if c % MX_BLOCK:
@@ -349,9 +402,14 @@ def mx_quantize_reference(x: torch.Tensor, fmt: str):
     amax = blk.abs().amax(-1)
     ok = torch.isfinite(amax) & (amax > 0)
     m, e = torch.frexp(torch.where(ok, amax, torch.ones_like(amax)))  # amax = (2 m) 2^(e - 1), 2 m in [1, 2)
-    p = int(math.log2(FMAX[_fmt(fmt)] / 1.75)) - (e - 1) - (2 * m > 1.75).int()
+    top = TOP[_fmt(fmt, mx=True)]
+    p = int(math.log2(FMAX[fmt] / top)) - (e - 1) - (2 * m > top).int()
     p = torch.where(ok, p.clamp(-126, 126), torch.zeros_like(p))
     y = (blk * torch.ldexp(torch.ones_like(amax), p).unsqueeze(-1)).clamp(-FMAX[fmt], FMAX[fmt])
+    if fmt == E2M1:
+        bad = ~torch.isfinite(amax)
+        y = torch.where(bad.unsqueeze(-1), torch.zeros_like(y), _round_fp4(y))
+        return y.view(r, c), torch.where(bad, torch.full_like(p, MX_NAN), MX_ONE - p).to(torch.uint8)
     return torch.where(torch.isfinite(blk), y, blk).view(r, c).to(TORCH_DTYPE[fmt]), (MX_ONE - p).to(torch.uint8)
 
 
@@ -386,25 +444,27 @@ def mx_quantize_into(x, fmt, q=None, scales=None, q_t=None, scales_t=None) -> No
     r, c = x.shape
     if q_t is not None and r % MX_BLOCK:
         raise ValueError(f"fp8.mx_quantize: the transposed image needs R % {MX_BLOCK} == 0, got R = {r}")
-    for o, shape in ((q, (r, c)), (scales, (r, mx_scale_cols(c))), (q_t, (c, r)), (scales_t, (c, mx_scale_cols(r)))):
+    _fmt(fmt, mx=True)
+    for o, shape in ((q, (r, _cols(fmt, c))), (scales, (r, mx_scale_cols(c))), (q_t, (c, _cols(fmt, r))),
+                     (scales_t, (c, mx_scale_cols(r)))):
         if o is not None and (o.dtype != torch.uint8 or tuple(o.shape) != shape or o.stride(1) != 1):
             raise ValueError(f"fp8.mx_quantize: an output must be a uint8 view of shape {shape}")
     if (q is None) != (scales is None) or (q_t is None) != (scales_t is None) or (q is None and q_t is None):
         raise ValueError("fp8.mx_quantize: an image and its scales come together, and one pair is needed")
     arg = lambda o: (o.data_ptr(), o.stride(0)) if o is not None else (0, 0)
-    _ext.mx().mx_quantize(x.data_ptr(), r, c, x.stride(0), FMT_CODE[_fmt(fmt)], *arg(q), *arg(scales), *arg(q_t),
+    _ext.mx().mx_quantize(x.data_ptr(), r, c, x.stride(0), FMT_CODE[fmt], *arg(q), *arg(scales), *arg(q_t),
                           *arg(scales_t), _stream(x))
 
 
 def mx_quantize(x: torch.Tensor, fmt: str, transpose: bool = False) -> MxTensor:
     """The MX image of the bf16 matrix ``x`` in one launch; ``transpose``: the image blocked along ``R`` too."""
-    _fmt(fmt)
+    _fmt(fmt, mx=True)
     if not x.is_cuda or x.dim() != 2:
         raise ValueError("fp8.mx_quantize: the input is a bf16 matrix on the GPU (CPU tensors take "
                          "mx_quantize_reference)")
     r, c = x.shape
     new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=x.device)
-    t = MxTensor(new(r, c), new(r, mx_scale_cols(c)), new(c, r) if transpose else None,
+    t = MxTensor(new(r, _cols(fmt, c)), new(r, mx_scale_cols(c)), new(c, _cols(fmt, r)) if transpose else None,
                  new(c, mx_scale_cols(r)) if transpose else None, fmt)
     mx_quantize_into(x, fmt, t.q, t.scales, t.q_t, t.scales_t)
     return t
@@ -412,13 +472,13 @@ def mx_quantize(x: torch.Tensor, fmt: str, transpose: bool = False) -> MxTensor:
 
 def mx_gemm_into(out: torch.Tensor, a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
     """:func:`mx_gemm` into the bf16 view ``out [M, N]`` (any row stride that is a multiple of 8)."""
-    m, k = a.q.shape
-    n = b.q.shape[0]
-    if (a.fmt, b.fmt) not in ((E4M3, E4M3), (E5M2, E4M3)):
-        raise ValueError("fp8.mx_gemm: the operands are e4m3 x e4m3 or e5m2 x e4m3")
-    if not a.q.is_cuda or b.q.shape[1] != k or k % MX_BLOCK or n % 8:
-        raise ValueError(f"fp8.mx_gemm: a [M, K] and b [N, K] on the GPU need K % 32 == 0 and N % 8 == 0, got "
-                         f"{tuple(a.q.shape)} and {tuple(b.q.shape)}")
+    if (a.fmt, b.fmt) not in MX_PAIRS:
+        raise ValueError("fp8.mx_gemm: the operands are e4m3 x e4m3, e5m2 x e4m3, e2m1 x e2m1 or e4m3 x e2m1")
+    m, n = a.q.shape[0], b.q.shape[0]
+    k = a.q.shape[1] * (2 if a.fmt == E2M1 else 1)  # values: an e2m1 image is packed
+    if not a.q.is_cuda or b.q.shape[1] != _cols(b.fmt, k) or k % MX_BLOCK or n % 8:
+        raise ValueError(f"fp8.mx_gemm: a [M, K] and b [N, K] on the GPU need K % 32 == 0 and N % 8 == 0 (an e2m1 image "
+                         f"has K / 2 columns), got {tuple(a.q.shape)} and {tuple(b.q.shape)}")
     for t, rows in ((a, m), (b, n)):
         if t.scales.dtype != torch.uint8 or t.scales.shape[0] != rows or t.scales.shape[1] < mx_scale_cols(k):
             raise ValueError(f"fp8.mx_gemm: a scale image must be uint8 [{rows}, >= {mx_scale_cols(k)}]")
@@ -440,8 +500,9 @@ def mx_gemm_into(out: torch.Tensor, a: MxTensor, b: MxTensor, bias: torch.Tensor
 
 
 def mx_gemm(a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
-    """``bf16(sum over K blocks of the dequantised a_blk . b_blk + bias)``: ``a [M, K]`` e4m3 or e5m2, ``b [N, K]``
-    e4m3, the block scales applied inside the MFMA, fp32 accumulation."""
+    """``bf16(sum over K blocks of the dequantised a_blk . b_blk + bias)``: ``a [M, K]`` e4m3 or e5m2 with ``b [N, K]``
+    e4m3, or ``a`` e2m1 or e4m3 with ``b`` e2m1 (``mx4_gemm.hip``); the block scales applied inside the MFMA, fp32
+    accumulation."""
     out = torch.empty(a.q.shape[0], b.q.shape[0], dtype=torch.bfloat16, device=a.q.device)
     return mx_gemm_into(out, a, b, bias)
 
@@ -504,13 +565,14 @@ class _MxLinearFn(torch.autograd.Function):
     """x, W and dy all in e4m3 (the OCP / Transformer Engine recipe: with a scale per 32 values e5m2's range is
     not needed); W's two images come from one launch in every forward (:class:`Fp8State` says why). ``fp8_wgrad``
     (``wgrad="mx"`` and a token count that is a multiple of 32): x and dy are cast with their token-blocked images in
-    the same launches, the backward keeps x's instead of the bf16 x, and dW is :func:`mx_wgrad` of the two."""
+    the same launches, the backward keeps x's instead of the bf16 x, and dW is :func:`mx_wgrad` of the two.
+    ``fwd="e2m1"``: x and W are cast to fp4 instead (W's transposed image packed along ``n_out``), dy stays e4m3."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, fp8_wgrad=False):
+    def forward(ctx, x, weight, bias, fp8_wgrad=False, fwd=E4M3):
         n_out, n_in = weight.shape
-        wq = mx_quantize(weight.detach(), E4M3, transpose=True)
-        xq = mx_quantize(x.view(-1, n_in), E4M3, transpose=fp8_wgrad)
+        wq = mx_quantize(weight.detach(), fwd, transpose=True)
+        xq = mx_quantize(x.view(-1, n_in), fwd, transpose=fp8_wgrad)
         if fp8_wgrad:
             ctx.save_for_backward(weight, xq.q_t, xq.scales_t)
         else:
@@ -531,7 +593,7 @@ class _MxLinearFn(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = mx_gemm(mx_quantize(dy2, E4M3), ctx.wq.t()).view(ctx.x_shape)
             dw, db = wgrad_bgrad(ctx.saved_tensors[0].reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
-            return dx, dw, db, None
+            return dx, dw, db, None, None
         # one cast of dy: the row-wise image feeds dx, the token-blocked one dW
         dyq = mx_quantize(dy2, E4M3, transpose=ctx.needs_input_grad[1])
         if ctx.needs_input_grad[0]:
@@ -544,21 +606,23 @@ class _MxLinearFn(torch.autograd.Function):
         # db as the default path takes it (bias_grad where ops.linear.native_ok): the bf16 x is gone, and dy2 has
         # its rows and layout, which is all that wgrad_bgrad asks of it when no dW is wanted
         _, db = wgrad_bgrad(dy2, w, ctx.bias, dy2, False, need_b)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def mx_linear_reference(x, w, b, dy):
+def mx_linear_reference(x, w, b, dy, fwd: str = E4M3):
     """``(y, dx, |y|, |dx|)`` in float64 on the CPU of the same quantisation, as :func:`fp8_linear_reference`: x and
-    w blocked along ``n_in`` for y, dy and w blocked along ``n_out`` for dx, all e4m3."""
+    w blocked along ``n_in`` for y, dy and w blocked along ``n_out`` for dx; x and both images of w in ``fwd``, dy in
+    e4m3."""
     n_out, n_in = w.shape
-    xd, wd, dyd, wtd = (mx_dequantize(*mx_quantize_reference(t, E4M3)) for t in
-                        (x.reshape(-1, n_in), w, dy.reshape(-1, n_out), w.detach().t().contiguous()))
+    xd, wd, dyd, wtd = (mx_dequantize(*mx_quantize_reference(t, f)) for t, f in
+                        ((x.reshape(-1, n_in), fwd), (w, fwd), (dy.reshape(-1, n_out), E4M3),
+                         (w.detach().t().contiguous(), fwd)))
     bd = b.detach().double().cpu() if b is not None else torch.zeros(n_out, dtype=torch.float64)
     y, ya = xd @ wd.t() + bd, xd.abs() @ wd.abs().t() + bd.abs()
     return y, dyd @ wtd.t(), ya, dyd.abs() @ wtd.abs().t()
 
 
-__all__ = ["E4M3", "E5M2", "FMAX", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
+__all__ = ["E4M3", "E5M2", "E2M1", "FMAX", "mx_pack_fp4", "mx_unpack_fp4", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
            "quantize", "quantize_into", "quantize_reference", "pow2_scale", "scale_update", "new_block", "gemm",
            "gemm_into", "supported", "layout_ok", "MX_BLOCK", "MxTensor", "mx_quantize", "mx_quantize_into",
            "mx_quantize_reference", "mx_dequantize", "mx_scale_image", "mx_gemm", "mx_gemm_into", "mx_supported",

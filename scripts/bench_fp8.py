@@ -23,8 +23,17 @@ GEMM lines the achieved PFLOP/s (2 M N K over the median).
   vit_b16_step_{bf16,mx,mx_wgrad}      ``bench.py --model vit_b16 --force-comm`` as child processes with ``FLUXMPI_FP8``
                                        unset / ``mx`` / ``mx+wgrad``, alternated: img/s and ``pack_copies_per_step``
 
+``--fp4`` measures the fp4 (e2m1) MX path (``mx4_quant.hip``, ``mx4_gemm.hip``) against the e4m3 MX one and bf16:
+
+  quant_{x,w}_{mx4,mx}                 the cast of x [tokens, 768] (row-wise image) and of W [2304, 768] (both images)
+  gemm_fwd_{layer}_{mx4,mx,bf16}       the forward GEMM alone: e2m1 x e2m1, e4m3 x e4m3, ``ops.linear.fwd``
+  gemm_dgrad_{layer}_{mx4,mx,bf16}     the input-gradient GEMM alone: e4m3 dy x e2m1 W^T, e4m3 x e4m3, ``ops.linear.dgrad``
+  qkv_fwdbwd_{bf16,fp8_mx,fp8_mx4}     ``Linear`` / ``Fp8Linear(scaling="mx")`` with ``fwd="e4m3"`` and ``"e2m1"``
+  vit_b16_step_{bf16,mx,mx4}           ``bench.py`` child processes as under ``--wgrad``, into ``--ab-out``
+
 usage: python scripts/bench_fp8.py [--out profiles/fp8_vit_b16.jsonl] [--rounds 7] [--iters 20] [--tokens 50432]
        python scripts/bench_fp8.py --wgrad [--out profiles/mx_wgrad_vit_b16.jsonl] [--vit-steps 20] [--vit-rounds 2]
+       python scripts/bench_fp8.py --fp4 [--out profiles/mx4_vit_b16.jsonl] [--ab-out profiles/mx4_bench_ab.jsonl]
 """
 import argparse
 import json
@@ -56,10 +65,10 @@ def measure(fns, a):
     return us
 
 
-def vit_steps(a):
+def vit_steps(a, keys=("bf16", "mx", "mx_wgrad")):
     """``bench.py --model vit_b16`` per ``FLUXMPI_FP8`` value in child processes, alternated ``a.vit_rounds`` times."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    runs = {"bf16": [], "mx": [], "mx_wgrad": []}
+    runs = {k: [] for k in keys}
     for _ in range(a.vit_rounds):
         for key in runs:
             env = dict(os.environ)
@@ -137,8 +146,77 @@ def main_wgrad(a):
     return 0
 
 
+def main_fp4(a):
+    M = a.tokens
+    torch.manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device="cuda").bfloat16()
+    fns, keep, flops = {}, [], {}
+    with torch.no_grad():
+        for name, (n_in, n_out) in LAYERS.items():
+            x, w, dy = rnd(M, n_in), rnd(n_out, n_in) * n_in ** -0.5, rnd(M, n_out)
+            dyq = fp8.mx_quantize(dy, fp8.E4M3)
+            for key, fmt in (("mx4", fp8.E2M1), ("mx", fp8.E4M3)):
+                xq, wq = fp8.mx_quantize(x, fmt), fp8.mx_quantize(w, fmt, transpose=True)
+                fns[f"gemm_fwd_{name}_{key}"], o1 = graphed(lambda xq=xq, wq=wq: fp8.mx_gemm(xq, wq))
+                fns[f"gemm_dgrad_{name}_{key}"], o2 = graphed(lambda wq=wq, dyq=dyq: fp8.mx_gemm(dyq, wq.t()))
+                keep += [xq, wq, o1, o2]
+                if name == "qkv":
+                    fns[f"quant_x_{key}"], o1 = graphed(lambda x=x, fmt=fmt: fp8.mx_quantize(x, fmt))
+                    fns[f"quant_w_{key}"], o2 = graphed(lambda w=w, fmt=fmt: fp8.mx_quantize(w, fmt, transpose=True))
+                    keep += [o1, o2]
+            fns[f"gemm_fwd_{name}_bf16"], o1 = graphed(lambda x=x, w=w: L.fwd(x, w, None))
+            fns[f"gemm_dgrad_{name}_bf16"], o2 = graphed(lambda dy=dy, w=w: L.dgrad(dy, w))
+            keep += [x, w, dy, dyq, o1, o2]
+            for k in fns:
+                if k.startswith(("gemm_fwd_" + name, "gemm_dgrad_" + name)):
+                    flops[k] = 2.0 * M * n_in * n_out
+    n_in, n_out = LAYERS["qkv"]
+    x, dy = rnd(M, n_in).requires_grad_(), rnd(M, n_out)
+    for key, lin in (("bf16", L.Linear(n_in, n_out)), ("fp8_mx", fp8.Fp8Linear(n_in, n_out, scaling="mx")),
+                     ("fp8_mx4", fp8.Fp8Linear(n_in, n_out, scaling="mx", fwd="e2m1"))):
+        lin = lin.cuda().bfloat16()
+
+        def fwdbwd(lin=lin):
+            lin.weight.grad = lin.bias.grad = x.grad = None
+            lin(x).backward(dy)
+            return x.grad, lin.weight.grad, lin.bias.grad
+
+        fns[f"qkv_fwdbwd_{key}"], out = graphed(fwdbwd)
+        keep += [lin, fwdbwd, out]
+    us = measure(fns, a)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        for k, v in us.items():
+            r = {"variant": k, "us": round(med[k], 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1),
+                 "rounds": a.rounds, "iters": a.iters, "mode": "graph", "tokens": M}
+            if k in flops:
+                r["pflops"] = round(flops[k] / med[k] * 1e-9, 3)
+            if k.endswith("_mx4"):
+                r["mx_over_mx4"] = round(med[k[:-1]] / med[k], 2)
+                other = k[:-3] + "bf16" if k.startswith("gemm") else "qkv_fwdbwd_bf16" if k.startswith("qkv") else None
+                if other:
+                    r["bf16_over_mx4"] = round(med[other] / med[k], 2)
+            line = json.dumps(r)
+            print(line, flush=True)
+            f.write(line + "\n")
+    del fns, keep
+    torch.cuda.empty_cache()
+    if a.vit_rounds > 0:
+        os.makedirs(os.path.dirname(os.path.abspath(a.ab_out)), exist_ok=True)
+        with open(a.ab_out, "w") as f:
+            for key, rs in vit_steps(a, ("bf16", "mx", "mx4")).items():
+                line = json.dumps({"variant": f"vit_b16_step_{key}", "value": [r.get("value") for r in rs],
+                                   "unit": rs[0].get("unit"), "steps": a.vit_steps})
+                print(line, flush=True)
+                f.write(line + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fp4", action="store_true", help="the fp4 (e2m1) MX rows (module docstring)")
+    ap.add_argument("--ab-out", default=os.path.join("profiles", "mx4_bench_ab.jsonl"))
     ap.add_argument("--wgrad", action="store_true", help="the MX weight-gradient rows (module docstring)")
     ap.add_argument("--vit-steps", type=int, default=20)
     ap.add_argument("--vit-rounds", type=int, default=2)
@@ -150,7 +228,10 @@ def main():
     if not torch.cuda.is_available():
         print("bench_fp8.py needs a GPU", file=sys.stderr)
         return 2
-    a.out = a.out or os.path.join("profiles", "mx_wgrad_vit_b16.jsonl" if a.wgrad else "fp8_vit_b16.jsonl")
+    a.out = a.out or os.path.join("profiles", "mx4_vit_b16.jsonl" if a.fp4 else
+                                  "mx_wgrad_vit_b16.jsonl" if a.wgrad else "fp8_vit_b16.jsonl")
+    if a.fp4:
+        return main_fp4(a)
     if a.wgrad:
         return main_wgrad(a)
     M = a.tokens
