@@ -704,6 +704,14 @@ void mx4_quantize_launch(const void* x, int64_t R, int64_t C, int64_t ld, void* 
 void mx4_gemm_launch(const void* a, const void* b, void* c, const void* bias, int bias_f32, const void* sa,
                      const void* sb, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldsa,
                      int64_t ldsb, int fa, int64_t n_tiles, int k_tiles, int64_t grid, hipStream_t stream);
+// fmt / fa / fb = 3 (e2m3) and 4 (e3m2) are packed fp6 (four values in three bytes, strides in bytes): as above,
+// mx_quantize and mx_gemm (fa x fb e2m3 x e2m3 or e3m2 x e2m3) hand over to mx6_quant.hip and mx6_gemm.hip
+void mx6_quantize_launch(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, void* q, int64_t ldq, void* s,
+                         int64_t lds, void* qt, int64_t ldt, void* st, int64_t ldst, int64_t col_tiles, int64_t grid,
+                         hipStream_t stream);
+void mx6_gemm_launch(const void* a, const void* b, void* c, const void* bias, int bias_f32, const void* sa,
+                     const void* sb, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldsa,
+                     int64_t ldsb, int fa, int64_t n_tiles, int k_tiles, int64_t grid, hipStream_t stream);
 // The weight gradient's shape (mx_wgrad.hip): ws fp32 [splits][M][N], ws[s] = the block-scaled products of a [M][K] and
 // b [N][K] (as mx_gemm's operands) over the 128-byte K tiles of split s; M = 1 .. , N % 8 == 0, K % 32 == 0. splits
 // must be mx_wgrad_splits(K, wanted) of kernels/mx_host.h (whole K tiles, no empty range), from which the caller

@@ -229,6 +229,9 @@ void mx_gemm(const void* a, const void* b, void* c, const void* bias, int bias_d
   if (fb == kFp8E2M1)
     return mx4_gemm_launch(a, b, c, bias, bias_dtype == static_cast<int>(kF32), sa, sb, M, N, K, lda, ldb, ldc, ldsa, ldsb,
                            fa, g.n_tiles, g.k_tiles, g.grid, stream);
+  if (mx_is_fp6(fb))
+    return mx6_gemm_launch(a, b, c, bias, bias_dtype == static_cast<int>(kF32), sa, sb, M, N, K, lda, ldb, ldc, ldsa, ldsb,
+                           fa, g.n_tiles, g.k_tiles, g.grid, stream);
   const MxGemmArgs p{static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(b), static_cast<bf16*>(c), bias,
                      static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb), lda, ldb, ldc, ldsa, ldsb,
                      static_cast<int>(M), static_cast<int>(N), static_cast<int>(K), static_cast<int>(g.n_tiles),

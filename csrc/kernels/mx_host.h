@@ -17,6 +17,13 @@
 //             amax)) too, with the format's top significand 1.5; a block with an inf or NaN is all zero with the
 //             byte 255. mx_quantize and mx_gemm take it (mx4_quant.hip, mx4_gemm.hip: K in tiles of 256 values),
 //             mx_wgrad does not.
+//   fp6:      formats 3 (e2m3: bias 1, subnormal step 0.125, max 7.5 = 1.875 * 2^2) and 4 (e3m2: bias 3, subnormal
+//             step 0.0625, max 28 = 1.75 * 2^4), OCP FP6 without inf / NaN, are packed four values in three bytes:
+//             value i of a 32-value block sits at bits 6 i .. 6 i + 5 of the block's 24 bytes read as one
+//             little-endian bit string, so a row of k values is 3 k / 4 bytes (a multiple of 24, not always of 16:
+//             the strides are still multiples of 16 bytes and the callers pad). Scale rule, scale images and the
+//             byte 255 of a non-finite block as fp4. mx_quantize and mx_gemm take them (mx6_quant.hip,
+//             mx6_gemm.hip: e2m3 x e2m3 and e3m2 x e2m3, K in tiles of 128 values = 96 bytes), mx_wgrad does not.
 //   wgrad:    256 x 256 of the output per workgroup, the K tiles split over workgroups (below).
 #pragma once
 #include "fp8_host.h"
@@ -34,14 +41,20 @@ struct MxQuantGeometry {
 // bytes of a scale row for a reduction length k: one dword per 128-byte K tile
 inline int64_t mx_scale_row(int64_t k) { return 4 * ((k + 127) / 128); }
 
-// the MX entries that have fp4 kernels take format 2 as well
+constexpr int kMxE2M3 = 3, kMxE3M2 = 4;  // fp6, four values in three bytes
+inline bool mx_is_fp6(int fmt) { return fmt == kMxE2M3 || fmt == kMxE3M2; }
+
+// the MX entries that have fp4 and fp6 kernels take formats 2 .. 4 as well
 inline void mx_format_check(const char* entry, int fmt) {
-  if (fmt != kFp8E4M3 && fmt != kFp8E5M2 && fmt != kFp8E2M1)
-    fp8_fail(entry, "the format is 0 (e4m3), 1 (e5m2) or 2 (e2m1, packed fp4)");
+  if (fmt != kFp8E4M3 && fmt != kFp8E5M2 && fmt != kFp8E2M1 && !mx_is_fp6(fmt))
+    fp8_fail(entry, "the format is 0 (e4m3), 1 (e5m2), 2 (e2m1, packed fp4), 3 (e2m3) or 4 (e3m2, packed fp6)");
 }
 
-// bytes of k values of a format
-inline int64_t mx_row_bytes(int64_t k, int fmt) { return fmt == kFp8E2M1 ? k / 2 : k; }
+// bytes of k values of a format (k % 32 == 0)
+inline int64_t mx_row_bytes(int64_t k, int fmt) { return fmt == kFp8E2M1 ? k / 2 : (mx_is_fp6(fmt) ? k / 4 * 3 : k); }
+
+constexpr int kMx6TileK = 128;                   // mx6_gemm.hip: K VALUES per step
+constexpr int kMx6RowBytes = kMx6TileK / 4 * 3;  // ... which are 96 bytes of a row: six 16-byte chunks
 
 constexpr int kMx4TileK = 256;  // mx4_gemm.hip: K VALUES per step (a 128-byte LDS row of fp4)
 
@@ -54,7 +67,7 @@ inline void mx_scale_check(const char* e, const void* s, int64_t lds, int64_t k,
 
 // x bf16 [R][C] (row stride ld elements), C % 32 == 0. Row-wise image: q [R][ldq] with s [R][lds], both or
 // neither. Transposed image (blocks along R, so R % 32 == 0): qt [C][ldt] with st [C][ldst], both or neither.
-// ldq / ldt are bytes: >= C / R for fp8, >= C / 2 and R / 2 for fp4.
+// ldq / ldt are bytes: >= C / R for fp8, >= C / 2 and R / 2 for fp4, >= 3 C / 4 and 3 R / 4 for fp6.
 inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, const void* q,
                                       int64_t ldq, const void* s, int64_t lds, const void* qt, int64_t ldt,
                                       const void* st, int64_t ldst) {
@@ -72,14 +85,14 @@ inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64
   if (q != nullptr) {
     if (!fp8_aligned16(q)) fp8_fail(e, "the output must be 16-byte aligned");
     if (ldq < mx_row_bytes(C, fmt) || ldq % 16 != 0)
-      fp8_fail(e, "the output's row stride must be >= C (fp4: C / 2) bytes and a multiple of 16");
+      fp8_fail(e, "the output's row stride must be >= C (fp4: C / 2, fp6: 3 C / 4) bytes and a multiple of 16");
     mx_scale_check(e, s, lds, C, "the scale image");
   }
   if (qt != nullptr) {
     if (R % kMxBlock != 0) fp8_fail(e, "the transposed image needs R % 32 == 0 (its blocks run along R)");
     if (!fp8_aligned16(qt)) fp8_fail(e, "the transposed output must be 16-byte aligned");
     if (ldt < mx_row_bytes(R, fmt) || ldt % 16 != 0)
-      fp8_fail(e, "the transposed output's row stride must be >= R (fp4: R / 2) bytes and a multiple of 16");
+      fp8_fail(e, "the transposed output's row stride must be >= R (fp4: R / 2, fp6: 3 R / 4) bytes and a multiple of 16");
     mx_scale_check(e, st, ldst, R, "the transposed scale image");
   }
   MxQuantGeometry g{};
@@ -91,21 +104,25 @@ inline MxQuantGeometry mx_quant_check(const void* x, int64_t R, int64_t C, int64
 }
 
 // C bf16 [M][ldc] = A fp8 [M][K] (lda bytes, scales sa [M][ldsa]) x B fp8 [N][K] (ldb, sb [N][ldsb]); bias [N]
-// bf16 (9) or fp32 (7) or null. K counts values: an fp4 operand's row is K / 2 bytes
+// bf16 (9) or fp32 (7) or null. K counts values: an fp4 operand's row is K / 2 bytes, an fp6 one's 3 K / 4
 inline Fp8GemmGeometry mx_gemm_check(const void* a, const void* b, const void* c, const void* bias, int bias_dtype,
                                      const void* sa, const void* sb, int64_t M, int64_t N, int64_t K, int64_t lda,
                                      int64_t ldb, int64_t ldc, int64_t ldsa, int64_t ldsb, int fa, int fb) {
   const char* e = "mx_gemm";
   mx_format_check(e, fa);
   mx_format_check(e, fb);
-  if (!(fb == kFp8E4M3 && fa != kFp8E2M1) && !(fb == kFp8E2M1 && fa != kFp8E5M2))
+  if (mx_is_fp6(fa) || mx_is_fp6(fb)) {
+    if (fb != kMxE2M3 || !mx_is_fp6(fa))
+      fp8_fail(e, "an fp6 operand: A x B is e2m3 x e2m3 or e3m2 x e2m3 (no other pair with an fp6 side is built)");
+  } else if (!(fb == kFp8E4M3 && fa != kFp8E2M1) && !(fb == kFp8E2M1 && fa != kFp8E5M2)) {
     fp8_fail(e, "A x B is e4m3 x e4m3, e5m2 x e4m3, e2m1 x e2m1 or e4m3 x e2m1 (no other pair is built)");
+  }
   if (M < 1 || M > kFp8MaxDim) fp8_fail(e, "M must lie in 1 .. 2^31 - 256");
   if (N < 8 || N % 8 != 0 || N > kFp8MaxDim) fp8_fail(e, "N must be a positive multiple of 8 below 2^31 - 256");
   if (K < kMxBlock || K % kMxBlock != 0 || K > kFp8MaxDim)
     fp8_fail(e, "K must be a positive multiple of 32 below 2^31 - 256");
   if (lda < mx_row_bytes(K, fa) || lda % 16 != 0 || ldb < mx_row_bytes(K, fb) || ldb % 16 != 0)
-    fp8_fail(e, "the operands' row strides must be >= K (fp4: K / 2) bytes and multiples of 16");
+    fp8_fail(e, "the operands' row strides must be >= K (fp4: K / 2, fp6: 3 K / 4) bytes and multiples of 16");
   if (ldc < N || ldc % 8 != 0) fp8_fail(e, "the output's row stride must be >= N and a multiple of 8 elements");
   if (a == nullptr || b == nullptr || c == nullptr) fp8_fail(e, "null tensor");
   if (!fp8_aligned16(a) || !fp8_aligned16(b) || !fp8_aligned16(c) || !fp8_aligned16(bias))

@@ -190,6 +190,8 @@ void mx_quantize(const void* x, int64_t R, int64_t C, int64_t ld, int fmt, void*
                  void* qt, int64_t ldt, void* st, int64_t ldst, hipStream_t stream) {
   const MxQuantGeometry g = mx_quant_check(x, R, C, ld, fmt, q, ldq, s, lds, qt, ldt, st, ldst);
   if (fmt == kFp8E2M1) return mx4_quantize_launch(x, R, C, ld, q, ldq, s, lds, qt, ldt, st, ldst, g.col_tiles, g.grid, stream);
+  if (mx_is_fp6(fmt))
+    return mx6_quantize_launch(x, R, C, ld, fmt, q, ldq, s, lds, qt, ldt, st, ldst, g.col_tiles, g.grid, stream);
   const MxQuantArgs a{static_cast<const uint16_t*>(x), static_cast<uint8_t*>(q), static_cast<uint8_t*>(s),
                       static_cast<uint8_t*>(qt), static_cast<uint8_t*>(st), ld, ldq, lds, ldt, ldst,
                       static_cast<int>(R), static_cast<int>(C), static_cast<int>(g.col_tiles)};

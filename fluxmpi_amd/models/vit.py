@@ -129,9 +129,9 @@ class Block(nn.Module):
         self.ln1 = FusedLayerNorm(dim, eps=1e-6)
         if fp8:  # qkv is the block's one plain Linear: the others live in fused nodes and stay bf16
             from ..ops.fp8 import Fp8Linear
-            mx = fp8 in ("mx", "mx+wgrad", "mx4")
+            mx = fp8 in ("mx", "mx+wgrad", "mx4", "mx6")
             self.qkv = Fp8Linear(dim, 3 * dim, scaling="mx" if mx else "current",
-                                 wgrad="mx" if fp8 == "mx+wgrad" else "bf16", fwd="e2m1" if fp8 == "mx4" else "e4m3")
+                                 wgrad="mx" if fp8 == "mx+wgrad" else "bf16", fwd={"mx4": "e2m1", "mx6": "e2m3"}.get(fp8, "e4m3"))
         else:
             self.qkv = Linear(dim, 3 * dim)
         self.proj = Linear(dim, dim)
@@ -215,9 +215,9 @@ def _default_embed() -> str:
 
 def _default_fp8():
     """False, or ``FLUXMPI_FP8=1`` (True) / ``FLUXMPI_FP8=mx`` (``"mx"``) / ``FLUXMPI_FP8=mx+wgrad`` (``"mx+wgrad"``) /
-    ``FLUXMPI_FP8=mx4`` (``"mx4"``) for A/B runs of an unchanged ``bench.py``."""
+    ``FLUXMPI_FP8=mx4`` (``"mx4"``) / ``FLUXMPI_FP8=mx6`` (``"mx6"``) for A/B runs of an unchanged ``bench.py``."""
     v = os.environ.get("FLUXMPI_FP8", "0")
-    return v if v in ("mx", "mx+wgrad", "mx4") else v == "1"
+    return v if v in ("mx", "mx+wgrad", "mx4", "mx6") else v == "1"
 
 
 class ViT(nn.Module):
@@ -231,12 +231,13 @@ class ViT(nn.Module):
     the same with MX block scaling (a scale per 32 values, the scaled MFMA); ``fp8="mx+wgrad"``: MX with the weight
     gradient in fp8 as well (``mx_wgrad.hip``; token counts that are multiples of 32); ``fp8="mx4"``: MX with fp4 (e2m1) forward operands and
     e4m3 ``dy`` against ``W``'s fp4 image for the input gradient (``mx4_gemm.hip``; experimental, convergence not
-    measured); ``state_dict()`` is unchanged."""
+    measured); ``fp8="mx6"``: MX with fp6 operands in both GEMMs, ``x`` and ``W`` in e2m3 and ``dy`` in e3m2
+    (``mx6_gemm.hip``; experimental, convergence not measured); ``state_dict()`` is unchanged."""
 
     def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, num_classes=1000, embed=None,
                  fp8=None):
         super().__init__()
-        fp8 = _default_fp8() if fp8 is None else (fp8 if fp8 in ("mx", "mx+wgrad", "mx4") else bool(fp8))
+        fp8 = _default_fp8() if fp8 is None else (fp8 if fp8 in ("mx", "mx+wgrad", "mx4", "mx6") else bool(fp8))
         embed = _default_embed() if embed is None else embed
         if embed not in ("unfold", "fused"):
             raise ValueError(f"embed must be 'unfold' or 'fused', got {embed!r}")

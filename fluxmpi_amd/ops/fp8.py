@@ -30,17 +30,20 @@ from .multi_tensor import DTYPE_CODE
 
 E4M3, E5M2 = "e4m3", "e5m2"
 E2M1 = "e2m1"  # fp4, the MX entries only (the MX section below)
-FMT_CODE = {E4M3: 0, E5M2: 1, E2M1: 2}
-FMAX = {E4M3: 448.0, E5M2: 57344.0, E2M1: 6.0}
-TOP = {E4M3: 1.75, E5M2: 1.75, E2M1: 1.5}  # the significand of FMAX
+E2M3, E3M2 = "e2m3", "e3m2"  # fp6, the MX entries only
+FMT_CODE = {E4M3: 0, E5M2: 1, E2M1: 2, E2M3: 3, E3M2: 4}
+FMAX = {E4M3: 448.0, E5M2: 57344.0, E2M1: 6.0, E2M3: 7.5, E3M2: 28.0}
+TOP = {E4M3: 1.75, E5M2: 1.75, E2M1: 1.5, E2M3: 1.875, E3M2: 1.75}  # the significand of FMAX
+MX_ONLY = (E2M1, E2M3, E3M2)
 TORCH_DTYPE = {E4M3: torch.float8_e4m3fn, E5M2: torch.float8_e5m2}
 BLOCK_WORDS = 8
 
 
 def _fmt(fmt: str, mx: bool = False) -> str:
-    """The format's name checked: ``'e2m1'`` where ``mx`` (the block-scaled entries that have fp4 kernels) only."""
-    if fmt not in FMT_CODE or (fmt == E2M1 and not mx):
-        names = "'e4m3', 'e5m2' or 'e2m1'" if mx else "'e4m3' or 'e5m2'"
+    """The format's name checked: ``'e2m1'``, ``'e2m3'`` and ``'e3m2'`` where ``mx`` (the block-scaled entries that
+    have fp4 and fp6 kernels) only."""
+    if fmt not in FMT_CODE or (fmt in MX_ONLY and not mx):
+        names = "'e4m3', 'e5m2', 'e2m1', 'e2m3' or 'e3m2'" if mx else "'e4m3' or 'e5m2'"
         raise ValueError(f"fp8: the format is {names}, got {fmt!r}")
     return fmt
 
@@ -214,13 +217,16 @@ class Fp8State:
             raise ValueError(f"fp8_linear: wgrad must be 'bf16' or 'mx', got {wgrad!r}")
         if wgrad == "mx" and scaling != "mx":
             raise ValueError(f"fp8_linear: wgrad='mx' needs scaling='mx', got scaling={scaling!r}")
-        if fwd not in (E4M3, E2M1) or (fwd == E2M1 and scaling != "mx"):
-            raise ValueError(f"fp8_linear: fwd is 'e4m3', or 'e2m1' with scaling='mx', got {fwd!r} with {scaling!r}")
-        if fwd == E2M1 and wgrad == "mx":
-            raise ValueError("fp8_linear: fwd='e2m1' has no fp8 weight gradient (wgrad='mx' wants an e4m3 token-blocked "
+        if fwd not in (E4M3, E2M1, E2M3) or (fwd != E4M3 and scaling != "mx"):
+            raise ValueError(f"fp8_linear: fwd is 'e4m3', or 'e2m1' or 'e2m3' with scaling='mx', got {fwd!r} with "
+                             f"{scaling!r}")
+        if fwd != E4M3 and wgrad == "mx":
+            raise ValueError(f"fp8_linear: fwd={fwd!r} has no fp8 weight gradient (wgrad='mx' wants an e4m3 token-blocked "
                              "image of x, which this mode does not produce)")
         self.scaling = scaling
-        self.fwd = fwd  # "e2m1" (MX only): x and W in fp4 for the forward, dy e4m3 against W's packed transposed image
+        # "e2m1" (MX only): x and W in fp4 for the forward, dy e4m3 against W's packed transposed image; "e2m3" (MX only):
+        # x and W in fp6 e2m3, dy in fp6 e3m2 against W's packed transposed image
+        self.fwd = fwd
         self.blocks = blocks
         self.wgrad = wgrad  # "mx": the weight gradient in block-scaled fp8 too (mx_wgrad.hip), T % 32 == 0
 
@@ -286,7 +292,8 @@ class Fp8Linear(torch.nn.Linear):
     buffer; ``scaling="mx"`` is block scaling (``mx_quant.hip``, ``mx_gemm.hip``) where :func:`mx_supported`, and
     with ``wgrad="mx"`` the weight gradient runs in fp8 too (``mx_wgrad.hip``) where the token count is a multiple
     of 32; ``fwd="e2m1"`` (with ``scaling="mx"``) runs the forward on fp4 images of ``x`` and ``W`` and the input
-    gradient on e4m3 ``dy`` against ``W``'s fp4 transposed image (``mx4_quant.hip``, ``mx4_gemm.hip``)."""
+    gradient on e4m3 ``dy`` against ``W``'s fp4 transposed image (``mx4_quant.hip``, ``mx4_gemm.hip``); ``fwd="e2m3"``
+    runs both on fp6: ``x`` and both images of ``W`` in e2m3, ``dy`` in e3m2 (``mx6_quant.hip``, ``mx6_gemm.hip``)."""
 
     def __init__(self, in_features, out_features, bias=True, scaling="current", wgrad="bf16", fwd=E4M3, **kw):
         super().__init__(in_features, out_features, bias=bias, **kw)
@@ -333,13 +340,69 @@ MX_BLOCK = 32
 MX_ONE = 127
 MX_NAN = 255  # E8M0's NaN: an e2m1 block that held a non-finite value
 MX4_STAGES = 2  # LDS stages of mx4_gemm.hip, each 256 values of K deep
-MX_PAIRS = ((E4M3, E4M3), (E5M2, E4M3), (E2M1, E2M1), (E4M3, E2M1))  # what mx_gemm builds, a x b
+MX6_STAGES = 2  # LDS stages of mx6_gemm.hip, each MX6_STAGE_K values of K deep
+MX6_STAGE_K = 128
+MX_PAIRS = ((E4M3, E4M3), (E5M2, E4M3), (E2M1, E2M1), (E4M3, E2M1), (E2M3, E2M3), (E3M2, E2M3))  # what mx_gemm builds, a x b
 FP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # code = sign << 3 | index
+# ``'e2m3'`` / ``'e3m2'`` (OCP FP6, no inf or NaN; code = sign << 5 | exponent << MB | mantissa) are packed four values in
+# three bytes: value ``i`` of a 32-value block at bits ``6 i .. 6 i + 5`` of the block's 24 bytes read as one little-endian
+# bit string, the order the scaled MFMA reads (``mx6_gemm.hip``). ``q`` is ``[R, 3 C / 4]``, a view of rows rounded up to
+# 16 bytes (the kernels' row strides are multiples of 16). Scale rule and the byte 255 as e2m1. ``mx6_quant.hip`` /
+# ``mx6_gemm.hip``; pairs e2m3 x e2m3 and e3m2 x e2m3.
+FP6_BITS = {E2M3: (3, 1), E3M2: (2, 3)}  # mantissa bits, exponent bias
+
+
+def fp6_grid(fmt: str) -> torch.Tensor:
+    """The 32 magnitudes of ``fmt`` by code (float64, increasing)."""
+    mb, bias = FP6_BITS[fmt]
+    c = torch.arange(32, dtype=torch.float64)
+    e, m = torch.div(c, 2 ** mb, rounding_mode="floor"), c % 2 ** mb
+    return torch.where(e == 0, m * 2.0 ** (1 - bias - mb), (1 + m / 2 ** mb) * 2.0 ** (e - bias))
 
 
 def _cols(fmt: str, k: int) -> int:
     """Bytes of ``k`` values of ``fmt``."""
-    return k // 2 if fmt == E2M1 else k
+    return k // 2 if fmt == E2M1 else (k // 4 * 3 if fmt in FP6_BITS else k)
+
+
+def _values(fmt: str, cols: int) -> int:
+    """:func:`_cols` inverted."""
+    return cols * 2 if fmt == E2M1 else (cols // 3 * 4 if fmt in FP6_BITS else cols)
+
+
+def _rows16(r: int, cols: int, device=None) -> torch.Tensor:
+    """uint8 zeros ``[r, cols]`` as a view of rows rounded up to 16 bytes."""
+    return torch.zeros(r, _pad16(cols), dtype=torch.uint8, device=device)[:, :cols]
+
+
+def mx_pack_fp6(values: torch.Tensor, fmt: str) -> torch.Tensor:
+    """Grid values ``[R, C]`` (float, ``C % 4 == 0``) of ``fmt`` as packed codes uint8 ``[R, 3 C / 4]`` (a view of rows
+    rounded up to 16 bytes): codes ``c0 .. c3`` of four values are the 24-bit little-endian string ``c0 | c1 << 6 |
+    c2 << 12 | c3 << 18``."""
+    v = values.detach().double()
+    code = torch.bucketize(v.abs(), fp6_grid(fmt).to(v.device)) | (torch.signbit(v).long() << 5)
+    w = code[:, 0::4] | (code[:, 1::4] << 6) | (code[:, 2::4] << 12) | (code[:, 3::4] << 18)
+    out = _rows16(v.shape[0], _cols(fmt, v.shape[1]), v.device)
+    out.copy_(torch.stack([w & 255, (w >> 8) & 255, w >> 16], -1).reshape(v.shape[0], -1))
+    return out
+
+
+def mx_unpack_fp6(q: torch.Tensor, fmt: str) -> torch.Tensor:
+    """Packed codes uint8 ``[R, 3 C / 4]`` as their float32 values ``[R, C]``."""
+    b = q.long().reshape(q.shape[0], -1, 3)
+    w = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    code = torch.stack([(w >> s) & 63 for s in (0, 6, 12, 18)], -1).reshape(q.shape[0], -1)
+    v = fp6_grid(fmt).float().to(q.device)[code & 31]
+    return torch.where((code & 32) != 0, -v, v)
+
+
+def _round_fp6(y: torch.Tensor, fmt: str) -> torch.Tensor:
+    """``y`` (float32, ``|y| <= FMAX``) to the grid of ``fmt``: the spacing at ``|y|``'s exponent (the subnormal step
+    below the smallest normal), then ``torch.round``, which takes a midpoint to the even multiple."""
+    mb, bias = FP6_BITS[fmt]
+    _, ex = torch.frexp(y.abs())  # |y| = m 2^ex, m in [0.5, 1): the exponent is ex - 1
+    step = torch.ldexp(torch.ones_like(y), (ex - 1).clamp(min=1 - bias) - mb)
+    return torch.copysign(torch.round(y.abs() / step) * step, y)
 
 
 def mx_pack_fp4(values: torch.Tensor) -> torch.Tensor:
@@ -379,7 +442,7 @@ class MxTensor:
     scales: torch.Tensor
     q_t: torch.Tensor | None
     scales_t: torch.Tensor | None
-    fmt: str  # 'e2m1': q and q_t are packed, [R, C / 2] and [C, R / 2]
+    fmt: str  # 'e2m1': q and q_t are packed, [R, C / 2] and [C, R / 2]; 'e2m3' / 'e3m2': [R, 3 C / 4] and [C, 3 R / 4]
 
     def t(self) -> "MxTensor":
         """The transposed image as a GEMM operand."""
@@ -393,7 +456,7 @@ def mx_quantize_reference(x: torch.Tensor, fmt: str):
     along the last axis; :func:`pow2_scale` of every block's amax (vectorised with ``torch.frexp``), torch's
     round-to-nearest-even cast, non-finite inputs kept non-finite in a block of scale 1. ``'e2m1'``: ``q`` is float32
     values on the fp4 grid (:func:`mx_pack_fp4` packs them), and a block with a non-finite input is zeros under the
-    byte 255."""
+    byte 255; ``'e2m3'`` / ``'e3m2'`` likewise on the fp6 grids (:func:`mx_pack_fp6`)."""
     xf = x.detach().float().cpu()
     r, c = xf.shape
     if c % MX_BLOCK:
@@ -406,9 +469,9 @@ def mx_quantize_reference(x: torch.Tensor, fmt: str):
     p = int(math.log2(FMAX[fmt] / top)) - (e - 1) - (2 * m > top).int()
     p = torch.where(ok, p.clamp(-126, 126), torch.zeros_like(p))
     y = (blk * torch.ldexp(torch.ones_like(amax), p).unsqueeze(-1)).clamp(-FMAX[fmt], FMAX[fmt])
-    if fmt == E2M1:
+    if fmt in MX_ONLY:
         bad = ~torch.isfinite(amax)
-        y = torch.where(bad.unsqueeze(-1), torch.zeros_like(y), _round_fp4(y))
+        y = torch.where(bad.unsqueeze(-1), torch.zeros_like(y), _round_fp4(y) if fmt == E2M1 else _round_fp6(y, fmt))
         return y.view(r, c), torch.where(bad, torch.full_like(p, MX_NAN), MX_ONE - p).to(torch.uint8)
     return torch.where(torch.isfinite(blk), y, blk).view(r, c).to(TORCH_DTYPE[fmt]), (MX_ONE - p).to(torch.uint8)
 
@@ -457,14 +520,16 @@ def mx_quantize_into(x, fmt, q=None, scales=None, q_t=None, scales_t=None) -> No
 
 
 def mx_quantize(x: torch.Tensor, fmt: str, transpose: bool = False) -> MxTensor:
-    """The MX image of the bf16 matrix ``x`` in one launch; ``transpose``: the image blocked along ``R`` too."""
+    """The MX image of the bf16 matrix ``x`` in one launch; ``transpose``: the image blocked along ``R`` too. fp6 images
+    are views of rows rounded up to 16 bytes (``3 C / 4`` is not always a multiple of 16, the row stride must be)."""
     _fmt(fmt, mx=True)
     if not x.is_cuda or x.dim() != 2:
         raise ValueError("fp8.mx_quantize: the input is a bf16 matrix on the GPU (CPU tensors take "
                          "mx_quantize_reference)")
     r, c = x.shape
     new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=x.device)
-    t = MxTensor(new(r, _cols(fmt, c)), new(r, mx_scale_cols(c)), new(c, _cols(fmt, r)) if transpose else None,
+    img = lambda rows, cols: new(rows, _pad16(cols))[:, :cols] if cols % 16 else new(rows, cols)
+    t = MxTensor(img(r, _cols(fmt, c)), new(r, mx_scale_cols(c)), img(c, _cols(fmt, r)) if transpose else None,
                  new(c, mx_scale_cols(r)) if transpose else None, fmt)
     mx_quantize_into(x, fmt, t.q, t.scales, t.q_t, t.scales_t)
     return t
@@ -473,12 +538,13 @@ def mx_quantize(x: torch.Tensor, fmt: str, transpose: bool = False) -> MxTensor:
 def mx_gemm_into(out: torch.Tensor, a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
     """:func:`mx_gemm` into the bf16 view ``out [M, N]`` (any row stride that is a multiple of 8)."""
     if (a.fmt, b.fmt) not in MX_PAIRS:
-        raise ValueError("fp8.mx_gemm: the operands are e4m3 x e4m3, e5m2 x e4m3, e2m1 x e2m1 or e4m3 x e2m1")
+        raise ValueError("fp8.mx_gemm: the operands are e4m3 x e4m3, e5m2 x e4m3, e2m1 x e2m1, e4m3 x e2m1, e2m3 x e2m3 "
+                         "or e3m2 x e2m3")
     m, n = a.q.shape[0], b.q.shape[0]
-    k = a.q.shape[1] * (2 if a.fmt == E2M1 else 1)  # values: an e2m1 image is packed
-    if not a.q.is_cuda or b.q.shape[1] != _cols(b.fmt, k) or k % MX_BLOCK or n % 8:
+    k = _values(a.fmt, a.q.shape[1])  # values: an e2m1 or fp6 image is packed
+    if not a.q.is_cuda or a.q.shape[1] != _cols(a.fmt, k) or b.q.shape[1] != _cols(b.fmt, k) or k % MX_BLOCK or n % 8:
         raise ValueError(f"fp8.mx_gemm: a [M, K] and b [N, K] on the GPU need K % 32 == 0 and N % 8 == 0 (an e2m1 image "
-                         f"has K / 2 columns), got {tuple(a.q.shape)} and {tuple(b.q.shape)}")
+                         f"has K / 2 columns, an fp6 one 3 K / 4), got {tuple(a.q.shape)} and {tuple(b.q.shape)}")
     for t, rows in ((a, m), (b, n)):
         if t.scales.dtype != torch.uint8 or t.scales.shape[0] != rows or t.scales.shape[1] < mx_scale_cols(k):
             raise ValueError(f"fp8.mx_gemm: a scale image must be uint8 [{rows}, >= {mx_scale_cols(k)}]")
@@ -501,7 +567,8 @@ def mx_gemm_into(out: torch.Tensor, a: MxTensor, b: MxTensor, bias: torch.Tensor
 
 def mx_gemm(a: MxTensor, b: MxTensor, bias: torch.Tensor | None = None) -> torch.Tensor:
     """``bf16(sum over K blocks of the dequantised a_blk . b_blk + bias)``: ``a [M, K]`` e4m3 or e5m2 with ``b [N, K]``
-    e4m3, or ``a`` e2m1 or e4m3 with ``b`` e2m1 (``mx4_gemm.hip``); the block scales applied inside the MFMA, fp32
+    e4m3, or ``a`` e2m1 or e4m3 with ``b`` e2m1 (``mx4_gemm.hip``), or ``a`` e2m3 or e3m2 with ``b`` e2m3
+    (``mx6_gemm.hip``); the block scales applied inside the MFMA, fp32
     accumulation."""
     out = torch.empty(a.q.shape[0], b.q.shape[0], dtype=torch.bfloat16, device=a.q.device)
     return mx_gemm_into(out, a, b, bias)
@@ -566,7 +633,8 @@ class _MxLinearFn(torch.autograd.Function):
     not needed); W's two images come from one launch in every forward (:class:`Fp8State` says why). ``fp8_wgrad``
     (``wgrad="mx"`` and a token count that is a multiple of 32): x and dy are cast with their token-blocked images in
     the same launches, the backward keeps x's instead of the bf16 x, and dW is :func:`mx_wgrad` of the two.
-    ``fwd="e2m1"``: x and W are cast to fp4 instead (W's transposed image packed along ``n_out``), dy stays e4m3."""
+    ``fwd="e2m1"``: x and W are cast to fp4 instead (W's transposed image packed along ``n_out``), dy stays e4m3.
+    ``fwd="e2m3"``: x and W are cast to fp6 e2m3 and dy to e3m2, a homogeneous fp6 pair in both GEMMs."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, fp8_wgrad=False, fwd=E4M3):
@@ -578,6 +646,7 @@ class _MxLinearFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(x, weight)
         ctx.wq, ctx.bias, ctx.fp8_wgrad, ctx.x_shape = wq, bias, fp8_wgrad, x.shape
+        ctx.dy_fmt = E3M2 if fwd == E2M3 else E4M3
         return mx_gemm(xq, wq, bias).view(*x.shape[:-1], n_out)
 
     @staticmethod
@@ -591,7 +660,7 @@ class _MxLinearFn(torch.autograd.Function):
         dx = None
         if not ctx.fp8_wgrad:
             if ctx.needs_input_grad[0]:
-                dx = mx_gemm(mx_quantize(dy2, E4M3), ctx.wq.t()).view(ctx.x_shape)
+                dx = mx_gemm(mx_quantize(dy2, ctx.dy_fmt), ctx.wq.t()).view(ctx.x_shape)
             dw, db = wgrad_bgrad(ctx.saved_tensors[0].reshape(-1, n_in), w, ctx.bias, dy2, ctx.needs_input_grad[1], need_b)
             return dx, dw, db, None, None
         # one cast of dy: the row-wise image feeds dx, the token-blocked one dW
@@ -612,17 +681,17 @@ class _MxLinearFn(torch.autograd.Function):
 def mx_linear_reference(x, w, b, dy, fwd: str = E4M3):
     """``(y, dx, |y|, |dx|)`` in float64 on the CPU of the same quantisation, as :func:`fp8_linear_reference`: x and
     w blocked along ``n_in`` for y, dy and w blocked along ``n_out`` for dx; x and both images of w in ``fwd``, dy in
-    e4m3."""
+    e4m3 (e3m2 with ``fwd="e2m3"``)."""
     n_out, n_in = w.shape
     xd, wd, dyd, wtd = (mx_dequantize(*mx_quantize_reference(t, f)) for t, f in
-                        ((x.reshape(-1, n_in), fwd), (w, fwd), (dy.reshape(-1, n_out), E4M3),
+                        ((x.reshape(-1, n_in), fwd), (w, fwd), (dy.reshape(-1, n_out), E3M2 if fwd == E2M3 else E4M3),
                          (w.detach().t().contiguous(), fwd)))
     bd = b.detach().double().cpu() if b is not None else torch.zeros(n_out, dtype=torch.float64)
     y, ya = xd @ wd.t() + bd, xd.abs() @ wd.abs().t() + bd.abs()
     return y, dyd @ wtd.t(), ya, dyd.abs() @ wtd.abs().t()
 
 
-__all__ = ["E4M3", "E5M2", "E2M1", "FMAX", "mx_pack_fp4", "mx_unpack_fp4", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
+__all__ = ["E4M3", "E5M2", "E2M1", "E2M3", "E3M2", "FMAX", "mx_pack_fp4", "mx_unpack_fp4", "mx_pack_fp6", "mx_unpack_fp6", "Fp8Tensor", "Fp8State", "Fp8Linear", "fp8_linear", "fp8_linear_reference",
            "quantize", "quantize_into", "quantize_reference", "pow2_scale", "scale_update", "new_block", "gemm",
            "gemm_into", "supported", "layout_ok", "MX_BLOCK", "MxTensor", "mx_quantize", "mx_quantize_into",
            "mx_quantize_reference", "mx_dequantize", "mx_scale_image", "mx_gemm", "mx_gemm_into", "mx_supported",

@@ -31,9 +31,15 @@ GEMM lines the achieved PFLOP/s (2 M N K over the median).
   qkv_fwdbwd_{bf16,fp8_mx,fp8_mx4}     ``Linear`` / ``Fp8Linear(scaling="mx")`` with ``fwd="e4m3"`` and ``"e2m1"``
   vit_b16_step_{bf16,mx,mx4}           ``bench.py`` child processes as under ``--wgrad``, into ``--ab-out``
 
+``--fp6`` is ``--fp4`` with the fp6 MX path (``mx6_quant.hip``, ``mx6_gemm.hip``) beside both, all variants alternated in
+one process: ``quant_{x,w}_mx6`` (e2m3) and ``quant_dy_mx6`` (e3m2), ``gemm_fwd_{layer}_mx6`` (e2m3 x e2m3),
+``gemm_dgrad_{layer}_mx6`` (e3m2 dy x e2m3 W^T), ``qkv_fwdbwd_fp8_mx6`` and ``vit_b16_step_mx6``; its rows carry
+``mx_over_mx6``, ``mx4_over_mx6`` and ``bf16_over_mx6``.
+
 usage: python scripts/bench_fp8.py [--out profiles/fp8_vit_b16.jsonl] [--rounds 7] [--iters 20] [--tokens 50432]
        python scripts/bench_fp8.py --wgrad [--out profiles/mx_wgrad_vit_b16.jsonl] [--vit-steps 20] [--vit-rounds 2]
        python scripts/bench_fp8.py --fp4 [--out profiles/mx4_vit_b16.jsonl] [--ab-out profiles/mx4_bench_ab.jsonl]
+       python scripts/bench_fp8.py --fp6 [--out profiles/mx6_vit_b16.jsonl] [--ab-out profiles/mx6_bench_ab.jsonl]
 """
 import argparse
 import json
@@ -146,34 +152,40 @@ def main_wgrad(a):
     return 0
 
 
-def main_fp4(a):
+def main_fp4(a, fp6=False):
     M = a.tokens
+    six = (("mx6", fp8.E2M3),) if fp6 else ()
     torch.manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device="cuda").bfloat16()
     fns, keep, flops = {}, [], {}
     with torch.no_grad():
         for name, (n_in, n_out) in LAYERS.items():
             x, w, dy = rnd(M, n_in), rnd(n_out, n_in) * n_in ** -0.5, rnd(M, n_out)
-            dyq = fp8.mx_quantize(dy, fp8.E4M3)
-            for key, fmt in (("mx4", fp8.E2M1), ("mx", fp8.E4M3)):
+            dy8 = fp8.mx_quantize(dy, fp8.E4M3)
+            for key, fmt in six + (("mx4", fp8.E2M1), ("mx", fp8.E4M3)):
                 xq, wq = fp8.mx_quantize(x, fmt), fp8.mx_quantize(w, fmt, transpose=True)
+                dyq = fp8.mx_quantize(dy, fp8.E3M2) if key == "mx6" else dy8
                 fns[f"gemm_fwd_{name}_{key}"], o1 = graphed(lambda xq=xq, wq=wq: fp8.mx_gemm(xq, wq))
                 fns[f"gemm_dgrad_{name}_{key}"], o2 = graphed(lambda wq=wq, dyq=dyq: fp8.mx_gemm(dyq, wq.t()))
-                keep += [xq, wq, o1, o2]
+                keep += [xq, wq, dyq, o1, o2]
+                if name == "qkv" and key == "mx6":
+                    fns["quant_dy_mx6"], o1 = graphed(lambda dy=dy: fp8.mx_quantize(dy, fp8.E3M2))
+                    keep.append(o1)
                 if name == "qkv":
                     fns[f"quant_x_{key}"], o1 = graphed(lambda x=x, fmt=fmt: fp8.mx_quantize(x, fmt))
                     fns[f"quant_w_{key}"], o2 = graphed(lambda w=w, fmt=fmt: fp8.mx_quantize(w, fmt, transpose=True))
                     keep += [o1, o2]
             fns[f"gemm_fwd_{name}_bf16"], o1 = graphed(lambda x=x, w=w: L.fwd(x, w, None))
             fns[f"gemm_dgrad_{name}_bf16"], o2 = graphed(lambda dy=dy, w=w: L.dgrad(dy, w))
-            keep += [x, w, dy, dyq, o1, o2]
+            keep += [x, w, dy, dy8, o1, o2]
             for k in fns:
                 if k.startswith(("gemm_fwd_" + name, "gemm_dgrad_" + name)):
                     flops[k] = 2.0 * M * n_in * n_out
     n_in, n_out = LAYERS["qkv"]
     x, dy = rnd(M, n_in).requires_grad_(), rnd(M, n_out)
     for key, lin in (("bf16", L.Linear(n_in, n_out)), ("fp8_mx", fp8.Fp8Linear(n_in, n_out, scaling="mx")),
-                     ("fp8_mx4", fp8.Fp8Linear(n_in, n_out, scaling="mx", fwd="e2m1"))):
+                     ("fp8_mx4", fp8.Fp8Linear(n_in, n_out, scaling="mx", fwd="e2m1"))) + (
+                         (("fp8_mx6", fp8.Fp8Linear(n_in, n_out, scaling="mx", fwd="e2m3")),) if fp6 else ()):
         lin = lin.cuda().bfloat16()
 
         def fwdbwd(lin=lin):
@@ -192,6 +204,11 @@ def main_fp4(a):
                  "rounds": a.rounds, "iters": a.iters, "mode": "graph", "tokens": M}
             if k in flops:
                 r["pflops"] = round(flops[k] / med[k] * 1e-9, 3)
+            if k.endswith("_mx6") and k != "quant_dy_mx6":
+                r["mx_over_mx6"], r["mx4_over_mx6"] = round(med[k[:-1]] / med[k], 2), round(med[k[:-1] + "4"] / med[k], 2)
+                other = k[:-3] + "bf16" if k.startswith("gemm") else "qkv_fwdbwd_bf16" if k.startswith("qkv") else None
+                if other:
+                    r["bf16_over_mx6"] = round(med[other] / med[k], 2)
             if k.endswith("_mx4"):
                 r["mx_over_mx4"] = round(med[k[:-1]] / med[k], 2)
                 other = k[:-3] + "bf16" if k.startswith("gemm") else "qkv_fwdbwd_bf16" if k.startswith("qkv") else None
@@ -205,7 +222,7 @@ def main_fp4(a):
     if a.vit_rounds > 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.ab_out)), exist_ok=True)
         with open(a.ab_out, "w") as f:
-            for key, rs in vit_steps(a, ("bf16", "mx", "mx4")).items():
+            for key, rs in vit_steps(a, ("bf16", "mx", "mx4") + (("mx6",) if fp6 else ())).items():
                 line = json.dumps({"variant": f"vit_b16_step_{key}", "value": [r.get("value") for r in rs],
                                    "unit": rs[0].get("unit"), "steps": a.vit_steps})
                 print(line, flush=True)
@@ -216,7 +233,8 @@ def main_fp4(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp4", action="store_true", help="the fp4 (e2m1) MX rows (module docstring)")
-    ap.add_argument("--ab-out", default=os.path.join("profiles", "mx4_bench_ab.jsonl"))
+    ap.add_argument("--fp6", action="store_true", help="the fp4 rows with the fp6 (e2m3 / e3m2) MX rows beside them")
+    ap.add_argument("--ab-out", default=None)
     ap.add_argument("--wgrad", action="store_true", help="the MX weight-gradient rows (module docstring)")
     ap.add_argument("--vit-steps", type=int, default=20)
     ap.add_argument("--vit-rounds", type=int, default=2)
@@ -228,10 +246,11 @@ def main():
     if not torch.cuda.is_available():
         print("bench_fp8.py needs a GPU", file=sys.stderr)
         return 2
-    a.out = a.out or os.path.join("profiles", "mx4_vit_b16.jsonl" if a.fp4 else
+    a.ab_out = a.ab_out or os.path.join("profiles", "mx6_bench_ab.jsonl" if a.fp6 else "mx4_bench_ab.jsonl")
+    a.out = a.out or os.path.join("profiles", "mx6_vit_b16.jsonl" if a.fp6 else "mx4_vit_b16.jsonl" if a.fp4 else
                                   "mx_wgrad_vit_b16.jsonl" if a.wgrad else "fp8_vit_b16.jsonl")
-    if a.fp4:
-        return main_fp4(a)
+    if a.fp4 or a.fp6:
+        return main_fp4(a, a.fp6)
     if a.wgrad:
         return main_wgrad(a)
     M = a.tokens

@@ -11,8 +11,10 @@
 // scale scatter fills each operand's area exactly once with the dword order its reader expects. For the weight
 // gradient (mx_wgrad_check, mx_wgrad_splits): the shapes and split counts of tests/test_mx_wgrad_gpu.py and the
 // ViT-B/16 ones, wanted counts of 0, 1 and above the tile count, the split ranges (contiguous, none empty, within one
-// tile of each other) and the kernel's LDS row and scale-area maps over 256 rows. Exit status 0 and "ok" when all
-// hold.
+// tile of each other) and the kernel's LDS row and scale-area maps over 256 rows. For fp6 (formats 3 and 4): row bytes
+// 3 k / 4, strides padded to 16, every store of mx6_quant.hip's quads and columns and every chunk of mx6_gemm.hip's
+// loader inside its row, the loader's chunk map covering the LDS tile once, and the refused pairs. Exit status 0 and
+// "ok" when all hold.
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -86,6 +88,59 @@ static void walk_gemm(int64_t M, int64_t N, int64_t K) {
         if (n < N) EXPECT(n + 8 <= N);
       }
     }
+}
+
+// fp6: mx6_quant.hip's stores (a quad's 48 bytes of a row in chunks of 16 or a last 8; a lane's 48 bytes of a column)
+// and mx6_gemm.hip's loader (chunk t + 256 u = 6 rho + ch; 16 bytes, a last 8, or nothing) stay inside rows of
+// 3 k / 4 bytes, and the padded strides are what the checks ask for
+static void walk_fp6(int64_t R, int64_t C) {
+  const auto pad16 = [](int64_t n) { return (n + 15) / 16 * 16; };
+  const bool t = R % kMxBlock == 0;
+  for (int fmt : {kMxE2M3, kMxE3M2}) {
+    const int64_t qb = mx_row_bytes(C, fmt), tb = mx_row_bytes(R, fmt);
+    EXPECT(qb * 4 == C * 3 && qb % 24 == 0 && pad16(qb) - qb < 16 && pad16(qb) % 16 == 0);
+    const MxQuantGeometry g = mx_quant_check(X, R, C, C, fmt, Q, pad16(qb), S, mx_scale_row(C), t ? QT : nullptr, pad16(tb),
+                                             t ? ST : nullptr, mx_scale_row(R));
+    for (int64_t ct = 0; ct < g.col_tiles; ct += (g.col_tiles > 2 ? g.col_tiles - 1 : 1))
+      for (int quad = 0; quad < 2; ++quad) {
+        const int64_t left = C - (ct * kMxQTile + 64 * quad), bytes = left >= 64 ? 48 : (left >= 32 ? 24 : 0);
+        int64_t written = 0;
+        for (int j = 0; j < 3; ++j) {
+          const int64_t ofs = 96 * ct + 48 * quad + 16 * j, n = 16 * j + 16 <= bytes ? 16 : (16 * j + 8 <= bytes ? 8 : 0);
+          EXPECT(ofs % 16 == 0 && (n == 0 || ofs + n <= qb));
+          written += n;
+        }
+        EXPECT(written == bytes);
+      }
+    if (t)
+      for (int half = 0; half < 2; ++half) {
+        const int64_t rt = g.row_tiles - 1, left = R - (rt * kMxQTile + 64 * half), bytes = left >= 64 ? 48 : (left >= 32 ? 24 : 0);
+        for (int k = 0; k < 3; ++k) {
+          const int64_t n = 16 * k + 16 <= bytes ? 16 : (16 * k + 8 <= bytes ? 8 : 0);
+          EXPECT(n == 0 || 96 * rt + 48 * half + 16 * k + n <= tb);
+        }
+      }
+    // the GEMM with K = C: e2m3 B, this format as A
+    const Fp8GemmGeometry gg = mx_gemm_check(X, Q, QT, nullptr, 0, S, ST, R, 8, C, pad16(qb), pad16(qb), 8, mx_scale_row(C),
+                                             mx_scale_row(C), fmt, kMxE2M3);
+    EXPECT(static_cast<int64_t>(gg.k_tiles) * kMx6TileK >= C && static_cast<int64_t>(gg.k_tiles - 1) * kMx6TileK < C);
+    int64_t covered = 0;
+    for (int step = 0; step < gg.k_tiles; ++step)
+      for (int ch = 0; ch < kMx6RowBytes / 16; ++ch) {
+        const int64_t have = qb - step * kMx6RowBytes - ch * 16, n = have >= 16 ? 16 : (have >= 8 ? 8 : 0);
+        EXPECT(n == 0 || step * kMx6RowBytes + ch * 16 + n <= qb);
+        covered += n;
+      }
+    EXPECT(covered == qb);
+  }
+  std::vector<int> seen(kFp8Tile * (kMx6RowBytes / 16), 0);
+  for (int u = 0; u < 3; ++u)
+    for (int lane = 0; lane < kFp8Threads; ++lane) {
+      const int idx = lane + kFp8Threads * u, rho = idx / 6, ch = idx - 6 * rho;
+      EXPECT(rho < kFp8Tile && ch < 6);
+      if (rho < kFp8Tile) ++seen[rho * 6 + ch];
+    }
+  for (int v : seen) EXPECT(v == 1);
 }
 
 // mx_gemm.hip's scale area: the loader lane of LDS row rho writes byte (rho >> 4) & 3 of the dwords
@@ -193,6 +248,9 @@ int main() {
                                                           {1, kFp8MaxDim - 248, 32}, {1, 8, kFp8MaxDim - 224}})
     walk_gemm(m, n, k), ++shapes;
   walk_scale_area();
+  for (auto [r, c] : std::vector<std::array<int64_t, 2>>{{32, 32}, {128, 128}, {160, 416}, {32, 544}, {130, 160}, {1, 32},
+                                                         {50432, 768}, {2304, 768}, {50432, 2304}, {kFp8MaxDim, 32}})
+    walk_fp6(r, c), ++shapes;
   for (int64_t m : {1, 129, 300})
     for (int64_t n : {8, 264})
       for (auto [k, wanted] : std::vector<std::array<int64_t, 2>>{{32, 1}, {160, 2}, {416, 3}, {1312, 4}, {1312, 64}, {1312, 0}})
@@ -219,7 +277,12 @@ int main() {
   rejects("ld % 8", [&] { quant(160, 96, 100); });
   rejects("null input", [&] { quant(160, 96, 96, nullptr); });
   rejects("unaligned input", [&] { quant(160, 96, 96, mem + 2); });
-  rejects("format 2", [&] { quant(160, 96, 96, X, 2); });
+  quant(160, 96, 96, X, 2);  // e2m1: rows of C / 2 bytes fit the same strides
+  quant(160, 96, 96, X, 3), quant(160, 96, 96, X, 4);  // fp6: rows of 72 and 120 bytes in strides of 96 and 160
+  rejects("format 5", [&] { quant(160, 96, 96, X, 5); });
+  rejects("fp6 ldq < 3 C / 4", [&] { quant(160, 96, 96, X, 3, Q, 64); });
+  rejects("fp6 ldq % 16", [&] { quant(160, 96, 96, X, 3, Q, 72); });
+  rejects("fp6 ldt < 3 R / 4", [&] { quant(160, 96, 96, X, 4, Q, -1, S, -1, QT, 112); });
   rejects("q without scales", [&] { quant(160, 96, 96, X, 0, Q, -1, nullptr); });
   rejects("scales without q", [&] { quant(160, 96, 96, X, 0, nullptr); });
   rejects("qt without scales", [&] { quant(160, 96, 96, X, 0, Q, -1, S, -1, QT, -1, nullptr); });
@@ -270,6 +333,13 @@ int main() {
   rejects("format of a", [&] { gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 2); });
   rejects("e5m2 b", [&] { gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 0, 1); });
   rejects("too many workgroups", [&] { gemm(kFp8MaxDim, kFp8MaxDim - 248, 32); });
+  gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 3, 3);  // fp6 rows of 120 bytes in strides of 160
+  gemm(130, 136, 160, 128, 128, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 4, 3);
+  for (auto [fa, fb] : std::vector<std::array<int, 2>>{{3, 4}, {4, 4}, {0, 3}, {1, 3}, {2, 3}, {3, 0}, {4, 0}, {3, 2}, {4, 2}, {5, 3}})
+    rejects("a pair with an fp6 side that is not built",
+            [&, fa = fa, fb = fb] { gemm(130, 136, 160, -1, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, fa, fb); });
+  rejects("fp6 lda < 3 K / 4", [&] { gemm(130, 136, 160, 112, -1, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 3, 3); });
+  rejects("fp6 ldb % 16", [&] { gemm(130, 136, 160, -1, 120, -1, X, Q, QT, nullptr, 0, S, ST, -1, -1, 3, 3); });
 
   const auto wgrad = [&](int64_t M, int64_t N, int64_t K, int64_t splits = 1, int64_t lda = -1, int64_t ldb = -1,
                          const void* a = X, const void* b = Q, const void* ws = QT, const void* sa = S,
@@ -301,6 +371,8 @@ int main() {
   rejects("ldsb % 4", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, 16, 18); });
   rejects("format of a", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 2); });
   rejects("e5m2 b", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 0, 1); });
+  rejects("fp6 a", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 4, 0); });
+  rejects("fp6 b", [&] { wgrad(300, 264, 416, 1, -1, -1, X, Q, QT, S, ST, -1, -1, 0, 3); });
   rejects("too many workgroups", [&] { wgrad(kFp8MaxDim, kFp8MaxDim - 248, 32); });
   rejects("mx_wgrad_splits: K = 0", [&] { mx_wgrad_splits(0, 1); });
   rejects("mx_wgrad_splits: K % 32", [&] { mx_wgrad_splits(144, 2); });
