@@ -349,6 +349,14 @@ void maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int64_t N, int64_
 // mean / rstd per row (fp32) saved. w/b: fp32 or the activation dtype (wdtype), 16-byte aligned.
 void layernorm_fwd(const void* x, const void* residual, void* h, void* y, const void* w, const void* b, float* mean,
                    float* rstd, int64_t rows, int64_t D, float eps, int dtype, int wdtype, hipStream_t stream);
+// Linear + residual add + LayerNorm forward in one launch (gemm_ln.hip): h = bf16(a W^T + bias + x) (one rounding),
+// y = LN(h) * ln_w + ln_b of the stored h, mean / rstd per row; a [M][K], W [N][K], x / h / y [M][N] bf16, dense,
+// 16-byte aligned. N is 384 or 768, K a multiple of 64 (linear_add_ln_supported); bias and the affine bf16 or fp32
+// (bias_dtype, ln_wdtype). max_blocks caps the persistent grid (0 = the resident workgroups), as stem_fwd's does.
+bool linear_add_ln_supported(int64_t M, int64_t N, int64_t K);
+void linear_add_ln_fwd(const void* a, const void* W, const void* bias, const void* x, void* h, void* y, const void* ln_w,
+                       const void* ln_b, float* mean, float* rstd, int64_t M, int64_t N, int64_t K, float eps,
+                       int bias_dtype, int ln_wdtype, hipStream_t stream, int max_blocks = 0);
 // backward: dx = LN backward of dy [+ dh_ext]; per-workgroup [2][D] fp32 partials of (dw, db)
 // stored into `partials` (capacity max_blocks x 2D); returns the number of partial rows written
 // (sum them with gemm_splitk_reduce). colsum (dh_ext required): [3][D] rows, the third the

@@ -451,3 +451,14 @@ PYBIND11_MODULE(_C_mx, m) {
   m.attr("MX_WGRAD_TILE") = kMxWgTile;
   m.attr("MX_WGRAD_PER_CU") = kMxWgPerCu;
 }
+
+// A third module of the same shared object (ops/_ext.py: ln()): the Linear + residual add + LayerNorm forward
+// (csrc/kernels/gemm_ln.hip), beside `_C` for the same reason as `_C_mx`.
+PYBIND11_MODULE(_C_ln, m) {
+  m.doc() = "fluxmpi_amd native library: the fused Linear + add + LayerNorm forward (csrc/kernels/gemm_ln.hip)";
+  m.def("linear_add_ln_supported", &linear_add_ln_supported, py::arg("M"), py::arg("N"), py::arg("K"));
+  m.def("linear_add_ln_fwd", raw(&linear_add_ln_fwd), py::arg("a"), py::arg("W"), py::arg("bias"), py::arg("x"),
+        py::arg("h"), py::arg("y"), py::arg("ln_w"), py::arg("ln_b"), py::arg("mean"), py::arg("rstd"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("eps"), py::arg("bias_dtype"), py::arg("ln_wdtype"), py::arg("stream"),
+        py::arg("max_blocks") = 0);
+}

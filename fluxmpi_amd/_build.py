@@ -89,13 +89,15 @@ EXTRA_FLAGS["mx_gemm.hip"] = EXTRA_FLAGS["mx_quant.hip"] = EXTRA_FLAGS["patch_em
 EXTRA_FLAGS["mx_wgrad.hip"] = EXTRA_FLAGS["patch_embed.hip"]  # profiles/mx_wgrad_resources.md
 EXTRA_FLAGS["mx4_gemm.hip"] = EXTRA_FLAGS["mx4_quant.hip"] = EXTRA_FLAGS["patch_embed.hip"]  # profiles/mx4_resources.md
 EXTRA_FLAGS["mx6_gemm.hip"] = EXTRA_FLAGS["mx6_quant.hip"] = EXTRA_FLAGS["patch_embed.hip"]  # profiles/mx6_resources.md
+# gemm_ln.hip's epilogue is fp32 add / fma chains over 8 adjacent values beside MFMAs (profiles/gemm_ln_resources.md)
+EXTRA_FLAGS["gemm_ln.hip"] = EXTRA_FLAGS["patch_embed.hip"]
 
 
 # kernels tuned to sit just under the 256-VGPR limit: a compiler that starts to spill them must show
 # at build time, not as a slow step (the resource remarks of their compile are checked for scratch)
 NO_SCRATCH = ("conv3bn3_bwd.hip", "conv3ds_bwd.hip", "bn_relu_conv1x1_fwd.hip", "xent.hip", "conv3bn3_s2_bwd.hip",
               "resize_crop.hip", "patch_embed.hip", "gemm_fp8.hip", "fp8_quant.hip", "mx_gemm.hip", "mx_quant.hip",
-              "mx_wgrad.hip", "mx4_gemm.hip", "mx4_quant.hip", "mx6_gemm.hip", "mx6_quant.hip")
+              "mx_wgrad.hip", "mx4_gemm.hip", "mx4_quant.hip", "mx6_gemm.hip", "mx6_quant.hip", "gemm_ln.hip")
 
 
 def _check_no_scratch(src: str, remarks: str) -> None:

@@ -109,6 +109,11 @@ def mx():
     return submodule("_C_mx", "the MX fp8 entries")
 
 
+def ln():
+    """The ``_C_ln`` module (``linear_add_ln_supported``, ``linear_add_ln_fwd``; ``csrc/kernels/gemm_ln.hip``)."""
+    return submodule("_C_ln", "the fused Linear + add + LayerNorm forward")
+
+
 def require_for(t: torch.Tensor):
     """The extension if ``t`` lives on the GPU (mandatory there), else ``None``."""
     if t.is_cuda:

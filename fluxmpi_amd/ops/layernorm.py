@@ -10,6 +10,8 @@ atomics). CPU tensors (and unsupported shapes) use the PyTorch composition.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -164,13 +166,17 @@ class _LinearAddLayerNormFn(torch.autograd.Function):
     kernel over dx; the weight gradient runs on the split-K HIP kernel (ops/linear.py)."""
 
     @staticmethod
-    def forward(ctx, a, weight, bias, x, ln_w, ln_b, eps, gelu_link=None):
+    @staticmethod
+    def forward(ctx, a, weight, bias, x, ln_w, ln_b, eps, gelu_link=None, fused=False):
         from .linear import fwd
-        p = fwd(a, weight, bias)
         ctx.gelu_link = gelu_link
         x = x.contiguous()
         w, b = _affine(x, ln_w, ln_b)
-        h, y, mean, rstd = _fwd(x, p.contiguous(), w, b, eps)
+        if fused and _fused_fwd_ok(a, weight, bias, x, w, b):
+            h, y, mean, rstd = _fused_fwd(a, weight, bias, x, w, b, eps)
+        else:
+            p = fwd(a, weight, bias)
+            h, y, mean, rstd = _fwd(x, p.contiguous(), w, b, eps)
         ctx.save_for_backward(a, weight, h, w, mean, rstd)
         ctx.weight = weight  # the leaf itself: its gradient's bucket slice (ops/graddst.py)
         ctx.dtypes = (ln_w.dtype if ln_w is not None else None, ln_b.dtype if ln_b is not None else None)
@@ -222,14 +228,53 @@ class _LinearAddLayerNormFn(torch.autograd.Function):
         return da, dw, (dbias if ctx.needs_input_grad[2] else None), dx, dlw, dlb, None, None
 
 
-def linear_add_layer_norm(a, weight, bias, x, ln_w, ln_b, eps=1e-5, gelu_link=None):
+class _LinearAddLayerNormGemmFn(_LinearAddLayerNormFn):
+    """The same node (and the same backward) with the forward as ONE launch where the shape allows it: a GEMM
+    whose workgroup owns whole output rows adds the bias and the residual and normalises in its epilogue
+    (``csrc/kernels/gemm_ln.hip``), so the projection output is never written. ``h`` is rounded once there (the
+    composition rounds the projection, then the sum), hence opt-in and not bit-identical to the composition."""
+
+    @staticmethod
+    def forward(ctx, a, weight, bias, x, ln_w, ln_b, eps, gelu_link=None):
+        return _LinearAddLayerNormFn.forward(ctx, a, weight, bias, x, ln_w, ln_b, eps, gelu_link, True)
+
+
+def _fused_fwd_ok(a, weight, bias, x, w, b) -> bool:
+    n, k = weight.shape
+    ts = (a, weight, bias, x, w, b)
+    return (x.dtype == torch.bfloat16 and bias.dtype in (torch.bfloat16, torch.float32) and w.dtype == b.dtype
+            and weight.is_contiguous() and bias.is_contiguous() and all(t.data_ptr() % 16 == 0 for t in ts)
+            and _ext.ln().linear_add_ln_supported(x.numel() // n, n, k))
+
+
+def _fused_fwd(a, weight, bias, x, w, b, eps):
+    n, k = weight.shape
+    rows = x.numel() // n
+    h, y = torch.empty_like(x), torch.empty_like(x)
+    mean = torch.empty(rows, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    _ext.ln().linear_add_ln_fwd(a.data_ptr(), weight.data_ptr(), bias.data_ptr(), x.data_ptr(), h.data_ptr(),
+                                y.data_ptr(), w.data_ptr(), b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, n, k,
+                                float(eps), DTYPE_CODE[bias.dtype], DTYPE_CODE[w.dtype], _stream(x))
+    return h, y, mean, rstd
+
+
+# FLUXMPI_LINEAR_LN=gemm (read once, at import): linear_add_layer_norm's forward on gemm_ln.hip by default
+_FUSED_FWD_DEFAULT = os.environ.get("FLUXMPI_LINEAR_LN", "") == "gemm"
+
+
+def linear_add_layer_norm(a, weight, bias, x, ln_w, ln_b, eps=1e-5, gelu_link=None, fused_fwd: bool | None = None):
     """``(h, layer_norm(h))`` with ``h = x + F.linear(a, weight, bias)`` (see
     :class:`_LinearAddLayerNormFn`); the PyTorch composition off the fused path. ``gelu_link``
     (:class:`ops.gelu.GeluLink`): ``a`` is ``linear_gelu(..., link=gelu_link)``'s output, whose
-    GELU backward this node's input-gradient GEMM then performs."""
+    GELU backward this node's input-gradient GEMM then performs. ``fused_fwd``: the forward as one launch
+    (:class:`_LinearAddLayerNormGemmFn`; bf16, N of 384 or 768, K a multiple of 64, else today's two launches);
+    ``None`` takes the ``FLUXMPI_LINEAR_LN=gemm`` switch, off by default."""
     if (supported(x) and bias is not None and a.is_contiguous() and a.shape[:-1] == x.shape[:-1]
             and weight.shape[0] == x.shape[-1] and a.dtype == x.dtype == weight.dtype and torch.is_grad_enabled()
             and (ln_w is None or ln_w.shape[-1] == x.shape[-1])):
+        if _FUSED_FWD_DEFAULT if fused_fwd is None else fused_fwd:
+            return _LinearAddLayerNormGemmFn.apply(a, weight, bias, x, ln_w, ln_b, eps, gelu_link)
         return _LinearAddLayerNormFn.apply(a, weight, bias, x, ln_w, ln_b, eps, gelu_link)
     from .linear import linear
     return add_layer_norm(x, linear(a, weight, bias), ln_w, ln_b, eps)
